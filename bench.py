@@ -3,7 +3,7 @@
 1 GPU (per rank), batch = 256 synthetic scenes, diff robot, 1000 obstacle points, T = 10,
 K = 10 PAN iterations (iter_threshold = 0 so that exactly K run), fp32 DUNE + fp64 QP.
 
-    python bench.py [--gpus N --steps K --warmup W]          # (N > 1 without a launcher: re-executes itself as below)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   # (N > 1 without a launcher: runs itself as below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the hot path (one forward call: K x {selection, QP}) over one batch of 256 scenes per
@@ -16,11 +16,22 @@ Every step still executes its full K iterations inside the timed region, on its 
 buffers and its own planner state; `--chains 0` gives one stream and one launch chain per step (round 4's
 schedule), `--inflight 1` the strictly sequential number.
 
-OUTPUT: the LAST stdout line is ONE compact JSON record (<= 6 KB: the contract fields, `roofline`,
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs of the last timed step when
+--dump-outputs DIR is given, and ONE JSON line on stdout (the contract fields, `config`, `host_issue_ms_per_step`,
+`region_ms`).  Everything else the bench measures or checks runs with --full only (the legs below).
+
+--dump-outputs DIR: after the timed steps, the arrays the timed path returned for its LAST step (the output dict of that
+step's forward call: opt_s, opt_u, opt_d, min_distance, iters, nrmp_points; with a process group also the gathered
+controls) go to DIR/<name>.npy, float32 or float64 (integers as float64), rank 0.  The inputs depend on the arguments
+only, so two builds run with the same arguments can be compared output for output.
+
+OUTPUT with --full: the LAST stdout line is ONE compact JSON record (<= 6 KB: the contract fields, `roofline`,
 `cpu_baseline`, the parity verdicts and one figure per extra leg); the full record (per-scene listings, PMC
 dump, CPU sweep, notes) goes to bench_full.json next to this file (NPA_BENCH_FULL=path moves it).
 
-Besides the headline the record carries (rank 0, one GPU, unless --no-extras):
+With --full the record also carries `roofline` (interior-point iterations counted on the device in an untimed step, PMC
+records of profiles/), `margin_audit`, `latency_B1_ms` (unless --no-latency), `cpu_baseline` and `parity` (rank 0, one
+GPU, unless --no-cpu) and (rank 0, one GPU, unless --no-extras):
   extra.paths          the SAME loop with the un-pruned / fallback selections: exact fp32 network keys over every point
                        (NPA_DUNE_FP32KEYS=1: SURVEY 8(d)'s literal "encoder on every obstacle point x horizon step"), network
                        keys with single / split fp16 products (NPA_KEY_TERMS=1 / 3), each with the encoder's executed MFMA
@@ -499,9 +510,33 @@ def slim(rep):
     return out
 
 
+DUMP_LIMIT = 64 << 20                        # bytes of --dump-outputs in all
+
+
+def dump_outputs(d, last_step, with_gathered=False):
+    """--dump-outputs: the arrays the timed path returned for its LAST step -- the output dict of that step's forward call and,
+    under a process group, the all-gathered controls (world, B, 2, T) as gathered_u -- as d/<name>.npy in float32 / float64
+    (integers as float64).  Above DUMP_LIMIT in all, every array keeps the same fixed, seeded sample of the B scenes of the
+    step (axis 0 of the output dict's arrays, axis 1 of gathered_u: the same scene positions in every rank's shard)."""
+    o, g = last_step
+    arrays = {k: v.detach().cpu().numpy() for k, v in o.items() if isinstance(v, torch.Tensor)}
+    B = o["opt_u"].shape[0]
+    if with_gathered and isinstance(g, torch.Tensor):
+        arrays["gathered_u"] = g.detach().cpu().numpy().reshape(-1, *o["opt_u"].shape)
+    arrays = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(0).choice(B, max(1, B * DUMP_LIMIT // total), replace=False))
+        arrays = {k: a[:, rows] if k == "gathered_u" else a[rows] for k, a in arrays.items()}
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), np.ascontiguousarray(a))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher around it: the same command again under torch.distributed.run, one rank
-    per GPU (what the round driver does itself for N > 1; a bare call should not die in argument handling)."""
+    per GPU (the way N > 1 ranks are launched; a bare call should not die in argument handling).  Run as a child process;
+    its exit status is this process's."""
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
@@ -509,7 +544,8 @@ def self_launch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), *sys.argv[1:]]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.call(cmd))
 
 
 def dry_run(args):
@@ -574,29 +610,31 @@ def _r(x, n=4):
 
 
 def compact(line, full_path):
-    """The record the driver parses: <= COMPACT_LIMIT bytes, every contract key, scalars only below them."""
+    """The last stdout line: <= COMPACT_LIMIT bytes, every contract key, scalars only below them.  full_path None: no full
+    record was written (a plain run)."""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data")
     out = {k: line[k] for k in keep}
     c = line["config"]
     out["config"] = {k: c[k] for k in ("workload", "scenes_per_gpu", "points", "T", "K", "M", "batches_in_flight", "chains",
                                        "issue_threads", "parallelism") if k in c}
-    out["config"]["scenes_per_launch"] = line["roofline"].get("scenes_per_launch")
-    r = line["roofline"]
-    ro = {k: r.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "scenes_per_launch",
-                                "select_launch_ms", "launches_timed", "ipm_iterations_per_launch", "flops_per_launch", "frac_alone",
-                                "valu_issue_frac_alone", "lds_bank_conflict_frac", "algorithmic_bytes_per_launch")}
-    if r.get("chip_aggregate"):
-        ro["chip_aggregate"] = r["chip_aggregate"]
-    if r.get("vector_pipe"):
-        ro["vector_pipe"] = {k: r["vector_pipe"][k] for k in ("simd_cycles_per_plan", "bound_plans_per_s", "frac")}
-    if r.get("pmc"):
-        pk = r["pmc"].get("per_kernel", {})
-        ro["pmc"] = {"file": r["pmc"].get("file"), "current": {k: v.get("current") for k, v in pk.items()}}
-    if r.get("select"):
-        ro["select"] = {k: r["select"].get(k) for k in ("kernel", "launch_ms", "mfma_tflops", "mfma_peak", "mfma_frac", "traffic",
-                                                        "algorithmic_bytes_per_launch")}
-    out["roofline"] = ro
+    r = line.get("roofline")           # (a plain run: the headline only, no roofline)
+    if r is not None:
+        out["config"]["scenes_per_launch"] = r.get("scenes_per_launch")
+        ro = {k: r.get(k) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "scenes_per_launch",
+                                    "select_launch_ms", "launches_timed", "ipm_iterations_per_launch", "flops_per_launch", "frac_alone",
+                                    "valu_issue_frac_alone", "lds_bank_conflict_frac", "algorithmic_bytes_per_launch")}
+        if r.get("chip_aggregate"):
+            ro["chip_aggregate"] = r["chip_aggregate"]
+        if r.get("vector_pipe"):
+            ro["vector_pipe"] = {k: r["vector_pipe"][k] for k in ("simd_cycles_per_plan", "bound_plans_per_s", "frac")}
+        if r.get("pmc"):
+            pk = r["pmc"].get("per_kernel", {})
+            ro["pmc"] = {"file": r["pmc"].get("file"), "current": {k: v.get("current") for k, v in pk.items()}}
+        if r.get("select"):
+            ro["select"] = {k: r["select"].get(k) for k in ("kernel", "launch_ms", "mfma_tflops", "mfma_peak", "mfma_frac", "traffic",
+                                                            "algorithmic_bytes_per_launch")}
+        out["roofline"] = ro
     if "cpu_baseline" in line:
         cb = line["cpu_baseline"]
         out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -650,7 +688,8 @@ def compact(line, full_path):
         # scenes_per_launch scenes -- the rate of the one-launch-chain-per-step schedule rides in the part that is never dropped
         if isinstance((x.get("launch_shapes") or {}).get("one_chain_per_step"), dict):
             out["config"]["plans_per_s_one_chain_per_step"] = x["launch_shapes"]["one_chain_per_step"]["plans_per_s"]
-    out["full_record"] = full_path
+    if full_path is not None:
+        out["full_record"] = full_path
     # never above the limit: drop the least essential parts first
     for drop in (("extra", "launch_shapes"), ("extra", "paths"), ("parity", "gpu_last_qp"), ("roofline", "pmc"), ("extra", "other_configs"),
                  ("extra", None)):
@@ -664,13 +703,15 @@ def compact(line, full_path):
                 del out[a][b]
     if len(json.dumps(out)) > COMPACT_LIMIT:
         # last resort: the contract keys, the two required objects at their required keys, nothing else -- a line is ALWAYS printed
-        r = out["roofline"]
+        r = out.get("roofline")
         out = {k: out[k] for k in keep + ("config",)}
-        out["roofline"] = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel")}
+        if r is not None:
+            out["roofline"] = {k: r.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel")}
         if "cpu_baseline" in line:
             cb = line["cpu_baseline"]
             out["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"], "sample": cb["sample"][:120]}
-        out["full_record"] = full_path
+        if full_path is not None:
+            out["full_record"] = full_path
     return out
 
 
@@ -708,10 +749,17 @@ def main():
                     choices=sorted(k for k in __import__("neupan_amd.scenes", fromlist=["CONFIGS"]).CONFIGS),
                     help="scene configuration (default: the one BASELINE.json's metric is quoted on)")
     ap.add_argument("--batch", type=int, default=BATCH, help="scenes per step and GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned for its last step to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: roofline, margin audit, latency, CPU baseline and parity, "
+                         "the extra legs (each still subject to --no-latency / --no-cpu / --no-extras)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
-        self_launch(args.gpus)                  # (does not return)
+        self_launch(args.gpus)                  # (exits with the launcher's status)
     if args.dry_run:
         return dry_run(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -775,113 +823,117 @@ def main():
         elapsed = float(tmax.item())
     out, gathered = last[0]
     timed_u = out["opt_u"].cpu().numpy().copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[(args.steps - 1) % nfl], with_gathered=dist is not None)
 
     plans = B * world * args.steps
     value = plans / elapsed
     km = lp.pans[0].key_mode()
 
-    # the run-time audit of the geometric-key margin over everything this process launched so far (all planners): a
-    # violation would mean plans computed from a wrong selection -- the number is reported AND must be zero
-    audit = lp.audit()
-    assert audit["violations"] == 0, f"geometric-key margin violated at run time: {audit}"
-
-    # ---- roofline of the dominant kernel -------------------------------------------------------------------------
-    # The step is dominated by the QP: a serial fp64 interior-point chain, one wave per scene -- VALU / latency bound, no MFMA,
-    # no HBM stream.  Work per launch = interior-point iterations the launch executes (MEASURED HERE on the device: qp_info of
-    # every scene after every PAN iteration of one untimed step) x fp64 flops per iteration + a fixed part per solve (set-up,
-    # write-out, stop test); the two per-unit figures come from PMC counts (SQ_INSTS_VALU_{ADD,MUL,FMA}_F64 x 64 lanes, FMA x2)
-    # at two operating points (warm / cold solves), tests/tools/pmc_collect.py -> profiles/r04_pmc.json, DESIGN.md section 6.
-    # Launch time: HIP events on the launches' own stream, inside the timed region.  SURVEY 8(d)'s figure -- algorithmic dense
-    # flops of the encoder over the fp32-MFMA peak -- is not the denominator of the default path: with geometric keys the
-    # encoder runs on ~2 % of the points (943 Mflop/plan x this rate would be 4x the peak); extra.paths reports it for the
-    # un-pruned selections, roofline.select for the default one.
-    pmc = load_pmc(args.workload)
-    its = lp.qp_iterations()
     # steps that share a launch (merged chains): the members of a chain, <= 8 per run (a full round of the slots; a trailing
     # partial round has shorter runs -- the default step counts are whole rounds)
     mem = (nfl + lp.chains - 1) // lp.chains if lp.chains else 1
     mem = (mem + ((mem + 7) // 8) - 1) // ((mem + 7) // 8)
     spl = B * mem                               # scenes per launch
-    its_per_launch = float(np.mean([s for s, _ in its])) * mem      # (batch 0's count stands for its chain mates)
-    qp_ms, sel_ms, dune_ms = prof["nrmp_ms"], prof["select_ms"], prof["dune_ms"]
-    qp_name = "nrmp_qp_group_kernel" if lp.chains else "nrmp_qp_kernel"
-    sel_name = "select_geo_group_kernel" if lp.chains else "select_geo_kernel"
-    roof = {"bound": "valu", "kernel": f"{qp_name}<{T},{cfg.nrmp_max_num}>", "unit": "TFLOP/s", "peak": PEAK_FP64_VALU_TFLOPS,
-            "launch_ms": round(qp_ms, 4), "scenes_per_launch": spl, "launches_timed": prof["launches"], "select_launch_ms": round(sel_ms, 4),
-            "dune_launch_ms": round(dune_ms, 4), "key_mode": km, "achieved": None, "frac": None, "traffic": None,
-            "ipm_iterations_per_launch": round(its_per_launch, 1),
-            "ipm_iterations_by_pan_iteration": [[int(s), int(m)] for s, m in its]}
-    kq = (pmc["kernels"].get(qp_name) or pmc["kernels"].get("nrmp_qp_kernel")) if pmc else None
-    if kq:
-        kq_spl = kq.get("scenes_per_launch", pmc["scenes_per_launch"])
-        model = pmc.get("qp_flops_model")
-        if model:
-            flops = model["per_iteration"] * its_per_launch + model["per_solve"] * spl
-            roof["flops_model"] = dict(model, units="fp64 flop per interior-point iteration of one scene / per solve")
-        else:                                   # (a record without the two-point fit: its launch average, scaled to this batch)
-            flops = kq["fp64_flops_per_launch"] * spl / kq_spl
-        roof["achieved"] = round(flops / (qp_ms * 1e-3) / 1e12, 4) if qp_ms > 0 else None
-        roof["frac"] = round(roof["achieved"] / PEAK_FP64_VALU_TFLOPS, 5) if roof["achieved"] else None
-        roof["flops_per_launch"] = int(flops)
-        roof["traffic"] = int(kq["hbm_bytes_per_launch"] * spl / kq_spl)
-        # algorithmic bytes of the QP launch: the rows it consumes (T+1 slices x M x (E + 5) floats + counts), the nominal in
-        # and out, the references and the outputs -- what a fused loop would still have to move is far less
-        roof["algorithmic_bytes_per_launch"] = int(spl * 4 * ((T + 1) * cfg.nrmp_max_num * (E + 5) + (T + 1) + 4 * (3 * (T + 1) + 2 * T) + 3 * T))
-        roof["valu_issue_frac_alone"] = kq.get("valu_issue_frac")
-        roof["frac_alone"] = (round(flops * (kq_spl / spl) / (kq["avg_ms_alone"] * 1e-3) / 1e12 / PEAK_FP64_VALU_TFLOPS, 5)
-                              if kq.get("avg_ms_alone") else None)
-        roof["lds_bank_conflict_frac"] = kq.get("lds_bank_conflict_frac")
-        # the chip's fp64 rate over the whole timed region: every QP launch of every chain / wall time
-        agg = flops / mem * K * args.steps / elapsed / 1e12
-        roof["chip_aggregate"] = {"tflops": round(agg, 3), "frac": round(agg / PEAK_FP64_VALU_TFLOPS, 5)}
-        roof["pmc"] = {"file": pmc["_file"],
-                       "per_kernel": {k: dict({kk: v[kk] for kk in ("valu_insts_per_launch", "valu_issue_frac", "hbm_bytes_per_launch",
-                                                                      "avg_ms_alone", "mfma_busy_frac", "source_hash", "isa_hash") if kk in v},
-                                                  current=record_is_current(k, v))
-                                      for k, v in pmc["kernels"].items()}}
-    ks = (pmc["kernels"].get(sel_name) or pmc["kernels"].get("select_geo_kernel")) if pmc else None
-    if ks and sel_ms > 0 and "SQ_INSTS_MFMA" in ks.get("counters", {}):
-        # the exact encoder's matrix work: executed v_mfma_f32_32x32x2_f32 (4096 flop each) over the fp32-MFMA peak
-        ks_spl = ks.get("scenes_per_launch", pmc["scenes_per_launch"])
-        mf = ks["counters"]["SQ_INSTS_MFMA"] * 4096.0 * spl / ks_spl
-        roof["select"] = {"kernel": f"{sel_name}<{E}>", "launch_ms": round(sel_ms, 4), "mfma_flops_per_launch": int(mf),
-                          "mfma_tflops": round(mf / (sel_ms * 1e-3) / 1e12, 3), "mfma_peak": PEAK_FP32_MFMA_TFLOPS,
-                          "mfma_frac": round(mf / (sel_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 5),
-                          "valu_issue_frac_alone": ks.get("valu_issue_frac"), "mfma_busy_frac_alone": ks.get("mfma_busy_frac"),
-                          "traffic": int(ks["hbm_bytes_per_launch"] * spl / ks_spl),
-                          "algorithmic_bytes_per_launch": int(spl * (8 * N * (2 if lp.args[0][5] is not None else 1) + 400))}
-    # the loop as a whole against the chip's vector pipes: SIMD-cycles the two kernels keep a SIMD's VALU or MFMA pipe busy per
-    # plan (PMC: 4 x SQ_ACTIVE_INST_VALU quad-cycles + SQ_VALU_MFMA_BUSY_CYCLES per launch, alone on the chip; fp32 MFMA and VALU
-    # do not co-execute on gfx950) -> the rate at which 1024 SIMDs at 2.4 GHz would run THIS instruction mix with no idle cycle
-    if pmc and km["key_terms"] == 4:
-        def pipe_cycles(name):
-            k_ = pmc["kernels"].get(name)
-            c_ = (k_ or {}).get("counters", {})
-            if "SQ_ACTIVE_INST_VALU" not in c_:
-                return None
-            return (4.0 * c_["SQ_ACTIVE_INST_VALU"] + c_.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0)) / k_.get("scenes_per_launch", pmc["scenes_per_launch"])
-        pc_sel = pipe_cycles(sel_name) or pipe_cycles("select_geo_kernel")
-        pc_qp = pipe_cycles(qp_name) or pipe_cycles("nrmp_qp_kernel")
-        pc_st = pipe_cycles("stage_group_kernel" if lp.chains else "stage_kernel") or 0.0
-        if pc_sel and pc_qp and args.workload == WORKLOAD:
-            per_plan = K * (pc_sel + pc_qp) + pc_st
-            bound = N_SIMD * 2.4e9 / per_plan
-            roof["vector_pipe"] = {"simd_cycles_per_plan": int(per_plan), "selection_share": round(K * pc_sel / per_plan, 3),
-                                   "bound_plans_per_s": int(bound), "frac": round(value / world / bound, 4),
-                                   "note": "VALU + MFMA busy SIMD-cycles of selection, QP and staging per plan (PMC, kernels alone) -> plans/s "
-                                           "of 1024 SIMDs at 2.4 GHz with no idle cycle; frac = this run's rate per GPU over it"}
-    roof["note"] = ("dominant kernel by GPU time = the QP (fp64 Mehrotra IPM, one wave per scene, serial chain: latency / VALU-issue "
-                    "bound).  achieved = (interior-point iterations per launch, measured on the device in this run) x (fp64 flops per "
-                    "iteration) + solves x (fixed flops per solve), the two per-unit figures from PMC counts at two operating points "
-                    "(roofline.flops_model), / launch time measured here with HIP events on the launch's stream (other batches' kernels "
-                    "co-run on the same SIMDs; frac_alone: over the kernel's duration alone on the chip; chip_aggregate: all QP "
-                    "launches of the region over its wall time); nothing is priced above what it executes.  DUNE: " +
-                    ("geometric distance keys inside select_geo_kernel nominate the candidates, the exact fp32-MFMA encoder runs on "
-                     "those only (~1.1 tiles of 32 points per slice instead of N/32); no dune_kernel launch" if km["key_terms"] == 4
-                     else f"network keys (mode {km['key_terms']}) from dune_kernel over every point, exact re-encode of the candidates"))
-    mfd = dune_mfma_rate(km, cfg, B, dune_ms, args.steps, elapsed)
-    if mfd:
-        roof["dune_executed_mfma"] = mfd
+    roof = audit = None
+    if args.full:
+        # the run-time audit of the geometric-key margin over everything this process launched so far (all planners): a
+        # violation would mean plans computed from a wrong selection -- the number is reported AND must be zero
+        audit = lp.audit()
+        assert audit["violations"] == 0, f"geometric-key margin violated at run time: {audit}"
+
+        # ---- roofline of the dominant kernel -------------------------------------------------------------------------
+        # The step is dominated by the QP: a serial fp64 interior-point chain, one wave per scene -- VALU / latency bound, no MFMA,
+        # no HBM stream.  Work per launch = interior-point iterations the launch executes (MEASURED HERE on the device: qp_info of
+        # every scene after every PAN iteration of one untimed step) x fp64 flops per iteration + a fixed part per solve (set-up,
+        # write-out, stop test); the two per-unit figures come from PMC counts (SQ_INSTS_VALU_{ADD,MUL,FMA}_F64 x 64 lanes, FMA x2)
+        # at two operating points (warm / cold solves), tests/tools/pmc_collect.py -> profiles/r04_pmc.json, DESIGN.md section 6.
+        # Launch time: HIP events on the launches' own stream, inside the timed region.  SURVEY 8(d)'s figure -- algorithmic dense
+        # flops of the encoder over the fp32-MFMA peak -- is not the denominator of the default path: with geometric keys the
+        # encoder runs on ~2 % of the points (943 Mflop/plan x this rate would be 4x the peak); extra.paths reports it for the
+        # un-pruned selections, roofline.select for the default one.
+        pmc = load_pmc(args.workload)
+        its = lp.qp_iterations()
+        its_per_launch = float(np.mean([s for s, _ in its])) * mem      # (batch 0's count stands for its chain mates)
+        qp_ms, sel_ms, dune_ms = prof["nrmp_ms"], prof["select_ms"], prof["dune_ms"]
+        qp_name = "nrmp_qp_group_kernel" if lp.chains else "nrmp_qp_kernel"
+        sel_name = "select_geo_group_kernel" if lp.chains else "select_geo_kernel"
+        roof = {"bound": "valu", "kernel": f"{qp_name}<{T},{cfg.nrmp_max_num}>", "unit": "TFLOP/s", "peak": PEAK_FP64_VALU_TFLOPS,
+                "launch_ms": round(qp_ms, 4), "scenes_per_launch": spl, "launches_timed": prof["launches"], "select_launch_ms": round(sel_ms, 4),
+                "dune_launch_ms": round(dune_ms, 4), "key_mode": km, "achieved": None, "frac": None, "traffic": None,
+                "ipm_iterations_per_launch": round(its_per_launch, 1),
+                "ipm_iterations_by_pan_iteration": [[int(s), int(m)] for s, m in its]}
+        kq = (pmc["kernels"].get(qp_name) or pmc["kernels"].get("nrmp_qp_kernel")) if pmc else None
+        if kq:
+            kq_spl = kq.get("scenes_per_launch", pmc["scenes_per_launch"])
+            model = pmc.get("qp_flops_model")
+            if model:
+                flops = model["per_iteration"] * its_per_launch + model["per_solve"] * spl
+                roof["flops_model"] = dict(model, units="fp64 flop per interior-point iteration of one scene / per solve")
+            else:                                   # (a record without the two-point fit: its launch average, scaled to this batch)
+                flops = kq["fp64_flops_per_launch"] * spl / kq_spl
+            roof["achieved"] = round(flops / (qp_ms * 1e-3) / 1e12, 4) if qp_ms > 0 else None
+            roof["frac"] = round(roof["achieved"] / PEAK_FP64_VALU_TFLOPS, 5) if roof["achieved"] else None
+            roof["flops_per_launch"] = int(flops)
+            roof["traffic"] = int(kq["hbm_bytes_per_launch"] * spl / kq_spl)
+            # algorithmic bytes of the QP launch: the rows it consumes (T+1 slices x M x (E + 5) floats + counts), the nominal in
+            # and out, the references and the outputs -- what a fused loop would still have to move is far less
+            roof["algorithmic_bytes_per_launch"] = int(spl * 4 * ((T + 1) * cfg.nrmp_max_num * (E + 5) + (T + 1) + 4 * (3 * (T + 1) + 2 * T) + 3 * T))
+            roof["valu_issue_frac_alone"] = kq.get("valu_issue_frac")
+            roof["frac_alone"] = (round(flops * (kq_spl / spl) / (kq["avg_ms_alone"] * 1e-3) / 1e12 / PEAK_FP64_VALU_TFLOPS, 5)
+                                  if kq.get("avg_ms_alone") else None)
+            roof["lds_bank_conflict_frac"] = kq.get("lds_bank_conflict_frac")
+            # the chip's fp64 rate over the whole timed region: every QP launch of every chain / wall time
+            agg = flops / mem * K * args.steps / elapsed / 1e12
+            roof["chip_aggregate"] = {"tflops": round(agg, 3), "frac": round(agg / PEAK_FP64_VALU_TFLOPS, 5)}
+            roof["pmc"] = {"file": pmc["_file"],
+                           "per_kernel": {k: dict({kk: v[kk] for kk in ("valu_insts_per_launch", "valu_issue_frac", "hbm_bytes_per_launch",
+                                                                          "avg_ms_alone", "mfma_busy_frac", "source_hash", "isa_hash") if kk in v},
+                                                      current=record_is_current(k, v))
+                                          for k, v in pmc["kernels"].items()}}
+        ks = (pmc["kernels"].get(sel_name) or pmc["kernels"].get("select_geo_kernel")) if pmc else None
+        if ks and sel_ms > 0 and "SQ_INSTS_MFMA" in ks.get("counters", {}):
+            # the exact encoder's matrix work: executed v_mfma_f32_32x32x2_f32 (4096 flop each) over the fp32-MFMA peak
+            ks_spl = ks.get("scenes_per_launch", pmc["scenes_per_launch"])
+            mf = ks["counters"]["SQ_INSTS_MFMA"] * 4096.0 * spl / ks_spl
+            roof["select"] = {"kernel": f"{sel_name}<{E}>", "launch_ms": round(sel_ms, 4), "mfma_flops_per_launch": int(mf),
+                              "mfma_tflops": round(mf / (sel_ms * 1e-3) / 1e12, 3), "mfma_peak": PEAK_FP32_MFMA_TFLOPS,
+                              "mfma_frac": round(mf / (sel_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 5),
+                              "valu_issue_frac_alone": ks.get("valu_issue_frac"), "mfma_busy_frac_alone": ks.get("mfma_busy_frac"),
+                              "traffic": int(ks["hbm_bytes_per_launch"] * spl / ks_spl),
+                              "algorithmic_bytes_per_launch": int(spl * (8 * N * (2 if lp.args[0][5] is not None else 1) + 400))}
+        # the loop as a whole against the chip's vector pipes: SIMD-cycles the two kernels keep a SIMD's VALU or MFMA pipe busy per
+        # plan (PMC: 4 x SQ_ACTIVE_INST_VALU quad-cycles + SQ_VALU_MFMA_BUSY_CYCLES per launch, alone on the chip; fp32 MFMA and VALU
+        # do not co-execute on gfx950) -> the rate at which 1024 SIMDs at 2.4 GHz would run THIS instruction mix with no idle cycle
+        if pmc and km["key_terms"] == 4:
+            def pipe_cycles(name):
+                k_ = pmc["kernels"].get(name)
+                c_ = (k_ or {}).get("counters", {})
+                if "SQ_ACTIVE_INST_VALU" not in c_:
+                    return None
+                return (4.0 * c_["SQ_ACTIVE_INST_VALU"] + c_.get("SQ_VALU_MFMA_BUSY_CYCLES", 0.0)) / k_.get("scenes_per_launch", pmc["scenes_per_launch"])
+            pc_sel = pipe_cycles(sel_name) or pipe_cycles("select_geo_kernel")
+            pc_qp = pipe_cycles(qp_name) or pipe_cycles("nrmp_qp_kernel")
+            pc_st = pipe_cycles("stage_group_kernel" if lp.chains else "stage_kernel") or 0.0
+            if pc_sel and pc_qp and args.workload == WORKLOAD:
+                per_plan = K * (pc_sel + pc_qp) + pc_st
+                bound = N_SIMD * 2.4e9 / per_plan
+                roof["vector_pipe"] = {"simd_cycles_per_plan": int(per_plan), "selection_share": round(K * pc_sel / per_plan, 3),
+                                       "bound_plans_per_s": int(bound), "frac": round(value / world / bound, 4),
+                                       "note": "VALU + MFMA busy SIMD-cycles of selection, QP and staging per plan (PMC, kernels alone) -> plans/s "
+                                               "of 1024 SIMDs at 2.4 GHz with no idle cycle; frac = this run's rate per GPU over it"}
+        roof["note"] = ("dominant kernel by GPU time = the QP (fp64 Mehrotra IPM, one wave per scene, serial chain: latency / VALU-issue "
+                        "bound).  achieved = (interior-point iterations per launch, measured on the device in this run) x (fp64 flops per "
+                        "iteration) + solves x (fixed flops per solve), the two per-unit figures from PMC counts at two operating points "
+                        "(roofline.flops_model), / launch time measured here with HIP events on the launch's stream (other batches' kernels "
+                        "co-run on the same SIMDs; frac_alone: over the kernel's duration alone on the chip; chip_aggregate: all QP "
+                        "launches of the region over its wall time); nothing is priced above what it executes.  DUNE: " +
+                        ("geometric distance keys inside select_geo_kernel nominate the candidates, the exact fp32-MFMA encoder runs on "
+                         "those only (~1.1 tiles of 32 points per slice instead of N/32); no dune_kernel launch" if km["key_terms"] == 4
+                         else f"network keys (mode {km['key_terms']}) from dune_kernel over every point, exact re-encode of the candidates"))
+        mfd = dune_mfma_rate(km, cfg, B, dune_ms, args.steps, elapsed)
+        if mfd:
+            roof["dune_executed_mfma"] = mfd
 
     line = {
         "metric": "MPC plans/sec (node), diff robot, 1k pts, T=10, K=10; ctrl L2 vs ref" if args.workload == WORKLOAD
@@ -914,18 +966,18 @@ def main():
                                      if dist is not None else " (no process group in a single-process run: nothing to gather)"),
                    "inputs": "resident in HBM and re-planned every step; the 8 N B of points per scene a host caller ships per "
                              "step over PCIe are NOT in the timed region (DESIGN.md section 6)"},
-        "roofline": roof,
+        **({"roofline": roof} if args.full else {}),
         # host time to enqueue a step (one library call = 21 launches) next to the step's wall time: when the two are close
         # the step is bound by the host's launch rate, not by the kernels
         "host_issue_ms_per_step": round(1e3 * t_issue / args.steps, 4),
         # rank 0's timed region in its three parts: issuing the steps, waiting for the device, the closing barrier of the contract
         "region_ms": {"issue": round(1e3 * t_issue, 3), "drain": round(1e3 * (r["t_drain"] - t_issue), 3),
                       "closing_barrier": round(1e3 * (r["elapsed_rank"] - r["t_drain"]), 3)},
-        "margin_audit": audit,
+        **({"margin_audit": audit} if args.full else {}),
     }
 
     # ---- single-scene latency: the reference's actual use (neupan/neupan.py:104-166, one robot, README "15 Hz") -------
-    if rank == 0 and not args.no_latency:
+    if args.full and rank == 0 and not args.no_latency:
         lat = {}
         for tag, over in (("K10_N1000", {}), ("shipped_K2_N100", dict(iter_num=2, dune_max_num=100, iter_threshold=0.1))):
             p1 = make_gpu_pan(cfg, device=dev, **over)
@@ -944,8 +996,8 @@ def main():
         line["latency_B1_ms"] = dict(lat, note="one scene per forward call, host call -> results synchronised, median of 50; "
                                                f"same workload ({N} points; the shipped config decimates to 100 and may stop early)")
 
-    extras = rank == 0 and world == 1 and not args.no_extras and args.workload == WORKLOAD
-    with_cpu = rank == 0 and world == 1 and not args.no_cpu
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras and args.workload == WORKLOAD
+    with_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu
     cores = args.cpu_cores if args.cpu_cores > 0 else (os.cpu_count() or 1)
     if with_cpu:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -1145,7 +1197,9 @@ def main():
         lh.close()
         ex["seconds"] = round(time.perf_counter() - t_ex, 1)
         line["extra"] = ex
-    if rank == 0:
+    if rank == 0 and not args.full:
+        print(json.dumps(compact(line, None)), flush=True)
+    elif rank == 0:
         full_path = os.environ.get("NPA_BENCH_FULL", os.path.join(ROOT, "bench_full.json"))
         try:
             with open(full_path, "w") as f:

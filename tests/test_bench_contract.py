@@ -159,7 +159,7 @@ def test_compact_line_stays_under_the_drivers_limit():
 
 def test_bare_gpus_2_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher around it (the shape of the driver's N = 1 command with another N) must
-    not die in argument handling: it re-executes itself under torch.distributed.run, one rank per GPU.  Driven here without a
+    not die in argument handling: it launches itself under torch.distributed.run, one rank per GPU.  Driven here without a
     GPU (--dry-run: gloo, a numpy stand-in for the step): rendezvous on 127.0.0.1, barrier + K steps + barrier, MAX over the
     ranks, exactly ONE JSON line on stdout, from rank 0, with n_gpus = 2."""
     import subprocess
@@ -181,3 +181,43 @@ def test_bare_gpus_2_launches_its_own_ranks(tmp_path):
                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300, env=env, cwd=str(tmp_path))
     assert r1.returncode == 0, r1.stderr[-2000:]
     assert json.loads([ln for ln in r1.stdout.strip().split("\n") if ln.startswith("{")][-1])["n_gpus"] == 1
+
+
+def test_plain_line_and_output_dump(tmp_path, monkeypatch):
+    """A plain run (no --full) prints the headline alone: compact() of such a line keeps every contract key and names no full
+    record.  --dump-outputs writes the last step's arrays as float32 / float64 .npy files, integers widened, None skipped, and
+    above the size limit the same seeded rows of every array."""
+    import numpy as np
+    import torch
+    import bench
+    full = _line("r06_bench_full.json")
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config", "host_issue_ms_per_step", "region_ms")
+    c = bench.compact({k: full[k] for k in keep}, None)
+    for k in keep:
+        assert k in c, k
+    assert c["value"] == full["value"] and c["ms_per_step"] == full["ms_per_step"]
+    assert not {"roofline", "cpu_baseline", "parity", "extra", "full_record"} & set(c)
+    g = torch.Generator().manual_seed(0)
+    out = {"opt_s": torch.rand(256, 3, 11, generator=g), "opt_u": torch.rand(256, 2, 10, generator=g), "opt_d": None,
+           "min_distance": torch.rand(256, generator=g, dtype=torch.float64), "iters": torch.full((256,), 10, dtype=torch.int32)}
+    # under a process group the step also returns the all-gathered controls, (world, B, 2, T): here two ranks
+    gathered = torch.stack([out["opt_u"], torch.rand(256, 2, 10, generator=g)])
+    bench.dump_outputs(str(tmp_path / "a"), (out, gathered), with_gathered=True)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"opt_s", "opt_u", "min_distance", "iters", "gathered_u"}
+    assert got["opt_s"].dtype == np.float32 and got["min_distance"].dtype == np.float64 and got["iters"].dtype == np.float64
+    assert np.array_equal(got["opt_u"], out["opt_u"].numpy()) and (got["iters"] == 10).all()
+    assert np.array_equal(got["gathered_u"], gathered.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 20000)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), (out, gathered), with_gathered=True)
+    small = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sum(a.nbytes for a in small.values()) <= 20000
+    assert all(np.array_equal(a, np.load(tmp_path / "c" / f"{k}.npy")) for k, a in small.items())
+    # the same scenes in every array: rows of the output dict, the same positions in every rank's shard of gathered_u
+    rows = [i for i in range(256) if (out["opt_u"].numpy()[i] == small["opt_u"]).all(axis=(1, 2)).any()]
+    assert 0 < len(rows) < 256 and all(small[k].shape[0] == len(rows) for k in ("opt_s", "opt_u", "min_distance", "iters"))
+    assert np.array_equal(small["opt_s"], out["opt_s"].numpy()[rows])
+    assert np.array_equal(small["min_distance"], out["min_distance"].numpy()[rows])
+    assert np.array_equal(small["gathered_u"], gathered.numpy()[:, rows])

@@ -5,9 +5,9 @@ out=gpurun_out/$tag; mkdir -p $out
 for r in $(seq 1 $rounds); do
   for lib in "$@"; do
     n=$(basename $lib .so)
-    NPA_LIB_PATH=$PWD/$lib timeout 150 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras --no-latency > $out/drv_${n}_$r.json 2>/dev/null
-    NPA_LIB_PATH=$PWD/$lib timeout 200 python bench.py --no-cpu --no-extras --no-latency > $out/def_${n}_$r.json 2>/dev/null
-    NPA_LIB_PATH=$PWD/$lib timeout 100 python bench.py --inflight 1 --no-cpu --no-latency --no-extras --steps 32 --warmup 8 > $out/inf_${n}_$r.json 2>/dev/null
+    NPA_LIB_PATH=$PWD/$lib timeout 150 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-extras --no-latency > $out/drv_${n}_$r.json 2>/dev/null
+    NPA_LIB_PATH=$PWD/$lib timeout 200 python bench.py --full --no-cpu --no-extras --no-latency > $out/def_${n}_$r.json 2>/dev/null
+    NPA_LIB_PATH=$PWD/$lib timeout 100 python bench.py --inflight 1 --full --no-cpu --no-latency --no-extras --steps 32 --warmup 8 > $out/inf_${n}_$r.json 2>/dev/null
   done
 done
 python - <<P

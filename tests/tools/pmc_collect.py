@@ -40,9 +40,9 @@ def short(name):
     return None
 
 
-BENCH_ARGS = ["--steps", "4", "--warmup", "1", "--no-cpu", "--no-latency", "--no-extras", "--inflight", "1"]
+BENCH_ARGS = ["--steps", "4", "--warmup", "1", "--full", "--no-cpu", "--no-latency", "--no-extras", "--inflight", "1"]
 # the merged-launch kernels (round 5): ONE chain of five steps, i.e. every stage one launch over 5 x 256 scenes, alone on the chip
-MERGED_ARGS = ["--steps", "5", "--warmup", "5", "--no-cpu", "--no-latency", "--no-extras", "--inflight", "5", "--chains", "1"]
+MERGED_ARGS = ["--steps", "5", "--warmup", "5", "--full", "--no-cpu", "--no-latency", "--no-extras", "--inflight", "5", "--chains", "1"]
 MERGED_SCENES = 5 * 256
 # (no create-time self-test in the profiled process: its 2-scene launches of the same kernels would be averaged in with the
 # 256-scene ones -- round 3's record has them: 9 of 79 QP launches, the per-launch averages of that file are ~10 % low)

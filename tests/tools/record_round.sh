@@ -25,9 +25,9 @@ if [ -s gpurun_out/r04/pmc_diff_1k_T10_K10.json ]; then
 fi
 
 stamp "default line"
-timeout 480 $py bench.py > "$out/${tag}_bench.json" 2> "$out/bench.err"; echo "rc $?" >> "$out/bench.err"
+timeout 480 $py bench.py --full > "$out/${tag}_bench.json" 2> "$out/bench.err"; echo "rc $?" >> "$out/bench.err"
 stamp "driver flags"
-timeout 420 $py bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras > "$out/${tag}_bench_driver_flags.json" 2> "$out/bench_drv.err"
+timeout 420 $py bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu --no-extras > "$out/${tag}_bench_driver_flags.json" 2> "$out/bench_drv.err"
 for i in 2 3; do timeout 120 $py bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras --no-latency > "$out/drv_rep$i.json" 2>/dev/null; done
 
 stamp "one rank under torch.distributed.run"

@@ -21,14 +21,14 @@ grep -v "RCCL version\|HIP version\|ROCm version\|Hostname\|Librccl\|amdgpu.ids"
 stamp "smoke"
 timeout 200 $py -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "rc $?" >> $out/smoke.log
 stamp "driver flags (full command: CPU baseline, parity, extras)"
-NPA_BENCH_FULL=$PWD/$out/bench_driver_flags_full.json timeout 600 $py bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_flags.log 2> $out/bench_driver_flags.err
+NPA_BENCH_FULL=$PWD/$out/bench_driver_flags_full.json timeout 600 $py bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_driver_flags.log 2> $out/bench_driver_flags.err
 tail -1 $out/bench_driver_flags.log > $out/bench_driver_flags.json
 stamp "default line"
-NPA_BENCH_FULL=$PWD/$out/bench_full.json timeout 600 $py bench.py > $out/bench.log 2> $out/bench.err
+NPA_BENCH_FULL=$PWD/$out/bench_full.json timeout 600 $py bench.py --full > $out/bench.log 2> $out/bench.err
 tail -1 $out/bench.log > $out/bench.json
 stamp "driver flags again x4 (GPU only), sequential steps"
 for i in 2 3 4 5; do timeout 150 $py bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-extras --no-latency > $out/drv_rep$i.json 2>/dev/null; done
-timeout 120 $py bench.py --inflight 1 --no-cpu --no-latency --no-extras --steps 32 --warmup 8 > $out/bench_inflight1.json 2>/dev/null
+timeout 120 $py bench.py --inflight 1 --full --no-cpu --no-latency --no-extras --steps 32 --warmup 8 > $out/bench_inflight1.json 2>/dev/null
 stamp "one rank under torch.distributed.run"
 timeout 200 $py -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --no-cpu --no-latency --no-extras 2> $out/torchrun1.err | tail -1 > $out/bench_torchrun1.json
 for i in 1 2 3; do timeout 200 $py -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $((29520 + i)) bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-latency --no-extras 2>> $out/torchrun1.err | tail -1 > $out/bench_torchrun1_driver_flags_$i.json; done
@@ -42,7 +42,7 @@ timeout 300 $py tests/tools/qp_phase_cycles.py > $out/qp_phase_cycles_raw.txt 2>
 grep -v "hipcc\|amdgpu.ids" $out/qp_phase_cycles_raw.txt > $out/qp_phase_cycles.txt
 timeout 300 $py tests/tools/select_phase_cycles.py 2>&1 | grep -v "amdgpu.ids" > $out/select_phase_cycles.txt
 stamp "other configurations, GPU only (the parity legs ride in the lines above)"
-for w in acker_2k_T20_K15 dyna_4k_T10_K10 poly8_5k_T10_K10; do timeout 200 $py bench.py --workload $w --no-cpu --no-latency --no-extras > $out/bench_$w.json 2>/dev/null; done
+for w in acker_2k_T20_K15 dyna_4k_T10_K10 poly8_5k_T10_K10; do timeout 200 $py bench.py --workload $w --full --no-cpu --no-latency --no-extras > $out/bench_$w.json 2>/dev/null; done
 stamp "64-scene x 12-member parity of the other configurations"
 timeout 900 $py tests/tools/parity_wide.py 2> $out/parity_wide.log | tail -1 > $out/parity_wide.json
 stamp "done"
