@@ -21,7 +21,7 @@ from math import cos, inf, sin, tan
 
 import numpy as np
 
-from .nrmp_qp import NrmpProblem, solve_nrmp_qp
+from .nrmp_qp import NrmpProblem, QPNotConverged, solve_nrmp_qp  # noqa: F401  (QPNotConverged: what nrmp() raises)
 
 f32 = np.float32
 
@@ -216,6 +216,10 @@ class PanOracle:
         self.min_distance = inf
         self.iters_run = 0
         self.trace = []          # per-iteration (s,u,d) for tests
+        # one record per QP this oracle solved (all calls): final merit and iterations of the fp64 solve.  solve_nrmp_qp
+        # refuses to hand out an unconverged solve (QPNotConverged); the log says how far below its cap each one ended
+        self.qp_log = []
+        self.last_qp_info = None
 
     def nrmp(self, nom_s, nom_u, ref_s, ref_us, mu_l, lam_l, pt_l):
         """nrmp.py:114-166: build the parameter values, solve in fp64, cast to fp32."""
@@ -230,10 +234,16 @@ class PanOracle:
         pb = NrmpProblem(nom_s, qref, puref, A, B, C, fa, fb, self.q_s, self.p_u, self.eta,
                          self.d_max, self.d_min, self.ro_obs, self.bk,
                          self.speed_bound, self.acce_bound, self.kin)
-        s, u, d = solve_nrmp_qp(pb)
+        s, u, d, info = solve_nrmp_qp(pb, return_info=True)
         self.last_problem = pb
+        self.last_qp_info = {"merit": float(info["merit"]), "iters": int(info["iters"])}
+        self.qp_log.append(self.last_qp_info)
         cast = lambda a: None if a is None else a.astype(np.float32)                 # nrmp.py:145-148
         return cast(s), cast(u), cast(d)
+
+    def qp_merit_max(self):
+        """Largest final merit over every QP this oracle solved (0.0 before the first)."""
+        return max((r["merit"] for r in self.qp_log), default=0.0)
 
     def stop_criteria(self, nom_s, nom_u, mu_l, lam_l):
         """pan.py:215-243."""

@@ -115,23 +115,28 @@ def _base_times(_):
 
 def ensemble_job(job):
     """One oracle run: (scene, member) with member -1 = the base run, 0..n_ulp-1 = inputs moved by +-1 ulp,
-    n_ulp.. = hidden units permuted.  Returns (scene, member, controls per iteration (K,2,T) float32)."""
+    n_ulp.. = hidden units permuted.  Returns (scene, member, controls per iteration (K,2,T) float32, largest final merit of
+    the run's QP solves).  Every solve is strict: an unconverged one raises oracle.nrmp_qp.QPNotConverged, it never enters
+    a spread."""
     from neupan_amd.scenes import make_scene
     b, m, n_ulp = job
     cfg, wd = _WORK["cfg"], _WORK["wd"]
     sc = make_scene(cfg, b)
     if m < 0:
         t0 = time.perf_counter()
-        tr = _trace_u(_make_oracle(cfg, wd), sc)
+        orc = _make_oracle(cfg, wd)
+        tr = _trace_u(orc, sc)
         _WORK.setdefault("base_s", []).append(time.perf_counter() - t0)
-        return b, m, tr
+        return b, m, tr, orc.qp_merit_max()
     if m < n_ulp:
         rng = np.random.default_rng(7_000_003 * (b + 1) + m)
         up = rng.random(sc["points"].shape) < 0.5
         pts = np.where(up, np.nextafter(sc["points"], np.float32(np.inf)), np.nextafter(sc["points"], np.float32(-np.inf)))
-        return b, m, _trace_u(_make_oracle(cfg, wd), sc, pts.astype(np.float32))
+        orc = _make_oracle(cfg, wd)
+        return b, m, _trace_u(orc, sc, pts.astype(np.float32)), orc.qp_merit_max()
     rng = np.random.default_rng(9_000_011 * (b + 1) + (m - n_ulp))
-    return b, m, _trace_u(_make_oracle(cfg, permuted_weights(wd, rng)), sc)
+    orc = _make_oracle(cfg, permuted_weights(wd, rng))
+    return b, m, _trace_u(orc, sc), orc.qp_merit_max()
 
 
 def host_cores():
@@ -179,7 +184,9 @@ def run_ensemble(workload, scenes, cores, n_ulp=8, n_perm=4, sweep=True):
     Phase 1, timed: base runs at several levels of concurrency (physical cores / 4, / 2, all physical cores, all
     hardware threads, capped by `cores`), 2 jobs per worker each; the CPU baseline is the BEST rate of the sweep
     (run_ensemble.last_sweep has the table, .last_job_seconds the per-job times of the winning level,
-    .last_single_seconds the time of a plan with ONE job in flight).  Phase 2, untimed: the ensemble members."""
+    .last_single_seconds the time of a plan with ONE job in flight).  Phase 2, untimed: the ensemble members.
+    run_ensemble.last_oracle_merit = {"base": .., "members": ..}: the largest final merit of the oracle's QP solves over the
+    base runs and over the members (every solve is strict, see ensemble_job)."""
     import multiprocessing as mp
     from concurrent.futures import ProcessPoolExecutor
     from neupan_amd.scenes import CONFIGS
@@ -189,6 +196,7 @@ def run_ensemble(workload, scenes, cores, n_ulp=8, n_perm=4, sweep=True):
     wd = _weights_np(CONFIGS[workload])
     got = {}
     run_ensemble.last_sweep, run_ensemble.last_job_seconds, run_ensemble.last_single_seconds = None, None, None
+    run_ensemble.last_oracle_merit = None
     for k in ("OMP_NUM_THREADS", "MKL_NUM_THREADS", "OPENBLAS_NUM_THREADS", "NUMEXPR_NUM_THREADS"):
         os.environ[k] = "1"                      # inherited by the spawned workers, in place before they import numpy
     if cores == 1:
@@ -237,11 +245,15 @@ def run_ensemble(workload, scenes, cores, n_ulp=8, n_perm=4, sweep=True):
             run_ensemble.last_sweep = table
             run_ensemble.last_job_seconds = best[1]
             rate, base_workers = best[0]["plans_per_s"], best[0]["workers"]
-            have = {b for b, m, _ in res if m < 0}
+            have = {r[0] for r in res if r[1] < 0}
             rest = [(b, -1, n_ulp) for b in scenes if b not in have] + [(b, m, n_ulp) for b in scenes for m in range(n_mem)]
             res += _timed_with_concurrency(ex, rest, base_workers)[0]      # (at the level that ran fastest)
-    for b, m, tr in res:
+    merit = {"base": 0.0, "members": 0.0}
+    for b, m, tr, mer in res:
         got[(b, m)] = tr
+        key = "base" if m < 0 else "members"
+        merit[key] = max(merit[key], float(mer))
+    run_ensemble.last_oracle_merit = merit
     base = np.stack([got[(b, -1)] for b in scenes])
     members = np.stack([np.stack([got[(b, m)] for m in range(n_mem)]) if n_mem else np.zeros((0,) + base.shape[1:], np.float32)
                         for b in scenes])
@@ -300,6 +312,7 @@ def _explain_step(orc, cfg, sc, nom_s, nom_u, hip_pts, u_or, dev, b, k, hip_u=No
                     out["rank_gap"] = max(out["rank_gap"], float(dist[idx]) - cut)
             out["slices_with_other_set"] += int(other)
     spread = 0.0
+    merit = 0.0
     for mem in range(6):
         rng = np.random.default_rng(5_000_011 * (b + 1) + 131 * k + mem)
         pts = sc["points"]
@@ -308,8 +321,9 @@ def _explain_step(orc, cfg, sc, nom_s, nom_u, hip_pts, u_or, dev, b, k, hip_u=No
             pts = np.where(up, np.nextafter(pts, np.float32(np.inf)), np.nextafter(pts, np.float32(-np.inf))).astype(np.float32)
         o2 = _make_oracle(cfg, _WORK["wd"])
         o2.iter_num = 1
-        _, u2, _ = o2.forward(nom_s, nom_u, sc["ref_s"], sc["ref_us"], pts, sc["velocities"])
+        _, u2, _ = o2.forward(nom_s, nom_u, sc["ref_s"], sc["ref_us"], pts, sc["velocities"])   # (strict: QPNotConverged)
         spread = max(spread, float(_l2(u2.astype(np.float32), u_or)))
+        merit = max(merit, o2.qp_merit_max())
     out["ensemble_spread"] = spread
     # the oracle's OWN problem at the HIP path's point: states through the oracle's linearised dynamics, d optimal for those
     # states (it separates per step), everything in fp64.  A point that is feasible to fp32 rounding and whose objective
@@ -360,6 +374,7 @@ def _explain_step(orc, cfg, sc, nom_s, nom_u, hip_pts, u_or, dev, b, k, hip_u=No
         pt_l = [np.ascontiguousarray(hip_pts[t].T) for t in range(T + 1)]
         o3 = _make_oracle(cfg, _WORK["wd"])
         _, u3, _ = o3.nrmp(nom_s, nom_u, sc["ref_s"], sc["ref_us"], mu_l, lam_l, pt_l)
+        merit = max(merit, o3.qp_merit_max())
         out["oracle_solver_on_hip_rows_vs_hip"] = float(_l2(u3.astype(np.float32), np.asarray(hip_u, dtype=np.float32)))
         # how far the kernel's rows are from the oracle's own, matched point by point (slice 0 never reaches the QP)
         omu, olam, opt = orc.last_lists
@@ -373,6 +388,10 @@ def _explain_step(orc, cfg, sc, nom_s, nom_u, hip_pts, u_or, dev, b, k, hip_u=No
                 dlam = max(dlam, float(np.abs(olam[t][:, i] - hlam[t, j]).max()))
         out["rows_mu_diff"], out["rows_lam_diff"] = dmu, dlam
         rows_ok = out["oracle_solver_on_hip_rows_vs_hip"] <= 1e-5 and dmu <= 3e-5 and dlam <= 8e-5
+    # the largest final merit of the oracle solves this explanation rests on: the step's own (orc) and the ones above.  Each is
+    # strict (an unconverged solve raises oracle.nrmp_qp.QPNotConverged): a spread or an optimum of a solve that stopped short
+    # would explain a deviation of any size
+    out["oracle_merit_max"] = max(merit, orc.qp_merit_max())
     out["explained"] = "rank-M tie" if tie else ("one-step ensemble spread" if flat else ("same optimum of a flat QP" if same_opt else
                        ("encoder rounding, solver exonerated" if rows_ok else None)))
     return out
@@ -399,8 +418,8 @@ def _best_d(pb, s):
 
 def one_step_job(job):
     """One PAN iteration of the ORACLE started from the HIP path's own iterate: (scene, k, nom_s, nom_u[, hip_u, hip_pts]) ->
-    (scene, k, controls, explanation | None).  With hip_u given, a deviation above ONE_STEP_TOL is explained on the spot
-    (_explain_step)."""
+    (scene, k, controls, explanation | None, largest final merit of the oracle's QP solves of the job, explanation included).
+    With hip_u given, a deviation above ONE_STEP_TOL is explained on the spot (_explain_step)."""
     from neupan_amd.scenes import make_scene
     b, k, nom_s, nom_u = job[:4]
     cfg, wd = _WORK["cfg"], _WORK["wd"]
@@ -416,7 +435,7 @@ def one_step_job(job):
             orc.last_solution = (np.asarray(s, dtype=np.float64), np.asarray(u, dtype=np.float64), None if d is None else np.asarray(d, dtype=np.float64))
             why = _explain_step(orc, cfg, sc, nom_s, nom_u, job[5], u, dev, b, k, hip_u=job[4], hip_merit=job[7] if len(job) > 7 else None,
                                 hip_rows=job[8] if len(job) > 8 else None)
-    return b, k, u, why
+    return b, k, u, why, max(orc.qp_merit_max(), 0.0 if why is None else why["oracle_merit_max"])
 
 
 def one_step_consistency(workload, scenes, trace_s, trace_u, cores, explain=False, trace_pts=None, tol=None, trace_merit=None,
@@ -428,10 +447,13 @@ def one_step_consistency(workload, scenes, trace_s, trace_u, cores, explain=Fals
     implementations differs by (fp32 encoder order, two fp64 solvers on the same QP, a tie at rank M / M+1 of a slice).
     trace_s [S,K,3,T+1], trace_u [S,K,2,T] from PAN.forward_batch_trace.  Returns the [S,K] control L2 deviations; with
     explain=True: (deviations, list of explanations of every step above `tol`, default ONE_STEP_TOL) -- trace_pts
-    [S,K,T+1,M,2] (the rows the HIP path's selection emitted in that iteration) lets the explanation look at the selection."""
+    [S,K,T+1,M,2] (the rows the HIP path's selection emitted in that iteration) lets the explanation look at the selection.
+    one_step_consistency.last_oracle_merit_max: the largest final merit of every oracle QP solve behind the result, the
+    explanations' included (each solve is strict: an unconverged one raises oracle.nrmp_qp.QPNotConverged)."""
     import multiprocessing as mp
     from concurrent.futures import ProcessPoolExecutor
     from neupan_amd.scenes import CONFIGS, make_scene
+    one_step_consistency.last_oracle_merit_max = None
     cfg = CONFIGS[workload]
     scenes = list(scenes)
     S, K = trace_u.shape[:2]
@@ -463,11 +485,14 @@ def one_step_consistency(workload, scenes, trace_s, trace_u, cores, explain=Fals
     pos = {b: i for i, b in enumerate(scenes)}
     dev = np.zeros((S, K))
     why = []
-    for b, k, u, w in res:
+    merit = 0.0
+    for b, k, u, w, mer in res:
+        merit = max(merit, float(mer))
         dev[pos[b], k] = float(_l2(u, trace_u[pos[b], k]))
         if w is not None:
             w["scene_pos"] = pos[b]
             why.append(w)
+    one_step_consistency.last_oracle_merit_max = merit
     return (dev, why) if explain else dev
 
 
@@ -545,22 +570,34 @@ def judge(hip_trace, base, members, tol=1e-4, early=1e-5):
     return rep, hip, sp
 
 
-def gpu_last_qp_certificates(pan, cfg, batch, scenes=None, tie_tol=2e-6):
-    """Optimality of the HIP path's OWN last QP, checked on the host in fp64 (the reference's solver, ECOS, is absent: a
+def gpu_last_qp_certificates(pan, cfg, batch, scenes=None, tie_tol=2e-6, iteration=None, robot_kw=None, highs=False):
+    """Optimality of one of the HIP path's OWN QPs, checked on the host in fp64 (the reference's solver, ECOS, is absent: a
     strictly convex QP has one optimum, so a point that passes the KKT certificate IS the answer the reference's solver
     approximates).  For a forward call on `batch` (dict of numpy arrays as make_batch returns them): the nominal
-    trajectory before the last PAN iteration is read back, the last iteration is re-run through the stage entry points
-    (npa_dune_stage, npa_nrmp_params, npa_nrmp_stage), and for every scene the problem is rebuilt on the host from the
-    parameters the KERNEL built (A/B/C, fa/fb in fp32) and
+    trajectory before PAN iteration `iteration` (0-based; None = the last) is read back, that iteration is re-run through
+    the stage entry points (npa_dune_stage, npa_nrmp_params, npa_nrmp_stage), and for every scene the problem is rebuilt on
+    the host from the parameters the KERNEL built (A/B/C, fa/fb in fp32) and
       * the kernel's fp64 solution is certified (oracle.nrmp_qp.kkt_certificate: stationarity with NNLS multipliers,
         complementarity, feasibility),
-      * the oracle solves the same problem: objective gap and control difference.
-    Returns a dict of maxima plus `tie_max` / `tied_to_forward` = the stage re-run reproduced the forward call's controls
-    (<= tie_tol; 2e-6 where the QPs are well conditioned, see the acker test for the flat case)."""
+      * the oracle solves the same problem (strict: oracle.nrmp_qp.QPNotConverged if it cannot): objective gap and control
+        difference, `oracle_merit_max` = the largest final merit of those solves,
+      * with highs=True HiGHS (tests/qp_highs.py, shares no code with the kernel or the oracle) solves it too:
+        `highs_not_optimal` = scenes whose HiGHS status is not optimal, `highs_obj_gap_rel` = the largest
+        (objective(kernel) - objective(HiGHS)) / max(1, |objective|); and the FORWARD call's own controls of that iteration
+        (fp32, possibly warm-started, where the stage re-run is a cold solve) are held against HiGHS too: states through the
+        problem's dynamics, d optimal for them, `fwd_highs_obj_gap_rel` the same relative gap, `fwd_bound_violation` the
+        largest violation of a speed / acceleration bound.
+    `robot_kw`: the robot the handle was built with when it is not cfg.robot.  Returns a dict of maxima plus `tie_max` /
+    `tied_to_forward` = the stage re-run reproduced the forward call's controls of that iteration (<= tie_tol; 2e-6 where
+    the QPs are well conditioned, see the acker test for the flat case), `merit` / `status_nonzero` = the re-run's largest
+    final merit and how many of its solves ended with a status other than 0."""
     import torch
     from helpers import robot_numbers
     from oracle.nrmp_qp import NrmpProblem, kkt_certificate, solve_nrmp_qp
     T, K, M = pan.T, pan.iter_num, pan.nrmp_max_num
+    it = K - 1 if iteration is None else int(iteration)
+    assert 0 <= it < K, (iteration, K)
+    robot = dict(cfg.robot if robot_kw is None else robot_kw)
     a = [batch[k] for k in ("nom_s", "nom_u", "ref_s", "ref_us", "points")]
     pan.reset_stop_state()
     pan.forward_begin(*a, batch.get("velocities"))
@@ -568,39 +605,56 @@ def gpu_last_qp_certificates(pan, cfg, batch, scenes=None, tie_tol=2e-6):
     wsf = pan._ws.view(torch.float32)
     n_s = B * 3 * (T + 1)
     off_u = (n_s + 3) // 4 * 4
-    for k in range(K - 1):
+    for k in range(it):
         pan.forward_iter(k)
-    snap_s = wsf[:n_s].clone().reshape(B, 3, T + 1)
-    snap_u = wsf[off_u:off_u + B * 2 * T].clone().reshape(B, 2, T)
-    pan.forward_iter(K - 1)
+    if it == 0:                                          # the nominal of the call itself
+        snap_s = torch.as_tensor(np.ascontiguousarray(a[0], dtype=np.float32)).to(pan.device)
+        snap_u = torch.as_tensor(np.ascontiguousarray(a[1], dtype=np.float32)).to(pan.device)
+    else:
+        snap_s = wsf[:n_s].clone().reshape(B, 3, T + 1)
+        snap_u = wsf[off_u:off_u + B * 2 * T].clone().reshape(B, 2, T)
+    pan.forward_iter(it)
+    fwd_u = wsf[off_u:off_u + B * 2 * T].clone().reshape(B, 2, T)        # the working controls after that iteration
+    for k in range(it + 1, K):
+        pan.forward_iter(k)
     out = pan.forward_end()
+    if it == K - 1:
+        fwd_u = out["opt_u"]
     stage = pan.dune_stage(snap_s, a[4], batch.get("velocities"))
     par = pan.nrmp_params(snap_s, snap_u, stage)
     sol = pan.nrmp_stage(snap_s, snap_u, a[2], a[3], stage)
     # (the forward call may have warm-started this solve from the previous iteration's, the stage entry point starts
     # cold: the same limit point, to the last few bits)
-    tie_max = float(np.abs(sol["opt_u"].cpu().numpy() - out["opt_u"].cpu().numpy()).max())
+    tie_max = float(np.abs(sol["opt_u"].cpu().numpy() - fwd_u.cpu().numpy()).max())
     tied = bool(tie_max <= tie_tol)
     x64 = sol["x64"].cpu().numpy()
+    info = sol["info"].cpu().numpy()
     ns, nu_ = snap_s.cpu().numpy(), snap_u.cpu().numpy()
-    G, h, sp, ac, L = robot_numbers(cfg.robot, cfg.dt)
+    G, h, sp, ac, L = robot_numbers(robot, cfg.dt)
     adj = dict(cfg.adjust)
     q_s, p_u = np.float32(adj.get("q_s", 1.0)), np.float32(adj.get("p_u", 1.0))
-    res = dict(stat=0.0, comp=0.0, feas=0.0, obj_gap_rel=0.0, du_vs_oracle=0.0, merit=float(sol["info"][:, 1].max()))
+    sel = list(range(B) if scenes is None else scenes)
+    res = dict(stat=0.0, comp=0.0, feas=0.0, obj_gap_rel=0.0, du_vs_oracle=0.0, merit=float(info[sel, 1].max()),
+               status_nonzero=int((info[sel, 3] != 0).sum()), oracle_merit_max=0.0, iteration=it)
+    if highs:
+        from qp_highs import compare_with_highs
+        res.update(highs_not_optimal=0, highs_obj_gap_rel=-np.inf, fwd_highs_obj_gap_rel=-np.inf, fwd_bound_violation=0.0)
+        fu = fwd_u.cpu().numpy().astype(np.float64)
     worst = []
-    for b in (range(B) if scenes is None else scenes):
+    for b in sel:
         qref = (q_s * batch["ref_s"][b]).astype(np.float32)
         puref = (p_u * batch["ref_us"][b]).astype(np.float32)
         pb = NrmpProblem(ns[b], qref, puref, par["A"][b], par["B"][b], par["C"][b], par["fa"][b], par["fb"][b][..., 0], q_s, p_u,
                          np.float32(adj.get("eta", 10.0)), np.float32(adj.get("d_max", 1.0)), np.float32(adj.get("d_min", 0.1)),
-                         adj.get("ro_obs", 400), adj.get("bk", 0.1), sp, ac, cfg.robot["kinematics"])
+                         adj.get("ro_obs", 400), adj.get("bk", 0.1), sp, ac, robot["kinematics"])
         u = x64[b, :2 * T].reshape(T, 2).T.copy()
         d = x64[b, 2 * T:].copy()
         s = np.zeros((3, T + 1)); s[:, 0] = pb.nom_s[:, 0]
         for t in range(T):
             s[:, t + 1] = pb.A[t] @ s[:, t] + pb.B[t] @ u[:, t] + pb.C[t]
         c = kkt_certificate(pb, s, u, d)
-        so, uo, do = solve_nrmp_qp(pb)
+        so, uo, do, oinfo = solve_nrmp_qp(pb, return_info=True)
+        res["oracle_merit_max"] = max(res["oracle_merit_max"], float(oinfo["merit"]))
         res["stat_oracle"] = max(res.get("stat_oracle", 0.0), kkt_certificate(pb, so, uo, do.reshape(-1))["stat"])
         og, oo = pb.objective(s, u, d), pb.objective(so, uo, do.reshape(-1))
         gap = (og - oo) / max(1.0, abs(oo))
@@ -608,6 +662,19 @@ def gpu_last_qp_certificates(pan, cfg, batch, scenes=None, tie_tol=2e-6):
             res[k] = max(res[k], c[k])
         res["obj_gap_rel"] = max(res["obj_gap_rel"], float(gap))
         res["du_vs_oracle"] = max(res["du_vs_oracle"], float(np.abs(u - uo).max()))
+        if highs:
+            hc = compare_with_highs(pb, s, u, d)
+            res["highs_not_optimal"] += int(hc["status"] != "Optimal")
+            res["highs_obj_gap_rel"] = max(res["highs_obj_gap_rel"], hc["obj_diff"] / max(1.0, abs(hc["obj"])))
+            obj_h = hc["obj"] - hc["obj_diff"]
+            sf = np.zeros((3, T + 1)); sf[:, 0] = pb.nom_s[:, 0]
+            for t in range(T):
+                sf[:, t + 1] = pb.A[t] @ sf[:, t] + pb.B[t] @ fu[b][:, t] + pb.C[t]
+            df = None if pb.no_obs else _best_d(pb, sf)
+            res["fwd_highs_obj_gap_rel"] = max(res["fwd_highs_obj_gap_rel"], (pb.objective(sf, fu[b], df) - obj_h) / max(1.0, abs(obj_h)))
+            viol = max(float((np.abs(fu[b]) - pb.speed_bound[:, None]).max()),
+                       float((np.abs(np.diff(fu[b], axis=1)) - pb.acce_bound[:, None]).max()) if T > 1 else 0.0, 0.0)
+            res["fwd_bound_violation"] = max(res["fwd_bound_violation"], viol)
         worst.append((float(np.abs(u - uo).max()), int(b)))
     res["scenes"] = len(worst)
     res["tied_to_forward"] = tied

@@ -52,6 +52,7 @@ def test_oracle_chain_reproduces_reference_cycles(name):
     arrived = False
     prev_u = np.zeros((2, 10))
     f32 = lambda a: np.asarray(a, dtype=np.float32)
+    solves = 0
     for c in range(len(g["states"])):
         st = g["states"][c]
         # check_arrive (initial_path.py:247-277)
@@ -73,6 +74,7 @@ def test_oracle_chain_reproduces_reference_cycles(name):
             pts_c = None                                  # the cloud is gone: DUNE.min_distance keeps its last value
         so, uo, do = orc.forward(f32(n_s), f32(n_u), f32(r_s), f32(r_us), None if pts_c is None else f32(pts_c),
                                  None if vel is None else f32(vel))
+        solves += orc.iters_run
         prev_u = f32(uo)
         stop = bool(orc.min_distance < 0.1)
         assert stop == bool(g["stop"][c]), (name, c)
@@ -81,6 +83,9 @@ def test_oracle_chain_reproduces_reference_cycles(name):
             want = np.array([want[0] * np.cos(want[1]), want[0] * np.sin(want[1])])
         assert np.abs(want - g["actions"][c]).max() <= 5e-6, (name, c, want, g["actions"][c])
         assert np.abs(f32(uo) - g["opt_u"][c]).max() <= 5e-6, (name, c)
+    # every QP of the chain was solved to the oracle's floor (not merely under its 1e-9 refusal cap): the solves behind the
+    # committed cycle are certified without re-recording it
+    assert len(orc.qp_log) == solves and orc.qp_merit_max() <= 1e-12, orc.qp_log
 
 
 @pytest.mark.gpu

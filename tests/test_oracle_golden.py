@@ -3,10 +3,11 @@
 import numpy as np
 import pytest
 
-from helpers import CONFIGS, golden, make_oracle, robot_numbers
+from helpers import CONFIGS, HARD_SCENES, golden, make_oracle, robot_numbers
+from oracle import nrmp_qp
 from oracle import pan_oracle as po
 from oracle.condensed_ipm import solve_condensed
-from oracle.nrmp_qp import NrmpProblem, kkt_certificate, solve_nrmp_qp
+from oracle.nrmp_qp import NrmpProblem, QPNotConverged, kkt_certificate, solve_nrmp_qp
 
 POLY = dict(kinematics="diff", vertices=[[-0.8, -1.0], [-1.8, 1.0], [1.8, 1.0], [0.8, -1.0]],
             max_speed=[8, 3], max_acce=[8, 3])
@@ -129,11 +130,13 @@ def test_pan_forward_matches_reference_control_flow(case, cfgname, over):
     ck = over.pop("checkpoint", None)
     o = make_oracle(CONFIGS[cfgname], robot_kw=over.pop("robot_kw", None),
                     checkpoint=ckpt_path(ck) if ck else None, **over)
+    solves = 0
     for c in range(int(g["calls"])):
         pts = g[f"c{c}_points"] if f"c{c}_points" in g.files and case != "nopoints_k3" else None
         vel = g[f"c{c}_velocities"] if bool(g[f"c{c}_has_vel"]) else None
         s, u, d = o.forward(g[f"c{c}_nom_s"], g[f"c{c}_nom_u"], g[f"c{c}_ref_s"], g[f"c{c}_ref_us"], pts, vel)
         assert o.iters_run == int(g[f"c{c}_iters"])
+        solves += o.iters_run
         np.testing.assert_allclose(u, g[f"c{c}_opt_u"], atol=2e-4)
         np.testing.assert_allclose(s, g[f"c{c}_opt_s"], atol=2e-4)
         if d is None:
@@ -142,6 +145,9 @@ def test_pan_forward_matches_reference_control_flow(case, cfgname, over):
             np.testing.assert_allclose(d, g[f"c{c}_opt_d"], atol=2e-4)
         if pts is not None and not o.no_obs:
             assert abs(float(o.min_distance) - float(g[f"c{c}_min_distance"])) < 2e-5
+    # every QP behind the golden's numbers was solved to the oracle's floor, not merely under its 1e-9 refusal cap: this
+    # certifies the solves of the committed vector without re-recording it
+    assert len(o.qp_log) == solves and o.qp_merit_max() <= 1e-12, o.qp_log
 
 
 def _qp_problem(g, i):
@@ -177,12 +183,15 @@ def test_qp_oracle_vs_highs_and_certificate():
 
 
 @pytest.mark.parametrize("cfgname,scene,kw", [("diff_1k_T10_K10", 5, {}), ("diff_1k_T10_K10", 63, {}),
-                                               ("acker_2k_T20_K15", 16, dict(iter_num=4)), ("dyna_4k_T10_K10", 3, dict(iter_num=4))])
+                                               ("acker_2k_T20_K15", 16, dict(iter_num=4)), ("dyna_4k_T10_K10", 3, dict(iter_num=4))]
+                         # the QPs both solvers once gave up on: the forward call up to and including the iteration that jammed
+                         + [(w, b, dict(iter_num=it + 1)) for w, b, it in HARD_SCENES])
 def test_qp_oracle_vs_highs_on_benchmark_problems(cfgname, scene, kw):
     """The oracle's QP solve against HiGHS on EVERY QP of a benchmark scene's PAN loop, solved live (the committed
-    qp_cases.npz holds 33 small problems; profiles/r02_qp_highs.json the sweep of tests/tools/qp_highs_sweep.py over
-    whole batches: 2560 + 360 + 240 + 64 QPs): HiGHS optimal, the oracle's objective never worse than HiGHS' by more
-    than 1e-9 relative, controls within HiGHS' own accuracy along the flat steering directions."""
+    qp_cases.npz holds 33 small problems; profiles/r07_qp_highs.json the sweep of tests/tools/qp_highs_sweep.py over
+    whole batches): HiGHS optimal, the oracle's objective never worse than HiGHS' by more than 1e-9 relative, controls
+    within HiGHS' own accuracy along the flat steering directions.  HARD_SCENES: the eight scenes whose QPs the oracle's
+    solver (and the kernel's) returned unconverged until round 6 -- HiGHS shares no code with either."""
     from neupan_amd.scenes import make_scene
     from oracle.nrmp_qp import kkt_certificate
     from qp_highs import compare_with_highs
@@ -203,6 +212,7 @@ def test_qp_oracle_vs_highs_on_benchmark_problems(cfgname, scene, kw):
     orc.nrmp = hook
     orc.forward(sc["nom_s"], sc["nom_u"], sc["ref_s"], sc["ref_us"], sc["points"], sc["velocities"])
     assert len(rows) == orc.iter_num
+    assert orc.qp_merit_max() <= 1e-12, orc.qp_log
     for c in rows:
         assert c["status"] == "Optimal", c
         assert c["obj_diff"] <= 1e-9 * max(1.0, abs(c["obj"])), c
@@ -211,6 +221,46 @@ def test_qp_oracle_vs_highs_on_benchmark_problems(cfgname, scene, kw):
         # the sharp comparison, the controls a sanity bound
         assert c["du"] <= (5e-2 if cfgname.startswith("acker") else 2e-4), c
         assert c["cert"]["dyn"] < 1e-10 and c["cert"]["feas"] < 1e-9 and c["cert"]["comp"] < 1e-8, c
+
+
+def test_oracle_end_game_solves_are_the_optimum():
+    """tests/golden/qp_end_game.npz: the QPs on which the oracle's interior point stalled furthest above its 1e-14 target -- two of
+    +-1 ulp ensemble members of the moving cloud's scene 0 (PAN iterations 4 / 5: three non-improving iterations at 1.3e-10 and
+    4.9e-10 on the dual residual floor of the reduced KKT solves, the second with an objective 2.8e-9 relative ABOVE HiGHS') and the
+    first QP of poly8 scene 961 (2.0e-12).  Found by the ensemble verdicts' cap on the oracle's merit.  dense_ipm now finishes such a
+    stalled end game with an active-set polish (nrmp_qp._polish): every one of them at <= 1e-12, the certificate feasible and
+    complementary, and the objective no worse than that of HiGHS (which shares no code with the oracle) by 1e-12 relative --
+    measured: 6e-12 / 2e-13 / 3e-16 BELOW it."""
+    from qp_highs import compare_with_highs
+    g = golden("qp_end_game")
+    n = int(g["count"])
+    assert n == 3
+    for i in range(n):
+        pb = _qp_problem(g, i)
+        s, u, d, info = solve_nrmp_qp(pb, return_info=True)
+        assert info["merit"] <= 1e-12, (i, info["merit"])
+        c = compare_with_highs(pb, s, u, d)
+        assert c["status"] == "Optimal" and c["obj_diff"] <= 1e-12 * max(1.0, abs(c["obj"])), (i, c)
+        cert = kkt_certificate(pb, s, u, d)
+        assert cert["dyn"] < 1e-10 and cert["feas"] < 1e-12 and cert["comp"] < 1e-12, (i, cert)
+
+
+def test_polish_is_an_end_game_step_only(monkeypatch):
+    """The polish may not turn a solve that got nowhere into an answer: capped at three iterations (merit ~0.3) the solve is still
+    refused, and a solve that ends at or below 1e-12 is returned exactly as the interior point left it."""
+    g = golden("qp_cases")
+    pb = _qp_problem(g, 0)
+    s0, u0, d0, info0 = solve_nrmp_qp(pb, return_info=True)
+    assert info0["merit"] <= 1e-12 and not info0["polished"]
+    monkeypatch.setattr(nrmp_qp, "POLISH_ABOVE", float("inf"))
+    s1, u1, d1, info1 = solve_nrmp_qp(pb, return_info=True)
+    assert np.array_equal(u0, u1) and info1["merit"] == info0["merit"]
+    monkeypatch.setattr(nrmp_qp, "POLISH_ABOVE", 1e-12)
+    monkeypatch.setattr(nrmp_qp, "MAX_ITER", 3)
+    s2, u2, d2, info2 = solve_nrmp_qp(pb, return_info=True, require=None)
+    assert info2["merit"] > 1e-6 and not info2["polished"]
+    with pytest.raises(QPNotConverged):
+        solve_nrmp_qp(pb)
 
 
 def test_condensed_solver_warm_start_rules():
@@ -279,13 +329,31 @@ def test_condensed_solver_repeats_a_jammed_cold_solve():
     np.testing.assert_allclose(u, u0, atol=5e-5)          # (acker QPs are flat in the steering direction: DESIGN.md section 5)
 
 
+def _oracle_traces(cfg, S):
+    """The oracle's own per-iteration trace of scenes 0..S-1: states, controls and the first M sorted points of every slice."""
+    from neupan_amd import scenes as sc_mod
+    tr_s, tr_u, tr_p = [], [], []
+    for b in range(S):
+        sc = sc_mod.make_scene(cfg, b)
+        orc = make_oracle(cfg)
+        ps = []
+        orig = orc.nrmp
+
+        def hook(*a, _ps=ps, _orig=orig):
+            _ps.append(np.stack([p[:, :cfg.nrmp_max_num].T for p in a[6]]))         # the first M sorted points of every slice
+            return _orig(*a)
+        orc.nrmp = hook
+        orc.forward(sc["nom_s"], sc["nom_u"], sc["ref_s"], sc["ref_us"], sc["points"], sc["velocities"])
+        tr_s.append(np.stack([t[0] for t in orc.trace])); tr_u.append(np.stack([t[1] for t in orc.trace])); tr_p.append(np.stack(ps))
+    return np.stack(tr_s), np.stack(tr_u), np.stack(tr_p)
+
+
 def test_one_step_explanations_flag_what_they_cannot_explain():
     """tests/parity_tools.one_step_consistency(explain=True), the machinery behind verdict D: fed with the ORACLE's own trace it
     finds nothing above the tolerance; fed with controls that are off by 1e-3 for no reason it reports every such step as
     UNEXPLAINED (no rank-M tie: the selection is the oracle's own; no sensitivity: the one-step ensemble under +-1 ulp does
     not move by a third of 1e-3 on these well-posed scenes)."""
     import dataclasses
-    from helpers import CONFIGS, make_oracle
     from neupan_amd import scenes as sc_mod
     from parity_tools import one_step_consistency, one_step_report
     name = "corridor_diff_small_k3"
@@ -293,20 +361,7 @@ def test_one_step_explanations_flag_what_they_cannot_explain():
     sc_mod.CONFIGS[name] = cfg
     try:
         S = 2
-        tr_s, tr_u, tr_p = [], [], []
-        for b in range(S):
-            sc = sc_mod.make_scene(cfg, b)
-            orc = make_oracle(cfg)
-            ps = []
-            orig = orc.nrmp
-
-            def hook(*a, _ps=ps, _orig=orig):
-                _ps.append(np.stack([p[:, :cfg.nrmp_max_num].T for p in a[6]]))         # the first M sorted points of every slice
-                return _orig(*a)
-            orc.nrmp = hook
-            orc.forward(sc["nom_s"], sc["nom_u"], sc["ref_s"], sc["ref_us"], sc["points"], sc["velocities"])
-            tr_s.append(np.stack([t[0] for t in orc.trace])); tr_u.append(np.stack([t[1] for t in orc.trace])); tr_p.append(np.stack(ps))
-        tr_s, tr_u, tr_p = np.stack(tr_s), np.stack(tr_u), np.stack(tr_p)
+        tr_s, tr_u, tr_p = _oracle_traces(cfg, S)
         dev, why = one_step_consistency(name, range(S), tr_s, tr_u, 1, explain=True, trace_pts=tr_p)
         assert dev.max() <= 1e-6 and why == []
         bad = tr_u.copy()
@@ -315,5 +370,71 @@ def test_one_step_explanations_flag_what_they_cannot_explain():
         rep = one_step_report(dev, why=why)
         assert len(why) == 1 and why[0]["scene"] == 1 and why[0]["iteration"] == 3 and why[0]["explained"] is None
         assert why[0]["slices_with_other_set"] == 0 and rep["unexplained"] == 1
+        # every oracle solve behind the verdict, the explanation's included, at the solver's floor
+        assert why[0]["oracle_merit_max"] <= 1e-12 and one_step_consistency.last_oracle_merit_max <= 1e-12, why[0]
+    finally:
+        del sc_mod.CONFIGS[name]
+
+
+def test_unconverged_oracle_solve_is_refused(monkeypatch):
+    """Round 6 found the oracle's QP solver handing out iterates at merit 0.69 - 0.89 (KKT stationarity 34 - 37) as solutions,
+    silently: every parity verdict judged against them.  solve_nrmp_qp now raises QPNotConverged above max(tol, 1e-9), so a
+    PanOracle cannot return one; require=None is the explicit opt-out that still returns the iterate.  A solve is made to stop
+    short by capping dense_ipm's iterations."""
+    from neupan_amd.scenes import make_scene
+    cfg = CONFIGS["diff_1k_T10_K10"]
+    sc = make_scene(cfg, 5)
+    args = (sc["nom_s"], sc["nom_u"], sc["ref_s"], sc["ref_us"], sc["points"], sc["velocities"])
+    orc = make_oracle(cfg, iter_num=2)
+    orc.forward(*args)
+    assert len(orc.qp_log) == 2 and orc.qp_merit_max() <= 1e-12, orc.qp_log
+    assert orc.last_qp_info is orc.qp_log[-1] and orc.last_qp_info["iters"] > 3
+    pb = orc.last_problem
+    s0, u0, d0 = solve_nrmp_qp(pb)
+    # a looser target is honoured (tests/tools/qp_tolerance_sweep.py): the cap follows tol
+    solve_nrmp_qp(pb, tol=1e-8)
+
+    monkeypatch.setattr(nrmp_qp, "MAX_ITER", 3)
+    short = make_oracle(cfg, iter_num=2)
+    with pytest.raises(QPNotConverged) as e:
+        short.forward(*args)
+    assert e.value.merit > 1e-9 and e.value.iters <= 3 and (e.value.T, e.value.M) == (cfg.T, cfg.nrmp_max_num), e.value
+    assert short.qp_log == [] and short.trace == []          # nothing of the refused solve was kept
+    with pytest.raises(QPNotConverged):
+        solve_nrmp_qp(pb)
+    s, u, d, info = solve_nrmp_qp(pb, return_info=True, require=None)      # the opt-out: the iterate, labelled
+    assert info["merit"] > 1e-9 and info["iters"] <= 3
+    assert kkt_certificate(pb, s, u, d)["stat"] > 1e-6 and np.abs(u - u0).max() > 1e-6   # and it is not the optimum
+
+
+def test_one_step_explanation_cannot_rest_on_an_unconverged_oracle(monkeypatch):
+    """The hole: _explain_step calls a deviation "explained" by the oracle's own one-step spread when six perturbed oracle runs
+    spread by a fifth of it.  A perturbed run that stops short spreads by anything, so an unjustified 1e-3 step (the one
+    test_one_step_explanations_flag_what_they_cannot_explain reports as UNEXPLAINED) would pass as "one-step ensemble spread".
+    With the perturbed runs capped at three interior-point iterations the verdict must not come back at all: QPNotConverged."""
+    import dataclasses
+    import parity_tools as pt
+    from neupan_amd import scenes as sc_mod
+    name = "corridor_diff_small_k3"
+    cfg = dataclasses.replace(CONFIGS["corridor_diff_small"], name=name, iter_num=3, n_points=120)
+    sc_mod.CONFIGS[name] = cfg
+    try:
+        S = 2
+        tr_s, tr_u, tr_p = _oracle_traces(cfg, S)
+        bad = tr_u.copy()
+        bad[1, 2] += np.float32(1e-3 / np.sqrt(bad[1, 2].size))          # one step, control L2 = 1e-3
+        explain = pt._explain_step
+
+        def explain_with_short_solves(*a, **k):                    # only the explanation's own oracle runs stop short
+            cap = nrmp_qp.MAX_ITER
+            nrmp_qp.MAX_ITER = 3
+            try:
+                return explain(*a, **k)
+            finally:
+                nrmp_qp.MAX_ITER = cap
+        monkeypatch.setattr(pt, "_explain_step", explain_with_short_solves)
+        with pytest.raises(QPNotConverged):
+            # (cores = 1: the jobs run in this process, where the patch is)
+            pt.one_step_consistency(name, range(S), tr_s, bad, 1, explain=True, trace_pts=tr_p)
     finally:
         del sc_mod.CONFIGS[name]
