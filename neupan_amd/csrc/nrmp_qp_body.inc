@@ -486,6 +486,13 @@
   const bool can_warm = WARM && wrm && flags && flags[b * 4 + 2];
   PROF(0);
   bool adj = false;                      // BWD: the pass below is the adjoint solve
+  // BWD: the residual phase of the converged iterate runs once more with the barrier weights l/w of the linear rows capped at
+  // QP_ADJ_DMAX before the adjoint solve.  Uncapped they reach 1e12 .. 1e19 on the active rows, and K' = H + C' (l/w) C formed
+  // with them keeps H only to (l/w) * 2^-53: the gradient came out up to 5e-2 off the derivative of the solution map
+  // (tests/test_nrmp_backward.py, oracle.nrmp_backward.backward_active_set).  At 1e9 a row is a spring stiff enough that the
+  // bias is ~1e-7 and the rounding ~1e-7 of the gradient as well.
+  bool adj_cap = false;
+  constexpr double QP_ADJ_DMAX = 1e9;
   int it_total = 0, warm_code = 0;       // diagnostics: iterations over all attempts; 1 warm start used, 2 / 3 dropped at it 0 / 6, 4 not converged, 5 cold retry
   bool warm_now = can_warm;              // the solve in progress started from the previous solution
   bool need_cold = false;                // re-initialise at the top of the next iteration (a dropped warm attempt)
@@ -623,7 +630,8 @@
       }
       const double rp = (cx + w.x - c.bp) * c.actf, rm = (w.y - cx - c.bm) * c.actf;
       ST_ROW(Rr2, r2, p, rp, rm);
-      st2(iwc + 2 * p, fast_rcp(w.x), fast_rcp(w.y));
+      if (BWD && adj_cap) st2(iwc + 2 * p, fmin(fast_rcp(w.x), QP_ADJ_DMAX / l.x), fmin(fast_rcp(w.y), QP_ADJ_DMAX / l.y));
+      else st2(iwc + 2 * p, fast_rcp(w.x), fast_rcp(w.y));
       rpmax = fmax(rpmax, fmax(fabs(rp), fabs(rm)));
       gap += l.x * w.x + l.y * w.y;             // (a switched-off pair keeps l = 0)
     }
@@ -825,6 +833,7 @@
       }
       if constexpr (BWD) {
         if (!bw.grad_theta) break;
+        if (!adj_cap && it < QP_MAX_IT) { adj_cap = true; continue; }     // the same iterate once more, weights capped
         adj = true;                      // factor K' of this final iterate once more, then solve K' v = dL/dx
       } else {
         break;

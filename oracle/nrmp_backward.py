@@ -44,6 +44,11 @@ from .condensed_ipm import condense, solve_condensed
 from .nrmp_qp import NrmpProblem, solve_nrmp_qp
 
 
+# the barrier weight lc/wc of a linear row in the adjoint solve is capped here (the kernel's QP_ADJ_DMAX): uncapped, forming K
+# at a converged iterate loses H to rounding (backward_active_set)
+ADJ_DMAX = 1e9
+
+
 def backward_ipm(pb: NrmpProblem, gs, gu, gd, tol=1e-12):
     """(tol: the implicit gradient is taken at the interior-point iterate; at 1e-12 the barrier Newton matrix is still
     well enough conditioned for it -- the forward solves stop at 1e-14, oracle/nrmp_qp.py.)
@@ -56,20 +61,32 @@ def backward_ipm(pb: NrmpProblem, gs, gu, gd, tol=1e-12):
     x = np.concatenate([u.T.reshape(-1), [] if pb.no_obs else d.reshape(-1)])
     ro = pb.ro_obs
     wc = np.maximum(c - C @ x, 1e-300)
-    Dc = lc / wc
+    Dc = np.minimum(lc / wc, ADJ_DMAX)          # (the kernel's cap: backward_active_set's docstring)
     K = H + C.T @ (Dc[:, None] * C)
     if not pb.no_obs:
         wf = F @ x - f + lf / ro
         Df = lf / (wf + lf / ro)
         K = K + F.T @ (Df[:, None] * F)
-    gx = np.zeros(H.shape[0])
+    gx = _upstream_x(pb, Phi, H.shape[0], gs, gu, gd)
+    v = np.linalg.solve(K, gx)
+    return _theta_gradient(pb, Phi, C, s, u, v, Dc * (C @ v))
+
+
+def _upstream_x(pb, Phi, n, gs, gu, gd):
+    """dL/dx of x = [u, d] for L = <gs, s> + <gu, u> + <gd, d>, s_t = Phi_t u + c_t"""
+    T, nu = pb.T, 2 * pb.T
+    gx = np.zeros(n)
     gx[:nu] = np.asarray(gu, dtype=np.float64).T.reshape(-1)
     for t in range(T + 1):
         gx[:nu] += Phi[t].T @ np.asarray(gs, dtype=np.float64)[:, t]
     if not pb.no_obs and gd is not None:
         gx[nu:] = np.asarray(gd, dtype=np.float64).reshape(-1)
-    v = np.linalg.solve(K, gx)
-    dc = Dc * (C @ v)
+    return gx
+
+
+def _theta_gradient(pb, Phi, C, s, u, v, dc):
+    """dL/dtheta from v = dL/dg (negated) and dc = dL/dc of the inequality rows (module docstring)"""
+    T, nu = pb.T, 2 * pb.T
     mask = pb.state_weight()
     out = dict(q_s=np.zeros(3), p_u=0.0, eta=0.0, d_max=0.0, d_min=0.0, nom_s=np.zeros((3, T + 1)))
     ref = pb.qref_s / np.where(pb.q_s == 0, 1.0, pb.q_s)[:, None]
@@ -86,6 +103,53 @@ def backward_ipm(pb: NrmpProblem, gs, gu, gd, tol=1e-12):
         out["d_max"] = float(np.sum(dc[base::2]))
         out["d_min"] = float(-np.sum(dc[base + 1::2])) if pb.d_min > 0 else 0.0
     return out
+
+
+def backward_active_set(pb: NrmpProblem, gs, gu, gd, info=None):
+    """The derivative of the solution map itself, independent of any interior-point iterate: the KKT system of the
+    active set at the converged solution (tol 1e-14), solved by a null-space method.
+    backward_ipm's barrier matrix K = H + C' (lc/wc) C + F' Df F tends to it as mu -> 0, but forming K at a converged iterate
+    adds lc/wc ~ 1e12 .. 1e15 on the active rows to entries of H of order one: H loses ~ (lc/wc) * 2^-53 of its value
+    there, and the gradient of such an iterate moves by up to 1e-2 from one iterate to the next.  Here the active rows
+    are equalities (the hinge rows with lf > 0 are the penalty ro (f - F x)^2 / 2), eliminated exactly:
+        v = Z (Z' Hh Z)^-1 Z' gx,  Hh = H + ro F_a' F_a,  Z a basis of the null space of the active rows C_a,
+        dL/dc_a = the least-squares multipliers of  C_a' y = gx - Hh v  (the limit of (lc/wc) C v).
+    info (dict, optional) receives `margin`: the smallest max(lam, w) over the rows (strict complementarity: near 0 the
+    active set is ambiguous and the solution map has no derivative), `residual`: |C_a' y - (gx - Hh v)| / |gx| (large when
+    the active rows cannot carry the load: a misread active set), and `rcond` of Z' Hh Z (0: a flat direction)."""
+    H, g, F, f, C, c, Phi, cv = condense(pb)
+    s, u, d, sinfo = solve_condensed(pb)
+    _, lc, lf = sinfo["warm"]
+    x = np.concatenate([u.T.reshape(-1), [] if pb.no_obs else d.reshape(-1)])
+    wc = c - C @ x
+    act = lc > wc
+    Hh = H.copy()
+    lam, w = [lc], [wc]
+    if not pb.no_obs:
+        wf = F @ x - f + lf / pb.ro_obs
+        Fa = F[lf > wf]
+        Hh = Hh + pb.ro_obs * Fa.T @ Fa
+        lam.append(lf); w.append(wf)
+    gx = _upstream_x(pb, Phi, H.shape[0], gs, gu, gd)
+    A = C[act]
+    if A.shape[0]:
+        _, sv, Vt = np.linalg.svd(A)
+        rank = int(np.sum(sv > 1e-10 * sv[0]))
+        Z = Vt[rank:].T
+    else:
+        Z = np.eye(H.shape[0])
+    R = Z.T @ Hh @ Z
+    v = Z @ np.linalg.solve(R, Z.T @ gx) if Z.shape[1] else np.zeros(H.shape[0])
+    dc = np.zeros(C.shape[0])
+    r = gx - Hh @ v
+    if A.shape[0]:
+        dc[act] = np.linalg.lstsq(A.T, r, rcond=None)[0]
+    if info is not None:
+        ev = np.linalg.eigvalsh(R) if R.size else np.ones(1)
+        info["margin"] = float(np.min(np.maximum(np.abs(np.concatenate(lam)), np.abs(np.concatenate(w)))))
+        info["residual"] = float(np.linalg.norm(C.T @ dc - r) / max(np.linalg.norm(gx), 1e-300))
+        info["rcond"] = float(ev.min() / ev.max())
+    return _theta_gradient(pb, Phi, C, s, u, v, dc)
 
 
 def _with(pb: NrmpProblem, **kw):

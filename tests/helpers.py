@@ -1,4 +1,5 @@
 """Shared test plumbing: fixture paths, oracle construction from a SceneConfig."""
+import dataclasses
 import os
 
 import numpy as np
@@ -16,6 +17,34 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 HARD_SCENES = [("poly8_5k_T10_K10", 122, 0), ("poly8_5k_T10_K10", 202, 3), ("poly8_5k_T10_K10", 408, 4),
                ("poly8_5k_T10_K10", 961, 0), ("dyna_4k_T10_K10", 204, 0), ("acker_2k_T20_K15", 544, 0),
                ("acker_2k_T20_K15", 850, 1), ("polygon_5k_T10_K10", 1479, 5)]
+
+
+OMNI = dict(kinematics="omni", length=1.6, width=2.0, max_speed=[8, 6.28], max_acce=[3, 3])
+
+# The shapes and edges the QP gradient (npa_nrmp_backward) is pinned at: case -> (workload, robot (None: the workload's),
+# overrides of the planner / oracle, points per scene).  T = 10 and T = 20 run the register-resident instantiations, T = 8
+# and T = 13 the generic one; `sparse` has fewer points than M = 10 rows (count < M, the rows padded with the first);
+# `no_obstacles` has no d, eta, d_max or d_min terms; with d_min <= 0 the rows -d_t <= -d_min drop d_min.
+GRAD_CASES = {
+    "diff_T10": ("diff_1k_T10_K10", None, {}, 300),
+    "acker_T20": ("acker_2k_T20_K15", None, {}, 300),
+    "diff_T8": ("diff_1k_T10_K10", None, dict(T=8), 300),
+    "diff_T13": ("diff_1k_T10_K10", None, dict(T=13), 300),
+    "omni_T10": ("diff_1k_T10_K10", OMNI, {}, 64),
+    "dyna_T10": ("dyna_4k_T10_K10", None, {}, 300),
+    "no_obstacles": ("diff_1k_T10_K10", None, dict(nrmp_max_num=0), 300),
+    "sparse": ("diff_1k_T10_K10", None, {}, 7),
+    "dmin_negative": ("diff_1k_T10_K10", None, dict(adjust=dict(d_min=-0.1)), 300),
+}
+
+
+def grad_case(case):
+    """(cfg, robot_kw, overrides for make_oracle / make_gpu_pan, points per scene) of GRAD_CASES[case]"""
+    cfgname, robot_kw, over, npts = GRAD_CASES[case]
+    cfg, over = CONFIGS[cfgname], dict(over)
+    if "T" in over:
+        cfg = dataclasses.replace(cfg, T=over.pop("T"))
+    return cfg, robot_kw, dict(over, dune_max_num=npts), npts
 
 
 def ckpt_path(name):

@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import CONFIGS, HARD_SCENES, golden, make_oracle
+from helpers import CONFIGS, HARD_SCENES, OMNI, golden, make_oracle
 from neupan_amd.scenes import make_batch, make_scene
 from oracle import pan_oracle as po
 from oracle.nrmp_qp import kkt_certificate
@@ -19,7 +19,6 @@ pytestmark = pytest.mark.gpu
 
 POLY = dict(kinematics="diff", vertices=[[-0.8, -1.0], [-1.8, 1.0], [1.8, 1.0], [0.8, -1.0]],
             max_speed=[8, 3], max_acce=[8, 3])
-OMNI = dict(kinematics="omni", length=1.6, width=2.0, max_speed=[8, 6.28], max_acce=[3, 3])
 
 STAGES = [("diff_n1000", "diff_1k_T10_K10", None, None, {}),
           ("dyna_n300", "dyna_4k_T10_K10", None, None, dict(dune_max_num=300)),
