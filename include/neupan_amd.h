@@ -157,6 +157,21 @@ int npa_pack_cache_stats(int64_t *calibrations, int64_t *shared_creates, int64_t
 /* Replaces NRMP.update_adjust_parameters_value (nrmp.py:170-217). */
 int npa_set_adjust(npa_handle *h, const float q_s[3], float p_u, float eta, float d_max, float d_min);
 
+/* Per-scene adjust parameters.  The reference makes (q_s, p_u, eta, d_max, d_min) parameters of ONE problem
+ * (neupan/blocks/nrmp.py:79-95) that are set per planner (nrmp.py:170-217); a batch here is B such problems, and this gives
+ * every scene its own set -- a fleet whose robots want different d_max / eta, a population of candidate sets for LON.
+ *   theta: DEVICE pointer to [batch][8] fp32: q_s[0..2], p_u, eta, d_max, d_min, reserved -- the columns of
+ *   npa_nrmp_backward's grad_theta, so a gradient row and a parameter row line up.
+ * The block is caller-owned and is READ AT KERNEL RUN TIME, in stream order: writing new rows into it changes what the
+ * next launch -- or the next replay of a captured graph -- uses, and it must stay valid while work that uses it is in
+ * flight.  The pointer is sticky on the handle; theta == NULL (any batch) returns the handle to its uniform set, which
+ * npa_set_adjust keeps updating meanwhile.  While it is set, every entry point that solves the QP uses row b for scene b:
+ * npa_forward_batch / _flags / _begin / _iter / _end, npa_forward_batch_group (calls that differ only in their block
+ * still share merged launches), npa_nrmp_stage and npa_nrmp_backward, whose grad_theta[b] is then the gradient with
+ * respect to theta[b].  A call with another batch than the registered one returns NPA_E_ARG.  A block that repeats the
+ * uniform set in every row gives the uniform path's results bitwise. */
+int npa_set_adjust_batch(npa_handle *h, const float *theta, int batch);
+
 /* Bytes of caller-owned device memory npa_forward_batch needs for `batch` scenes:
  * scratch (no meaning between calls) and state (the stop criterion's memory of the
  * previous iterate, pan.py:100-105 / 215-243; zero it to reset a scene). */

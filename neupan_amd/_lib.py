@@ -57,6 +57,7 @@ SYMBOLS = {
     "npa_selftest_flags": (_I, [_P, C.POINTER(C.c_int)]),
     "npa_pack_cache_stats": (_I, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "npa_set_adjust": (_I, [_P, C.POINTER(C.c_float * 3), C.c_float, C.c_float, C.c_float, C.c_float]),
+    "npa_set_adjust_batch": (_I, [_P, _P, _I]),
     "npa_workspace_bytes": (_SZ, [_P, _I]),
     "npa_state_bytes": (_SZ, [_P, _I]),
     "npa_workspace_qp_info_offset": (_SZ, [_P, _I]),

@@ -59,7 +59,7 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                                     float* out_s, float* out_u, float* out_d, float* out_min_distance,
                                     int* out_iters, float* out_nrmp_points, int* flags, float* state,
                                     double* qp_info, double* warm, float* trig_out, float* dbg_abc, float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, int aset_launch);
+                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, int aset_launch, const float* theta);
 extern "C" size_t npa_qp_shmem_bytes(int T, int M);
 extern "C" int npa_select_geo_group_supported(int E);
 extern "C" hipError_t npa_launch_k16_calib(const DevParams& P, const float* wpack, int nside, float half, float inner, unsigned* out,
@@ -104,6 +104,7 @@ struct PendingCall {
   bool dune = false;
   const float *nom_s = nullptr, *nom_u = nullptr;     // (the staging launch's sources: the merged group path launches it later)
   bool reset_state = false;
+  const float* theta = nullptr;      // the handle's per-scene parameter block as it was when the call began (npa_set_adjust_batch)
 };
 
 // ---- one weight pack, one calibration and one key table per (checkpoint, polygon, knobs, device) per PROCESS -----------------
@@ -145,6 +146,10 @@ struct npa_handle {
   PendingCall pc;
   std::mutex mu;              // guards pc (two threads on ONE handle are a caller's bug; this makes it an error, not a race)
   DevParams P;
+  // per-scene adjust parameters (npa_set_adjust_batch): a caller-owned DEVICE block [theta_batch][8] the QP launches read at run
+  // time, or null: the uniform set in P.  Not part of P -- calls that differ in it still share a merged launch (QpCall::theta)
+  const float* theta = nullptr;
+  int theta_batch = 0;
   float* wpack = nullptr;     // device
   int device = 0;
   int n_cu = 256;
@@ -215,7 +220,7 @@ extern "C" const char* npa_last_error(void) { return g_err.c_str(); }
 #ifndef NPA_HIPCC_VERSION
 #define NPA_HIPCC_VERSION "unknown"
 #endif
-extern "C" const char* npa_version(void) { return "neupan_amd 0.3 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
+extern "C" const char* npa_version(void) { return "neupan_amd 0.4 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
 static int mdim(const DevParams& P) { return P.M > 0 ? P.M : 1; }
 // per-slice stride of the key buffer inside the workspace: none with geometric keys (select_kernel keeps them in LDS)
 static int kstride(const npa_handle* h) { return h->key_terms == 4 ? 0 : h->P.key_stride; }
@@ -961,6 +966,23 @@ extern "C" int npa_set_adjust(npa_handle* h, const float q_s[3], float p_u, floa
   return NPA_OK;
 }
 
+extern "C" int npa_set_adjust_batch(npa_handle* h, const float* theta, int batch) {
+  if (!h) return fail(NPA_E_ARG, "npa_set_adjust_batch: null handle");
+  if (theta && batch < 1) return fail(NPA_E_ARG, "npa_set_adjust_batch: batch < 1");
+  std::lock_guard<std::mutex> lock(h->mu);
+  h->theta = theta;
+  h->theta_batch = theta ? batch : 0;
+  return NPA_OK;
+}
+// a solve of `batch` scenes on a handle whose block was registered for another number of rows would read past it (or leave
+// rows unread): refused
+static int check_theta_batch(const npa_handle* h, int batch, const char* who) {
+  if (h->theta && batch != h->theta_batch)
+    return fail(NPA_E_ARG, std::string(who) + ": batch " + std::to_string(batch) + " differs from the " + std::to_string(h->theta_batch) +
+                               " rows registered with npa_set_adjust_batch");
+  return NPA_OK;
+}
+
 extern "C" size_t npa_workspace_bytes(const npa_handle* h, int batch) {
   if (!h || batch < 1) return 0;
   return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h)).total * sizeof(float);
@@ -1082,9 +1104,10 @@ extern "C" int npa_nrmp_stage(npa_handle* h, int batch, const float* nom_s, cons
     return fail(NPA_E_ARG, "npa_nrmp_stage: bad argument");
   if (h->P.M > 0 && (!mu_sorted || !lam_sorted || !pts_sorted || !count || !out_d))
     return fail(NPA_E_ARG, "npa_nrmp_stage: obstacle arrays required when nrmp_max_num > 0");
+  if (int rc = check_theta_batch(h, batch, "npa_nrmp_stage")) return rc;
   HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
                         out_s, out_u, out_d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        qp_info, nullptr, nullptr, nullptr, nullptr, x64, (hipStream_t)stream, nullptr, nullptr, 0));
+                        qp_info, nullptr, nullptr, nullptr, nullptr, x64, (hipStream_t)stream, nullptr, nullptr, 0, h->theta));
   return NPA_OK;
 }
 
@@ -1097,7 +1120,8 @@ extern "C" int npa_nrmp_params(npa_handle* h, int batch, const float* nom_s, con
   // (the reference trajectory only enters the cost: the nominal arrays stand in for it, the kernel returns before the solve)
   HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, nom_s, nom_u, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, out_abc, h->P.M > 0 ? out_f : nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, 0));
+                        nullptr, nullptr, nullptr, out_abc, h->P.M > 0 ? out_f : nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, 0,
+                        nullptr));         // (the linearisation and the hinge rows do not depend on the adjust parameters)
   return NPA_OK;
 }
 
@@ -1106,7 +1130,7 @@ extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, cons
                                              const float* lam_sorted, const float* pts_sorted, const int* count,
                                              float* out_s, float* out_u, float* out_d, const float* grad_s,
                                              const float* grad_u, const float* grad_d, float* grad_theta,
-                                             float* grad_nom_s, double* qp_info, hipStream_t stream);
+                                             float* grad_nom_s, double* qp_info, hipStream_t stream, const float* theta);
 extern "C" int npa_nrmp_backward(npa_handle* h, int batch, const float* nom_s, const float* nom_u, const float* ref_s,
                                  const float* ref_us, const float* mu_sorted, const float* lam_sorted,
                                  const float* pts_sorted, const int32_t* count, float* out_s, float* out_u, float* out_d,
@@ -1116,8 +1140,9 @@ extern "C" int npa_nrmp_backward(npa_handle* h, int batch, const float* nom_s, c
     return fail(NPA_E_ARG, "npa_nrmp_backward: bad argument");
   if (h->P.M > 0 && (!mu_sorted || !lam_sorted || !pts_sorted || !count || !out_d))
     return fail(NPA_E_ARG, "npa_nrmp_backward: obstacle arrays required when nrmp_max_num > 0");
+  if (int rc = check_theta_batch(h, batch, "npa_nrmp_backward")) return rc;
   HIP_TRY(npa_launch_qp_backward(h->P, batch, nom_s, nom_u, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, count,
-                                 out_s, out_u, out_d, grad_s, grad_u, grad_d, grad_theta, grad_nom_s, qp_info, (hipStream_t)stream));
+                                 out_s, out_u, out_d, grad_s, grad_u, grad_d, grad_theta, grad_nom_s, qp_info, (hipStream_t)stream, h->theta));
   return NPA_OK;
 }
 
@@ -1220,6 +1245,7 @@ static int forward_begin_impl(npa_handle* h, int batch, int n_stride, const floa
   std::lock_guard<std::mutex> lock(h->mu);
   PendingCall* pc = &h->pc;
   if (pc->active) return fail(NPA_E_ARG, "npa_forward_begin: previous forward on this handle not ended");
+  if (int rc = check_theta_batch(h, batch, "npa_forward_begin")) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   const int T = P.T;
   const bool reset_state = (flags & NPA_FWD_RESET_STATE) != 0;
@@ -1231,6 +1257,7 @@ static int forward_begin_impl(npa_handle* h, int batch, int n_stride, const floa
   pc->state = (float*)state; pc->stream = stream;
   pc->dune = P.M > 0 && points != nullptr;
   pc->nom_s = nom_s; pc->nom_u = nom_u; pc->reset_state = reset_state;
+  pc->theta = h->theta;
   if (pc->dune) key_policy(h, batch, n_stride);
   if (launch_stage) {
     // one launch instead of two copies and up to three memsets (each costs tens of microseconds of stream time)
@@ -1387,7 +1414,7 @@ extern "C" int npa_group_iter_merged(int n, const npa_forward_call* calls, int k
     Q.c[c] = QpCall{cur_s, cur_u, pc.ref_s, pc.ref_us, ws + L.mu, ws + L.lam, ws + L.pts, ws + L.dist, (const int*)(ws + L.count),
                     cur_s, cur_u, ws + L.cur_d, pc.out_s, pc.out_u, pc.out_d, pc.out_md, pc.out_iters, pc.out_np,
                     (int*)(ws + L.flags), pc.state, (double*)(ws + L.qp_info), h->qp_warm ? (double*)(ws + L.warm) : nullptr,
-                    pc.dune ? ws + L.trig : nullptr};
+                    pc.dune ? ws + L.trig : nullptr, pc.theta};
   }
   EventPair* ev = next_event(h0, h0->ev_qp, h0->n_qp);
   HIP_TRY(npa_launch_qp_group(P, Q, n, batch, stream, ev ? ev->a : nullptr, ev ? ev->b : nullptr));
@@ -1446,14 +1473,14 @@ extern "C" int npa_forward_iter(npa_handle* h, int k) {
     HIP_TRY(npa_launch_qp(Pa, batch, 0, cur_s, cur_u, pc->ref_s, pc->ref_us, mu, lam, pts, dist, count, cur_s, cur_u,
                           cur_d, pc->out_s, pc->out_u, pc->out_d, pc->out_md, pc->out_iters, pc->out_np, flags,
                           pc->state, qp_info, (double*)(ws + L.warm), pc->dune ? ws + L.trig : nullptr,
-                          nullptr, nullptr, nullptr, stream, eva ? eva->a : nullptr, eva ? eva->b : nullptr, 1));
+                          nullptr, nullptr, nullptr, stream, eva ? eva->a : nullptr, eva ? eva->b : nullptr, 1, pc->theta));
   }
   EventPair* ev = next_event(h, h->ev_qp, h->n_qp);
   HIP_TRY(npa_launch_qp(P, batch, 0, cur_s, cur_u, pc->ref_s, pc->ref_us, mu, lam, pts, dist, count, cur_s, cur_u,
                         cur_d, pc->out_s, pc->out_u, pc->out_d, pc->out_md, pc->out_iters, pc->out_np, flags,
                         pc->state, qp_info, h->qp_warm ? (double*)(ws + L.warm) : nullptr, pc->dune ? ws + L.trig : nullptr,
                         nullptr, nullptr, nullptr, stream,
-                        ev ? ev->a : nullptr, ev ? ev->b : nullptr, 0));
+                        ev ? ev->a : nullptr, ev ? ev->b : nullptr, 0, pc->theta));
   if (h->key_auto && pc->dune && k == P.K - 1)
     HIP_TRY(hipMemcpyAsync(h->sel_stats_host, h->sel_stats_dev, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   return NPA_OK;

@@ -81,7 +81,8 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                                     float* out_min_distance, int* out_iters, float* out_nrmp_points, int* flags,
                                     float* state, double* qp_info, double* warm, float* trig_out, float* dbg_abc,
                                     float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, int aset_launch) {
+                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, int aset_launch,
+                                    const float* theta) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;     // tests: the generic (LDS) instantiation for every (T, M)
   const bool fast = qp_fast_path(P.T, P.M) && !force_generic;
   const size_t shmem = npa_qp_shmem_bytes_path(P.T, P.M, fast ? 1 : 0);      // one scene (wave) per workgroup, see the kernel
@@ -106,7 +107,7 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                         P, cur_s_in, cur_u_in, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, dist_sorted, count,  \
                         cur_s_out, cur_u_out, cur_d_out, out_s, out_u, out_d, out_min_distance, out_iters,            \
                         out_nrmp_points, flags, state, qp_info, warm, scene0, batch,                                 \
-                        QpBackward{nullptr, nullptr, nullptr, nullptr, nullptr, dbg_abc, dbg_f, dbg_x}, trig_out)
+                        QpBackward{nullptr, nullptr, nullptr, nullptr, nullptr, dbg_abc, dbg_f, dbg_x}, trig_out, theta)
   const bool scan_wide = qp_scan_wide();
   if (aset_launch) {
     // the active-set launch that precedes the interior-point launch of the same PAN iteration (see the kernel's top)
@@ -157,7 +158,7 @@ extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, cons
                                              const float* lam_sorted, const float* pts_sorted, const int* count,
                                              float* out_s, float* out_u, float* out_d, const float* grad_s,
                                              const float* grad_u, const float* grad_d, float* grad_theta,
-                                             float* grad_nom_s, double* qp_info, hipStream_t stream) {
+                                             float* grad_nom_s, double* qp_info, hipStream_t stream, const float* theta) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;
   const bool fast = qp_fast_path(P.T, P.M) && !force_generic && (P.T <= 16 || qp_scan_wide());
   const size_t wave_bytes = npa_qp_shmem_bytes_path(P.T, P.M, fast ? 1 : 0);
@@ -176,7 +177,7 @@ extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, cons
                      ref_us, mu_sorted, lam_sorted, pts_sorted, (const float*)nullptr, count, out_s, out_u, out_d,        \
                      (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr,  \
                      (int*)nullptr, (float*)nullptr, qp_info, (double*)nullptr, 0, batch,                                 \
-                     QpBackward{grad_s, grad_u, grad_d, grad_theta, grad_nom_s, nullptr, nullptr, nullptr}, (float*)nullptr)
+                     QpBackward{grad_s, grad_u, grad_d, grad_theta, grad_nom_s, nullptr, nullptr, nullptr}, (float*)nullptr, theta)
   if (fast && P.T == 10) QPB_LAUNCH(10, 10, true);
   else if (fast && P.T == 20) QPB_LAUNCH(20, 10, true, true);
   else QPB_LAUNCH(0, 0, true);

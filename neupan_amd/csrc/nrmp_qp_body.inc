@@ -2,7 +2,8 @@
 // + stop test), as statements: included by nrmp_qp_kernel and nrmp_qp_group_kernel (nrmp_qp_device.h: workgroup -> scene /
 // (call, scene)).  A textual body, not a function of its own, so
 // that the kernel's token stream -- and with it its machine code, which the counter records of profiles/ are tied to --
-// is what it was.  Expects in scope: the kernel's parameters, `sm_all` (the scene's LDS block, LDS address 0), `lane`, `b`.
+// is what it was.  Expects in scope: the kernel's parameters (`theta` among them), `sm_all` (the scene's LDS block, LDS address 0), `lane`, `b`
+// (the GLOBAL scene number: the row of every per-scene array, theta included).
   double* sm = sm_all;
   if (flags && flags[b * 4 + 0]) return;
   // Two launches per PAN iteration when the active-set iteration is on (P.qp_aset): the ASET instantiation goes first and tries
@@ -31,7 +32,17 @@
   const int ldp = nu + 1, ldk = nu + 1;       // odd leading dimensions
   const int npair = nu * (nu + 1) / 2;
   const double ro = P.ro_obs, iro = uni64(1.0 / ro);
-  const double dmin0 = uni64(fmax((double)P.d_min, 0.0)), dmaxv = uni64((double)P.d_max);
+  // the adjust parameters of THIS scene: row b of the caller's block theta [B][8] = q_s[0..2], p_u, eta, d_max, d_min, reserved
+  // (npa_set_adjust_batch; nrmp.py:79-95 makes them per-problem leaves), else the handle's uniform set out of the kernel
+  // arguments.  One wave is one scene: the row is wave-uniform, read once here and kept scalar; everything below uses these
+  // copies with the arithmetic it always had, so a block that repeats the uniform set gives the uniform path's bits.
+  float qs0 = P.q_s[0], qs1 = P.q_s[1], qs2 = P.q_s[2], p_u = P.p_u, eta = P.eta, d_max = P.d_max, d_min = P.d_min;
+  if (theta) {
+    const float* trow = theta + (size_t)b * 8;
+    qs0 = uni32(trow[0]); qs1 = uni32(trow[1]); qs2 = uni32(trow[2]); p_u = uni32(trow[3]);
+    eta = uni32(trow[4]); d_max = uni32(trow[5]); d_min = uni32(trow[6]);
+  }
+  const double dmin0 = uni64(fmax((double)d_min, 0.0)), dmaxv = uni64((double)d_max);
   // T = 10, M = 10: each lane owns ONE pair of hinge rows (lanes < T M / 2 = 50) and ONE pair of u / d rows (lanes <
   // 5T - 2 = 48) in every phase, so the per-row arrays that only their owner touches -- slacks, residuals, multiplier
   // directions, the hinge offsets -- live in registers, not in LDS (7 arrays, 5.5 KB of the scene's 26 KB: the LDS
@@ -236,10 +247,10 @@
 
   // ---- cost: H (constant block), state-cost gradient at u=0 ---------------------------------
   const double m2 = (P.kin == 2) ? 0.0 : 1.0;            // omni: theta row not in the state cost
-  const double W0 = uni64(2.0 * (double)P.q_s[0] * (double)P.q_s[0] + P.bk);
-  const double W1 = uni64(2.0 * (double)P.q_s[1] * (double)P.q_s[1] + P.bk);
-  const double W2 = uni64(2.0 * m2 * (double)P.q_s[2] * (double)P.q_s[2] + P.bk);
-  const double pu = uni64((double)P.p_u);
+  const double W0 = uni64(2.0 * (double)qs0 * (double)qs0 + P.bk);
+  const double W1 = uni64(2.0 * (double)qs1 * (double)qs1 + P.bk);
+  const double W2 = uni64(2.0 * m2 * (double)qs2 * (double)qs2 + P.bk);
+  const double pu = uni64((double)p_u);
   if constexpr (SCAN) {
     // the state cost's Hessian Phi' W Phi is not formed: W joins S'_t in the P_t blocks of every iteration (K' build), and the
     // packed triangle only carries the band terms of C_u' D C_u (+ 2 p_u^2 on the speed diagonal), zero elsewhere
@@ -268,7 +279,7 @@
   double hdiag = 0, hoff = 0;
   for (int q = lane; q < 3 * T; q += QP_THREADS) {
     int t = q / 3, k = q - 3 * t;
-    const float qsk = k == 0 ? P.q_s[0] : (k == 1 ? P.q_s[1] : P.q_s[2]);
+    const float qsk = k == 0 ? qs0 : (k == 1 ? qs1 : qs2);
     double qk = qsk, mk = (k == 2) ? m2 : 1.0, c = cv[q];
     // gamma_a = q_s * ref_s is an fp32 product in the reference (nrmp.py:158)
     double r = (double)__fmul_rn(qsk, rs[k * (T + 1) + t + 1]);
@@ -325,7 +336,7 @@
   // BWD instantiations (one start, the one that never jammed; a restart path there costs registers the adjoint needs)
   bool cold_alt = BWD;
   QP_COLD_INIT();
-  double gmax = obs ? (double)P.eta : 0.0;
+  double gmax = obs ? (double)eta : 0.0;
   // g_u = Phi' lin - 2 p_u gamma_b on the speed entries
   if constexpr (SCAN) {
     // Phi' lin by the suffix-sum form (phi_tmul below, written out here: lin itself must survive)
@@ -338,7 +349,7 @@
     const double* o = Abc + t * QP_ABC_LD;
     const double2 b0 = ld2(o + 2), b1 = ld2(o + 4), b2 = ld2(o + 6);
     if (on) {
-      const double g0 = b0.x * l0 + b1.x * l1 + b2.x * l2 - 2.0 * pu * (double)__fmul_rn(P.p_u, rus[t]);
+      const double g0 = b0.x * l0 + b1.x * l1 + b2.x * l2 - 2.0 * pu * (double)__fmul_rn(p_u, rus[t]);
       const double g1 = b0.y * l0 + b1.y * l1 + b2.y * l2;
       gmax = fmax(gmax, fmax(fabs(g0), fabs(g1)));
     }
@@ -349,14 +360,14 @@
       const double* Pt = Phi + (size_t)t * 3 * ldp;
       acc += Pt[a] * lin[t * 3] + Pt[ldp + a] * lin[t * 3 + 1] + Pt[2 * ldp + a] * lin[t * 3 + 2];
     }
-    if (!(a & 1)) acc += -2.0 * pu * (double)__fmul_rn(P.p_u, rus[a >> 1]);
+    if (!(a & 1)) acc += -2.0 * pu * (double)__fmul_rn(p_u, rus[a >> 1]);
     gmax = fmax(gmax, fabs(acc));
   }
   // (the merit divides the residuals by these scales: reciprocals once, no fp64 division inside the loop)
   const double iscale_d = uni64(1.0 / (1.0 + wave_reduce<OpMax>(gmax))), iscale_p = uni64(1.0 / (1.0 + wave_reduce<OpMax>(cmax)));
   const double m_tot = fmax(wave_reduce<OpSum>(m_act) + (double)mf + (obs ? 2.0 * T : 0.0), 1.0);
   const double inv_m = uni64(1.0 / m_tot);
-  const double pub = (von && !(va & 1)) ? -2.0 * pu * (double)__fmul_rn(P.p_u, rus[va >> 1]) : 0.0;
+  const double pub = (von && !(va & 1)) ? -2.0 * pu * (double)__fmul_rn(p_u, rus[va >> 1]) : 0.0;
   LSYNC();
   if constexpr (SCAN) {
     hdiag = (lane < NU && !(lane & 1)) ? 2.0 * pu * pu : 0.0;
@@ -673,7 +684,7 @@
       double kap = sg, r1d = 0;
       if (obs) {
         kap += ld_[2 * t] * iwd[2 * t] + ld_[2 * t + 1] * iwd[2 * t + 1];
-        r1d = -(double)P.eta + ld_[2 * t] - ld_[2 * t + 1] + zs;       // g_d + C'lam - F'lam
+        r1d = -(double)eta + ld_[2 * t] - ld_[2 * t + 1] + zs;       // g_d + C'lam - F'lam
       }
       double ik = obs ? fast_rcp(kap) : 0.0;
       if constexpr (ASET) {
@@ -681,7 +692,7 @@
           // d of this step: frozen where it sits on a bound it is pushed against (its row then carries eta - zs as a multiplier),
           // frozen as well when no hinge row is on (nothing to eliminate it through; eta pushes it up: consistent only on d_max),
           // else eliminated as always (no weight from its rows: kappa = ro |rows on|)
-          const double resd = (double)P.eta - zs, dcur = xd[t];
+          const double resd = (double)eta - zs, dcur = xd[t];
           aset_dtp = obs && dcur >= dmaxv && resd > 0.0; aset_dtm = obs && dcur <= dmin0 && resd < 0.0;
           aset_dfix = aset_dtp || aset_dtm || !(sg > 0.0);
           aset_resd = resd;
@@ -1247,7 +1258,7 @@
         }
         for (int q = lane; q < 3 * T; q += QP_THREADS) {
           int t = q / 3, k = q - 3 * t;
-          const float qsk = k == 0 ? P.q_s[0] : (k == 1 ? P.q_s[1] : P.q_s[2]);
+          const float qsk = k == 0 ? qs0 : (k == 1 ? qs1 : qs2);
           double refv = (double)__fmul_rn(qsk, rs[k * (T + 1) + t + 1]) / (qsk != 0.f ? (double)qsk : 1.0);
           lin[q] = (s3[q] + cv[q]) - refv;
           q3[q] = (double)gs[k * (T + 1) + t + 1];
@@ -1546,7 +1557,7 @@
           g0 += k == 0 ? v : 0.0; g1 += k == 1 ? v : 0.0; g2 += k == 2 ? v : 0.0;
         }
         for (int t = lane; t < T; t += QP_THREADS) {
-          double refu = (double)__fmul_rn(P.p_u, rus[t]) / (P.p_u != 0.f ? (double)P.p_u : 1.0);
+          double refu = (double)__fmul_rn(p_u, rus[t]) / (p_u != 0.f ? (double)p_u : 1.0);
           gp += dxu[2 * t] * (xu[2 * t] - refu);
           if (obs) {
             ge += dxd[t];
@@ -1570,13 +1581,13 @@
         gmx = wave_reduce<OpSum>(gmx); gmn = wave_reduce<OpSum>(gmn);
         if (lane == 0) {
           float* gt = bw.grad_theta + (size_t)b * 8;
-          gt[0] = (float)(-4.0 * (double)P.q_s[0] * g0);
-          gt[1] = (float)(-4.0 * (double)P.q_s[1] * g1);
-          gt[2] = (float)(-4.0 * m2 * (double)P.q_s[2] * g2);
+          gt[0] = (float)(-4.0 * (double)qs0 * g0);
+          gt[1] = (float)(-4.0 * (double)qs1 * g1);
+          gt[2] = (float)(-4.0 * m2 * (double)qs2 * g2);
           gt[3] = (float)(-4.0 * pu * gp);
           gt[4] = (float)ge;
           gt[5] = (float)gmx;
-          gt[6] = (P.d_min > 0.f) ? (float)(-gmn) : 0.f;
+          gt[6] = (d_min > 0.f) ? (float)(-gmn) : 0.f;
           gt[7] = (float)status;
         }
         break;

@@ -266,6 +266,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 __device__ __forceinline__ double uni64(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
+__device__ __forceinline__ float uni32(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 struct OpSum { __device__ static double f(double a, double b) { return a + b; } };
 struct OpMax { __device__ static double f(double a, double b) { return fmax(a, b); } };
 struct OpMin { __device__ static double f(double a, double b) { return fmin(a, b); } };
@@ -322,6 +323,8 @@ __device__ __forceinline__ void st2(double* p, double a, double b) { *reinterpre
 // columns) and the columns of Phi live in registers, one matrix row per lane, every loop over
 // the horizon is unrolled and all broadcasts are v_readlane (no LDS round trip on the serial
 // chain).  TT == 0: generic horizon, same algorithm with the matrices in LDS.
+// theta: null, or the per-scene adjust parameters [nscene total][8] (npa_set_adjust_batch; read in nrmp_qp_body.inc): BWD then
+// differentiates with respect to the row it read.
 // BWD: after convergence, one more solve with the Newton matrix of the final iterate and the upstream
 // gradient as right-hand side gives dL/d(q_s, p_u, eta, d_max, d_min) (oracle/nrmp_backward.py states
 // the derivation; reference: the adjust parameters are differentiable through cvxpylayers,
@@ -379,7 +382,7 @@ void nrmp_qp_kernel(
     float* __restrict__ out_u, float* __restrict__ out_d, float* __restrict__ out_min_distance,
     int* __restrict__ out_iters, float* __restrict__ out_nrmp_points, int* __restrict__ flags,
     float* __restrict__ state, double* __restrict__ qp_info, double* __restrict__ warm, int scene0, int nscene,
-    QpBackward bw, float* __restrict__ trig_out) {
+    QpBackward bw, float* __restrict__ trig_out, const float* __restrict__ theta) {
   extern __shared__ __attribute__((aligned(16))) double sm_all[];
   // one scene (one wave) per workgroup: the dispatcher spreads the waves of a launch evenly over the CUs, and -- the
   // reason it is fixed here and not a launch parameter -- the scene's LDS block starts at LDS address 0, so every array
@@ -414,6 +417,7 @@ void nrmp_qp_group_kernel(DevParams P, QpGroup G, int nscene) {
   float* __restrict__ out_min_distance = q.out_min_distance; int* __restrict__ out_iters = q.out_iters;
   float* __restrict__ out_nrmp_points = q.out_nrmp_points; int* __restrict__ flags = q.flags; float* __restrict__ state = q.state;
   double* __restrict__ qp_info = q.qp_info; double* __restrict__ warm = q.warm; float* __restrict__ trig_out = q.trig_out;
+  const float* __restrict__ theta = q.theta;          // this call's parameter block (null: the uniform set of P), row b = its scene b
   const QpBackward bw{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 #include "nrmp_qp_body.inc"
 }

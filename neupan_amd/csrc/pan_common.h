@@ -68,6 +68,7 @@ struct QpCall {
   const float* lam_sorted; const float* pts_sorted; const float* dist_sorted; const int* count; float* cur_s_out;
   float* cur_u_out; float* cur_d_out; float* out_s; float* out_u; float* out_d; float* out_min_distance; int* out_iters;
   float* out_nrmp_points; int* flags; float* state; double* qp_info; double* warm; float* trig_out;
+  const float* theta;         // [batch][8] per-scene adjust parameters of THIS call (npa_set_adjust_batch), or null: P's uniform set
 };
 struct QpGroup { QpCall c[NPA_GROUP_MAX]; };
 struct StageCall {

@@ -71,6 +71,14 @@ class FleetPlanner:
         self.cur_vel = None                          # zeros on the first cycle (neupan.py:73)
         self.arrived = np.zeros(self.B, dtype=bool)
 
+    def set_adjust(self, theta):
+        """Per-robot adjust parameters: `theta` (B, 7) or (B, 8) float32 on the device, row b = q_s[0..2], p_u, eta, d_max, d_min
+        of robot b (a robot in a corridor and one in open space want different d_max and eta) -- PAN.set_scene_adjust; None
+        returns every robot to the planner's shared parameters.  B must be the number of paths given to set_paths."""
+        if theta is not None and self.B and theta.shape[0] != self.B:
+            raise ValueError(f"FleetPlanner.set_adjust: {theta.shape[0]} parameter rows for {self.B} robots")
+        self.pan.set_scene_adjust(theta)
+
     def _upload(self, point_index=None):
         self.nb.set_curves([cl[i] for cl, i in zip(self.curve_lists, self.curve_index)], self.intervals, point_index)
 

@@ -187,6 +187,7 @@ class PAN(torch.nn.Module):
             self._h = C.c_void_p()
             self._B = 0
             self._ws = self._state = self._last = None
+            self._theta = None
             self.printed = False
             return
         if not self.no_obs:
@@ -221,6 +222,7 @@ class PAN(torch.nn.Module):
         self._B = 0
         self._ws = self._state = None
         self._last = None
+        self._theta = None                           # per-scene adjust parameters in force (set_scene_adjust), or None
         self.printed = False
 
     # ------------------------------------------------------------------ plumbing
@@ -236,6 +238,43 @@ class PAN(torch.nn.Module):
         q = (C.c_float * 3)(*self.nrmp_layer.q_s3())
         check(self._lib.npa_set_adjust(self._h, C.byref(q), self._cfg.p_u, self._cfg.eta, self._cfg.d_max,
                                        self._cfg.d_min), "npa_set_adjust")
+
+    def set_scene_adjust(self, theta):
+        """Give every scene of a batch its own adjust parameters (npa_set_adjust_batch): `theta` is a float32 tensor on the
+        planner's device, (B, 8) -- columns q_s[0..2], p_u, eta, d_max, d_min, reserved, the columns of nrmp_backward's
+        `grad` -- or (B, 7), which is copied into an owned (B, 8) block; None returns to the planner's uniform parameters
+        (nrmp_layer.update_adjust_parameters_value keeps updating those meanwhile).  A contiguous (B, 8) tensor is used in
+        place.  The block (`scene_adjust`) is read by the kernels at run time: writing rows into it in place changes what the
+        next forward, the next step() of a prepared step and the next replay of a captured graph use -- nothing has to be made
+        again.  While it is set, every forward / nrmp_stage / nrmp_backward must plan exactly B scenes."""
+        if not torch.cuda.is_available():
+            raise NeupanAmdError("PAN.set_scene_adjust needs a ROCm GPU: the parameter block lives in device memory and is "
+                                 "read by the HIP kernels; there is no CPU fallback")
+        if getattr(self, "_untrained", False) or not self._h.value:
+            raise NeupanAmdError("PAN.set_scene_adjust: this planner has no kernel handle")
+        if theta is None:
+            check(self._lib.npa_set_adjust_batch(self._h, None, 0), "npa_set_adjust_batch")
+            self._theta = None
+            return
+        dev = self.device
+        if not isinstance(theta, torch.Tensor) or theta.dtype != torch.float32 or theta.dim() != 2 or \
+                theta.shape[0] < 1 or theta.shape[1] not in (7, 8):
+            raise ValueError("set_scene_adjust: theta must be a float32 tensor of shape (B, 7) or (B, 8), or None")
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        if theta.device.type != "cuda" or theta.device.index != idx:
+            raise ValueError(f"set_scene_adjust: theta must live on the planner's device ({dev}), got {theta.device}")
+        if theta.shape[1] == 8 and theta.is_contiguous():
+            block = theta.detach()
+        else:
+            block = torch.zeros((theta.shape[0], 8), dtype=torch.float32, device=theta.device)
+            block[:, :theta.shape[1]] = theta.detach()
+        check(self._lib.npa_set_adjust_batch(self._h, _ptr(block), block.shape[0]), "npa_set_adjust_batch")
+        self._theta = block                          # (held: the kernels read it until it is replaced)
+
+    @property
+    def scene_adjust(self):
+        """The (B, 8) parameter block in force (set_scene_adjust), or None: write into it in place to change parameters."""
+        return self._theta
 
     def __del__(self):
         try:
@@ -430,12 +469,18 @@ class PAN(torch.nn.Module):
                             out["min_distance"], out["iters"], out["nrmp_points"], ws, state) if t is not None]
         held_ptrs = tuple(t.data_ptr() for t in held)
         calls = [0]
+        # the per-scene parameter block: a plain step's library call reads the handle's pointer afresh; a captured graph holds
+        # the ADDRESS it saw (its contents are read at every replay: in-place updates need nothing, another block a new capture)
+        blk = self._theta
 
         def validate():
             if tuple(t.data_ptr() for t in held) != held_ptrs or \
                     any(t.data_ptr() != p0 or tuple(t.shape) != sh for t, p0, sh in watched):
                 raise NeupanAmdError("PAN.make_step: a tensor captured at prepare time has moved or changed shape (resize_ / "
                                      "set_ / a new workspace): step() would plan stale memory -- make the step again")
+            if graph and self._theta is not blk:
+                raise NeupanAmdError("PAN.make_step(graph=True): set_scene_adjust installed another block after the capture; the "
+                                     "graph reads the one it captured -- update rows in place, or make the step again")
             calls[0] += 1
             if (calls[0] & 63) == 0:
                 self.check_audit()
@@ -662,7 +707,7 @@ class PAN(torch.nn.Module):
                   "npa_nrmp_backward")
         return dict(opt_s=out_s, opt_u=out_u, opt_d=out_d, grad=gth, grad_nom_s=gns)
 
-    def forward_batch_grad(self, nom_s, nom_u, ref_s, ref_us, points=None, velocities=None, n_points=None):
+    def forward_batch_grad(self, nom_s, nom_u, ref_s, ref_us, points=None, velocities=None, n_points=None, adjust=None):
         """`forward_batch` whose outputs are connected to `nrmp_layer.adjust_parameters` for autograd, as the
         reference's are through cvxpylayers (nrmp.py:79-95, :144; example/LON/LON_corridor.py:94-127):
         `loss(opt_s, opt_u, opt_d).backward()` fills `.grad` of q_s, p_u, eta, d_max, d_min (make them
@@ -671,7 +716,14 @@ class PAN(torch.nn.Module):
         differentiation of its KKT system, npa_nrmp_backward) and hands dL/d(its proximal centre) to the solve of
         the iteration before -- the one recurrent path the reference keeps (A/B/C, mu, lam are detached there:
         robot.py:272-316, dune.py:81, pan.py:207).  `recurrent=False` on the planner keeps only the last solve.
+        `adjust`: a (B, 7) float32 device tensor of PER-SCENE parameters (columns q_s[0..2], p_u, eta, d_max, d_min; a (B, 8)
+        tensor with the reserved column is taken too), usually a `requires_grad` leaf: scene b is planned with row b
+        (set_scene_adjust for the duration of the call; the block in force before is restored), the outputs are connected to
+        it, and backward fills `adjust.grad` with one row per scene ON THE DEVICE -- not summed over the batch, no copy to the
+        host: a population of candidate parameter sets, or one tuner per environment, in one launch chain.
         Returns (opt_s (B,3,T+1), opt_u (B,2,T), opt_d (B,1,T)|None)."""
+        if adjust is not None:
+            return _PanGradScene.apply(self, (nom_s, nom_u, ref_s, ref_us, points, velocities, n_points), adjust)
         f = self.nrmp_layer
         params = [f.q_s, f.p_u, f.eta, f.d_max, f.d_min]
         return _PanGrad.apply(self, (nom_s, nom_u, ref_s, ref_us, points, velocities, n_points), *params)
@@ -756,67 +808,115 @@ class PAN(torch.nn.Module):
         return dict(dune_ms=a.value, select_ms=s_.value, nrmp_ms=b.value, launches=n.value, aset_ms=am.value, aset_launches=an.value)
 
 
+def _grad_forward(ctx, pan, args):
+    """The PAN loop of a differentiable forward: runs it and records, on ctx, what the backward pass re-solves from."""
+    nom_s, nom_u, ref_s, ref_us, points, velocities, n_points = args
+    pan.forward_begin(nom_s, nom_u, ref_s, ref_us, points, velocities, n_points)
+    B, T = pan._B, pan.T
+    # nominal trajectory each solve linearises around (cur_s, cur_u at the head of the workspace)
+    wsf = pan._ws.view(torch.float32)
+    n_s = B * 3 * (T + 1)
+    off_u = (n_s + 3) // 4 * 4
+    first = 0 if getattr(pan, "recurrent", True) else pan.iter_num - 1
+    snaps = []
+    use_rows = (not pan.no_obs) and points is not None
+    vw = pan._workspace_views() if use_rows else None
+    for k in range(pan.iter_num):
+        if k >= first:
+            snaps.append([k, wsf[:n_s].clone().reshape(B, 3, T + 1), wsf[off_u:off_u + B * 2 * T].clone().reshape(B, 2, T), None])
+        pan.forward_iter(k)
+        if k >= first and use_rows:
+            # the sorted rows THIS iteration's QP was built from: the backward pass re-solves it from them instead of
+            # re-running the DUNE stage (slice 0 is only refreshed in iteration 0 and stays valid: the QP never reads it)
+            snaps[-1][3] = {key: vw[key].clone() for key in ("mu", "lam", "pts", "count")}
+    out = pan.forward_end()
+    ctx.pan = pan
+    ctx.snaps = snaps
+    ctx.iters = out["iters"].clone()
+    ctx.args = (pan._dev(ref_s), pan._dev(ref_us), points, velocities, n_points)
+    ctx.no_obs = out["opt_d"] is None
+    d = out["opt_d"] if out["opt_d"] is not None else torch.zeros((B, 1, T), device=pan.device)
+    return out["opt_s"], out["opt_u"], d
+
+
+def _grad_backward_rows(ctx, gs, gu, gd):
+    """npa_nrmp_backward on re-runs of the executed iterations, last to first, chained through the proximal centre:
+    (B, 7) float64 on the device, row b = dL/d(the parameters scene b was solved with)."""
+    pan = ctx.pan
+    ref_s, ref_us, points, velocities, n_points = ctx.args
+    B, T, dev = ctx.iters.shape[0], pan.T, pan.device
+    gs = torch.zeros((B, 3, T + 1), device=dev) if gs is None else gs.contiguous()
+    gu = torch.zeros((B, 2, T), device=dev) if gu is None else gu.contiguous()
+    gd = None if (gd is None or ctx.no_obs) else gd.contiguous()
+    tot = torch.zeros((B, 7), dtype=torch.float64, device=dev)
+    for k, snap_s, snap_u, stage in reversed(ctx.snaps):
+        ran = ctx.iters > k                        # scenes whose stop test ended the loop earlier skip this solve
+        if not bool(ran.any()):
+            continue
+        r = pan.nrmp_backward(snap_s, snap_u, ref_s, ref_us, stage, gs, gu, gd)
+        tot += torch.where(ran[:, None], r["grad"][:, :7].double(), torch.zeros_like(tot))
+        m = ran[:, None, None]
+        gs = torch.where(m, r["grad_nom_s"], gs)
+        gu = torch.where(m, torch.zeros_like(gu), gu)
+        if gd is not None:
+            gd = torch.where(m, torch.zeros_like(gd), gd)
+        if not bool((gs != 0).any()):
+            break
+    return tot
+
+
 class _PanGrad(torch.autograd.Function):
     """PAN loop forward on the HIP path; backward = npa_nrmp_backward on re-runs of the executed iterations, last
-    to first, chained through the proximal centre."""
+    to first, chained through the proximal centre.  The gradient rows are summed over the batch into the five leaves."""
 
     @staticmethod
     def forward(ctx, pan, args, q_s, p_u, eta, d_max, d_min):
-        nom_s, nom_u, ref_s, ref_us, points, velocities, n_points = args
         pan._push_adjust()
-        pan.forward_begin(nom_s, nom_u, ref_s, ref_us, points, velocities, n_points)
-        B, T = pan._B, pan.T
-        # nominal trajectory each solve linearises around (cur_s, cur_u at the head of the workspace)
-        wsf = pan._ws.view(torch.float32)
-        n_s = B * 3 * (T + 1)
-        off_u = (n_s + 3) // 4 * 4
-        first = 0 if getattr(pan, "recurrent", True) else pan.iter_num - 1
-        snaps = []
-        use_rows = (not pan.no_obs) and points is not None
-        vw = pan._workspace_views() if use_rows else None
-        for k in range(pan.iter_num):
-            if k >= first:
-                snaps.append([k, wsf[:n_s].clone().reshape(B, 3, T + 1), wsf[off_u:off_u + B * 2 * T].clone().reshape(B, 2, T), None])
-            pan.forward_iter(k)
-            if k >= first and use_rows:
-                # the sorted rows THIS iteration's QP was built from: the backward pass re-solves it from them instead of
-                # re-running the DUNE stage (slice 0 is only refreshed in iteration 0 and stays valid: the QP never reads it)
-                snaps[-1][3] = {key: vw[key].clone() for key in ("mu", "lam", "pts", "count")}
-        out = pan.forward_end()
-        ctx.pan = pan
-        ctx.snaps = snaps
-        ctx.iters = out["iters"].clone()
-        ctx.args = (pan._dev(ref_s), pan._dev(ref_us), points, velocities, n_points)
         ctx.qs_shape = tuple(q_s.shape)
-        ctx.no_obs = out["opt_d"] is None
-        d = out["opt_d"] if out["opt_d"] is not None else torch.zeros((B, 1, T), device=pan.device)
-        return out["opt_s"], out["opt_u"], d
+        return _grad_forward(ctx, pan, args)
+
+    @staticmethod
+    def backward(ctx, gs, gu, gd):
+        g = _grad_backward_rows(ctx, gs, gu, gd).sum(dim=0).float().cpu()
+        gq = g[0:3].reshape(3, 1) if len(ctx.qs_shape) == 2 else g[0:3].sum().reshape(ctx.qs_shape)
+        return None, None, gq, g[3].reshape(()), g[4].reshape(()), g[5].reshape(()), g[6].reshape(())
+
+
+class _PanGradScene(torch.autograd.Function):
+    """_PanGrad with per-scene parameters (PAN.forward_batch_grad(adjust=theta)): scene b is solved with row b of theta and
+    the gradient keeps its rows -- theta.grad[b] = dL/d theta[b], on the device.  The block is installed for the forward and
+    again for the backward pass (the re-solves must read the rows the forward read); whatever set_scene_adjust had
+    installed before is put back."""
+
+    @staticmethod
+    def forward(ctx, pan, args, theta):
+        if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.shape[1] not in (7, 8) or theta.dtype != torch.float32:
+            raise ValueError("forward_batch_grad: adjust must be a float32 tensor of shape (B, 7) or (B, 8)")
+        prev = pan.scene_adjust
+        # (an owned copy: what backward re-solves with must not follow an optimiser step taken in between)
+        block = torch.zeros((theta.shape[0], 8), dtype=torch.float32, device=theta.device)
+        block[:, :theta.shape[1]] = theta.detach()
+        pan.set_scene_adjust(block)
+        try:
+            res = _grad_forward(ctx, pan, args)
+        finally:
+            pan.set_scene_adjust(prev)
+        ctx.block = block
+        ctx.ncol = theta.shape[1]
+        return res
 
     @staticmethod
     def backward(ctx, gs, gu, gd):
         pan = ctx.pan
-        ref_s, ref_us, points, velocities, n_points = ctx.args
-        B, T, dev = ctx.iters.shape[0], pan.T, pan.device
-        gs = torch.zeros((B, 3, T + 1), device=dev) if gs is None else gs.contiguous()
-        gu = torch.zeros((B, 2, T), device=dev) if gu is None else gu.contiguous()
-        gd = None if (gd is None or ctx.no_obs) else gd.contiguous()
-        tot = torch.zeros((B, 7), dtype=torch.float64, device=dev)
-        for k, snap_s, snap_u, stage in reversed(ctx.snaps):
-            ran = ctx.iters > k                        # scenes whose stop test ended the loop earlier skip this solve
-            if not bool(ran.any()):
-                continue
-            r = pan.nrmp_backward(snap_s, snap_u, ref_s, ref_us, stage, gs, gu, gd)
-            tot += torch.where(ran[:, None], r["grad"][:, :7].double(), torch.zeros_like(tot))
-            m = ran[:, None, None]
-            gs = torch.where(m, r["grad_nom_s"], gs)
-            gu = torch.where(m, torch.zeros_like(gu), gu)
-            if gd is not None:
-                gd = torch.where(m, torch.zeros_like(gd), gd)
-            if not bool((gs != 0).any()):
-                break
-        g = tot.sum(dim=0).float().cpu()
-        gq = g[0:3].reshape(3, 1) if len(ctx.qs_shape) == 2 else g[0:3].sum().reshape(ctx.qs_shape)
-        return None, None, gq, g[3].reshape(()), g[4].reshape(()), g[5].reshape(()), g[6].reshape(())
+        prev = pan.scene_adjust
+        pan.set_scene_adjust(ctx.block)
+        try:
+            rows = _grad_backward_rows(ctx, gs, gu, gd).float()
+        finally:
+            pan.set_scene_adjust(prev)
+        if ctx.ncol == 8:
+            rows = torch.cat([rows, torch.zeros_like(rows[:, :1])], dim=1)
+        return None, None, rows
 
 
 _STREAMS = {}
