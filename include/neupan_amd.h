@@ -384,6 +384,39 @@ int npa_scan_to_points(int batch, int beam_stride, const double *ranges, const d
                        int out_stride, float *points, float *velocities, int32_t *count,
                        void *stream);
 
+/* ---- the packed input record: host-fed serving loops (handle-free, stream-ordered) ------------------
+ *
+ * The reference's contract is neupan.forward(state, points): the obstacle cloud arrives from the HOST on every control
+ * cycle and is converted to tensors at neupan/neupan.py:123-127 (np_to_tensor; the nominal / reference tensors at :121).
+ * Here a cycle's inputs travel as ONE record: a contiguous block of 4-byte words the host builds in pinned memory and ships
+ * with one DMA, and npa_ingest_unpack turns its device copy into the tensors npa_forward_batch takes.  fp32 is the wire
+ * type because the reference casts to fp32 at exactly this boundary.
+ *
+ * Sections, in this order, each starting on a 256-byte boundary of the record:
+ *   [0] n_points  [B] int32        points of scene b (ragged clouds: 0 .. n_stride)
+ *   [1] cloud_off [B] int32        WORD offset of scene b's cloud inside the cloud section
+ *   [2] nom_s [B][3][T+1]  [3] nom_u [B][2][T]  [4] ref_s [B][3][T+1]  [5] ref_us [B][T]   fp32, npa_forward_batch's layouts
+ *   [6] the cloud section: scene b owns the words cloud_off[b] .. cloud_off[b] + c n_b - 1 (c = 2, or 4 with velocities):
+ *       x[n_b], y[n_b] (, vx[n_b], vy[n_b]).  Clouds sit back to back -- the exclusive prefix sums of c n_b -- with no
+ *       padding to the stride and no alignment beyond the word; only the words in use need to be uploaded.
+ * npa_ingest_layout: out[0..n), n <= 8 = the byte offsets of sections [0] .. [6] and, out[7], the worst-case bytes of a
+ *   record (every scene at n_stride points): the size of a record buffer.  NPA_E_ARG when the cloud section would exceed
+ *   2^31 words.
+ * npa_ingest_unpack (csrc/ingest.hip, one launch on `stream`): record = DEVICE copy of a record (4-byte aligned; 16-byte
+ *   accesses are taken where a cloud's source and destination both allow), record_bytes = the bytes of it that were
+ *   uploaded, a multiple of 4 with out[6] <= record_bytes <= out[7].  Writes nom_s, nom_u, ref_s, ref_us, n_points [B] and
+ *   columns [0, n_b) of points [B][2][n_stride] (and of velocities, same shape, when with_velocities != 0); columns beyond
+ *   n_b are NOT written (the selection kernel bounds its reads by n_points).
+ *   A malformed header never causes an out-of-range access: a scene with n_b < 0, n_b > n_stride, or a cloud that does not
+ *   lie inside [0, (record_bytes - out[6]) / 4) words gets n_points = 0 (it is planned without obstacle points), status[0]
+ *   is incremented and status[1] lowered to the scene's index (atomic add / min on a DEVICE int32 pair the caller
+ *   initialises to {0, INT32_MAX} and reads when it wants to); the other scenes are unaffected. */
+int npa_ingest_layout(int batch, int receding, int n_stride, int with_velocities, size_t *out, int n);
+int npa_ingest_unpack(int batch, int receding, int n_stride, int with_velocities,
+                      const void *record, size_t record_bytes,
+                      float *nom_s, float *nom_u, float *ref_s, float *ref_us,
+                      float *points, float *velocities, int32_t *n_points, int32_t *status, void *stream);
+
 /* ---- DUNE training labels (offline) ---------------------------------------------------------------
  * npa_dune_labels replaces DUNETrain.prob_solve / generate_data_set
  *   (neupan/blocks/dune_train.py:82-99, :109-140): for every point p the maximiser mu of

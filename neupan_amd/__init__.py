@@ -10,7 +10,8 @@ _LAZY = {"PAN": ("pan", "PAN"), "forward_interleaved": ("pan", "forward_interlea
          "FleetPlanner": ("fleet", "FleetPlanner"), "NominalBatch": ("frontend", "NominalBatch"),
          "scan_to_point_batch": ("frontend", "scan_to_point_batch"),
          "scan_to_point_velocity_batch": ("frontend", "scan_to_point_velocity_batch"),
-         "DuneTrain": ("dune_train", "DuneTrain"), "neupan": ("planner", "neupan")}      # (dune_labels.dune_labels: import it from its module)
+         "DuneTrain": ("dune_train", "DuneTrain"), "neupan": ("planner", "neupan"),
+         "InputPipeline": ("ingest", "InputPipeline")}      # (dune_labels.dune_labels: import it from its module)
 
 
 def __getattr__(name):

@@ -78,6 +78,11 @@ extern "C" hipError_t npa_launch_nominal(int batch, int T, int kin, double dt, d
 extern "C" hipError_t npa_launch_scan(int batch, int beam_stride, const double* ranges, const double* beam_vel,
                                       const int* n_beams, const npa_scan_params* params, int mode, int out_stride,
                                       float* points, float* velocities, int* count, hipStream_t stream);
+extern "C" int npa_ingest_offsets(int batch, int T, int n_stride, int with_vel, size_t* out, int n);
+extern "C" hipError_t npa_launch_ingest_unpack(int batch, int T, int n_stride, int with_vel, const void* record,
+                                               size_t record_bytes, float* nom_s, float* nom_u, float* ref_s, float* ref_us,
+                                               float* points, float* velocities, int* n_points, int* status,
+                                               hipStream_t stream);
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -1573,6 +1578,41 @@ extern "C" int npa_scan_to_points(int batch, int beam_stride, const double* rang
   if (mode != 0 && mode != 1) return fail(NPA_E_ARG, "npa_scan_to_points: mode must be 0 or 1");
   HIP_TRY(npa_launch_scan(batch, beam_stride, ranges, beam_vel, n_beams, params, mode, out_stride, points, velocities,
                           count, (hipStream_t)stream));
+  return NPA_OK;
+}
+
+// ---- the packed input record (csrc/ingest.hip) ----
+static int ingest_args_ok(int batch, int receding, int n_stride) {
+  return batch >= 1 && receding >= 1 && receding <= NPA_MAX_T && n_stride >= 1;
+}
+
+extern "C" int npa_ingest_layout(int batch, int receding, int n_stride, int with_velocities, size_t* out, int n) {
+  if (!ingest_args_ok(batch, receding, n_stride) || !out || n < 1 || n > 8)
+    return fail(NPA_E_ARG, "npa_ingest_layout: bad argument");
+  if (npa_ingest_offsets(batch, receding, n_stride, with_velocities != 0, out, n) != 0)
+    return fail(NPA_E_ARG, "npa_ingest_layout: the cloud section would not fit int32 word offsets");
+  return NPA_OK;
+}
+
+extern "C" int npa_ingest_unpack(int batch, int receding, int n_stride, int with_velocities, const void* record,
+                                 size_t record_bytes, float* nom_s, float* nom_u, float* ref_s, float* ref_us, float* points,
+                                 float* velocities, int32_t* n_points, int32_t* status, void* stream) {
+  if (!ingest_args_ok(batch, receding, n_stride) || !record || !nom_s || !nom_u || !ref_s || !ref_us || !points ||
+      !n_points || !status || (with_velocities && !velocities))
+    return fail(NPA_E_ARG, "npa_ingest_unpack: bad argument");
+  const void* ptrs[] = {record, nom_s, nom_u, ref_s, ref_us, points, velocities, n_points, status};
+  for (const void* p : ptrs)
+    if (((uintptr_t)p & 3) != 0) return fail(NPA_E_ARG, "npa_ingest_unpack: pointers must be 4-byte aligned");
+  size_t off[8];
+  if (npa_ingest_offsets(batch, receding, n_stride, with_velocities != 0, off, 8) != 0)
+    return fail(NPA_E_ARG, "npa_ingest_unpack: the cloud section would not fit int32 word offsets");
+  // the header and the dense sections must be inside what was uploaded; the cloud section may be cut short (ragged clouds)
+  if (record_bytes < off[6] || record_bytes > off[7] || (record_bytes & 3) != 0)
+    return fail(NPA_E_ARG, "npa_ingest_unpack: record_bytes must be a multiple of 4 between the cloud section's offset (" +
+                               std::to_string(off[6]) + ") and the layout's total (" + std::to_string(off[7]) + "), got " +
+                               std::to_string(record_bytes));
+  HIP_TRY(npa_launch_ingest_unpack(batch, receding, n_stride, with_velocities != 0, record, record_bytes, nom_s, nom_u, ref_s,
+                                   ref_us, points, velocities, n_points, status, (hipStream_t)stream));
   return NPA_OK;
 }
 
