@@ -903,6 +903,24 @@ def test_handles_of_one_checkpoint_share_pack_and_calibration():
     gc.collect()
     got = _stage_np(b, batch)
     assert np.array_equal(got["mu"], ref["mu"])
+    # the bf16 key tier's figures travel through the shared record as well: a handle that SHARES a pack calibrated under
+    # NPA_KEYS_PRECISION=bf16 reports what a handle with a private pack measured, and emits bitwise its rows
+    c0, h0, _ = _pack_stats()
+    t0 = time.perf_counter()
+    maker = _with_env({"NPA_KEYS_PRECISION": "bf16"}, lambda: make_gpu_pan(cfg))
+    t1 = time.perf_counter()
+    shared = _with_env({"NPA_KEYS_PRECISION": "bf16"}, lambda: make_gpu_pan(cfg))
+    t2 = time.perf_counter()
+    c1, h1, _ = _pack_stats()
+    assert c1 - c0 <= 1 and h1 - h0 >= 1, (c0, h0, c1, h1)
+    print(f"npa_create + checkpoint load, bf16 keys: first {1e3 * (t1 - t0):.1f} ms, sharing {1e3 * (t2 - t1):.1f} ms")
+    own = _with_env({"NPA_KEYS_PRECISION": "bf16", "NPA_PACK_CACHE": "0"}, lambda: make_gpu_pan(cfg))
+    assert shared.geo_report() == own.geo_report() == maker.geo_report() and shared.key_mode() == own.key_mode()
+    assert shared.geo_report()["bf16_key_error"] > 0 and shared.geo_report()["bf16_key_margin"] >= shared.geo_report()["bf16_key_error"]
+    r_shared, r_own = _stage_np(shared, batch), _stage_np(own, batch)
+    for k in ("mu", "lam", "pts", "dist", "count"):
+        assert np.array_equal(r_shared[k], r_own[k]), k
+        assert np.array_equal(r_shared[k], ref[k]), k             # (and the bf16 tier emits the exact rows)
 
 
 @pytest.mark.parametrize("cfgname,B", [("poly8_5k_T10_K10", 24), ("dyna_4k_T10_K10", 24), ("acker_2k_T20_K15", 24), ("diff_1k_T10_K10", 48)])
