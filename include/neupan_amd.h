@@ -417,6 +417,32 @@ int npa_ingest_unpack(int batch, int receding, int n_stride, int with_velocities
                       float *nom_s, float *nom_u, float *ref_s, float *ref_us,
                       float *points, float *velocities, int32_t *n_points, int32_t *status, void *stream);
 
+/* ---- exact clearance of a plan against the full cloud (stream-ordered, one launch) --------------------
+ *
+ * The reference's safety signal is min_distance: the NETWORK's distance at horizon step 0 over the cloud after decimation
+ * to dune_max_num points (dune.py:98; the decimation and the point flow: pan.py:171-212), compared with
+ * collision_threshold by check_stop (neupan.py:169-170); info["collision"] is declared (neupan.py:86) and never set.
+ * npa_plan_clearance (csrc/clearance.hip) is the independent check: the closed-form distance of the robot polygon to EVERY
+ * point of the cloud at every step of a trajectory.  For scene b, step t = 0..T, point n < n_points[b]:
+ *     q = p_n + t dt v_n (pan.py:182),  p0 = R(theta_t)^T (q - s_t[0:2]) (pan.py:205-210),
+ *     d = the distance of p0 to the polygon: outside, the smallest point-segment distance over the edges; inside, the largest
+ *         signed distance to an edge line (<= 0: minus the penetration depth).
+ * traj_s [B][3][T+1] (T = the handle's receding: opt_s, or any other trajectory of that shape); points, velocities
+ * [B][2][n_stride] and n_points [B] as npa_forward_batch takes them (velocities null: static points; n_points null: every scene
+ * has n_stride points; n_points[b] is clamped to [0, n_stride]).  ALL n_points[b] points count -- dune_max_num does not
+ * apply -- and columns at or beyond n_points[b] are never read.
+ * Outputs: clearance [B][T+1] = min_n d (+inf for a scene without points), nearest [B][T+1] = the smallest n that attains it
+ * (-1 without points); min_clearance [B] = min_t clearance, first_violation [B] = the smallest t with clearance < threshold,
+ * -1 if there is none (either of the two may be null).  fp32 arithmetic; deterministic (no atomics: the result does not
+ * depend on the order of the reduction).  No workspace, no allocation, no host synchronisation.
+ * NPA_E_ARG: a null handle or required pointer, batch <= 0, n_stride <= 0, a pointer that is not 4-byte aligned (16-byte
+ *   loads are taken where a scene's rows allow them) -- checked before anything touches a device.
+ * NPA_E_UNSUPPORTED: the handle's G, h rows are not consecutive counter-clockwise edges (no vertices: npa_geo_report). */
+int npa_plan_clearance(npa_handle *h, int batch, int n_stride, const float *traj_s, const float *points,
+                       const float *velocities, const int32_t *n_points, float threshold,
+                       float *clearance, int32_t *nearest, float *min_clearance, int32_t *first_violation,
+                       void *stream);
+
 /* ---- DUNE training labels (offline) ---------------------------------------------------------------
  * npa_dune_labels replaces DUNETrain.prob_solve / generate_data_set
  *   (neupan/blocks/dune_train.py:82-99, :109-140): for every point p the maximiser mu of

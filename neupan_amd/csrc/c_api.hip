@@ -68,7 +68,7 @@ extern "C" hipError_t npa_launch_ingest_unpack(int batch, int T, int n_stride, i
                                                hipStream_t stream);
 
 extern "C" const char* npa_last_error(void) { return g_err.c_str(); }
-extern "C" const char* npa_version(void) { return "neupan_amd 0.4 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
+extern "C" const char* npa_version(void) { return "neupan_amd 0.5 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
 // per-slice stride of the key buffer inside the workspace: none with geometric keys (select_kernel keeps them in LDS)
 static int kstride(const npa_handle* h) { return h->key_terms == 4 ? 0 : h->P.key_stride; }
 
@@ -706,6 +706,27 @@ extern "C" int npa_ingest_unpack(int batch, int receding, int n_stride, int with
                                std::to_string(record_bytes));
   HIP_TRY(npa_launch_ingest_unpack(batch, receding, n_stride, with_velocities != 0, record, record_bytes, nom_s, nom_u, ref_s,
                                    ref_us, points, velocities, n_points, status, (hipStream_t)stream));
+  return NPA_OK;
+}
+
+// ---- exact clearance of a plan against the full cloud (csrc/clearance.hip) ----
+extern "C" hipError_t npa_launch_clearance(const DevParams& P, int batch, int n_stride, const float* traj, const float* points,
+                                           const float* velocities, const int* n_points, float threshold, float* clearance,
+                                           int* nearest, float* min_clearance, int* first_violation, hipStream_t stream);
+extern "C" int npa_plan_clearance(npa_handle* h, int batch, int n_stride, const float* traj_s, const float* points,
+                                  const float* velocities, const int32_t* n_points, float threshold, float* clearance,
+                                  int32_t* nearest, float* min_clearance, int32_t* first_violation, void* stream) {
+  // (everything that can be refused without the handle's content is refused first: no device call, no read of *h)
+  if (!h || batch <= 0 || n_stride <= 0 || !traj_s || !points || !clearance || !nearest)
+    return fail(NPA_E_ARG, "npa_plan_clearance: bad argument");
+  const void* ptrs[] = {traj_s, points, velocities, n_points, clearance, nearest, min_clearance, first_violation};
+  for (const void* p : ptrs)
+    if (((uintptr_t)p & 3) != 0) return fail(NPA_E_ARG, "npa_plan_clearance: pointers must be 4-byte aligned");
+  if (!h->geo_valid)
+    return fail(NPA_E_UNSUPPORTED, "npa_plan_clearance: the robot polygon's rows are not consecutive counter-clockwise edges "
+                                   "(no vertices could be derived from G, h)");
+  HIP_TRY(npa_launch_clearance(h->P, batch, n_stride, traj_s, points, velocities, n_points, threshold, clearance, nearest,
+                               min_clearance, first_violation, (hipStream_t)stream));
   return NPA_OK;
 }
 

@@ -7,6 +7,7 @@
     warm start          cur_vel_array <- opt_u (not shifted)        neupan.py:137
     stop test           min_distance < collision_threshold          neupan.py:150-154, :169
     action              opt_u[:, 0] (omni: v cos, v sin)            neupan.py:156-164
+    certify (optional)  exact clearance of opt_s, the whole cloud   (info["collision"], neupan.py:86) -> npa_plan_clearance
 
 Path generation (gctl curves) stays with the caller: `set_paths` takes each robot's initial path as the
 reference's `set_initial_path` does (list of (4,1) points x, y, theta, gear) and splits it by gear like
@@ -83,9 +84,14 @@ class FleetPlanner:
         self.nb.set_curves([cl[i] for cl, i in zip(self.curve_lists, self.curve_index)], self.intervals, point_index)
 
     # ------------------------------------------------------------------ one control cycle
-    def forward(self, states, points=None, velocities=None, n_points=None):
+    def forward(self, states, points=None, velocities=None, n_points=None, certify=False):
         """states [B,3]; points [B,2,N] float32 (global frame) with optional n_points [B] / velocities [B,2,N].
-        Returns (action [B,2] float32 device tensor, info dict)."""
+        Returns (action [B,2] float32 device tensor, info dict).
+        certify=True (with points): one more launch behind the plan measures opt_s against the cycle's WHOLE cloud, velocities
+        included (PAN.plan_clearance, threshold = collision_threshold), and adds info["clearance"] (B,T+1), info["nearest"]
+        (B,T+1), info["unsafe_step"] (B,): the first step closer than the threshold, -1 if none, and info["collision"] (B,):
+        clearance[:, 0] <= 0, the polygon at the robot's current pose touches or contains a point (the reference declares the
+        key, neupan.py:86, and never sets it).  Neither the action nor `stop` depends on it."""
         B, dev = self.B, self.device
         st = np.asarray(states.cpu() if isinstance(states, torch.Tensor) else states, dtype=np.float64).reshape(B, -1)[:, :3]
         # 1. progress along the path, arrival (host bookkeeping only when a curve ends)
@@ -130,6 +136,10 @@ class FleetPlanner:
         act = torch.where((done | stop)[:, None], torch.zeros_like(act), act)
         info = dict(arrive=done, stop=stop & ~done, opt_u=opt_u, opt_s=out["opt_s"], opt_d=out["opt_d"], min_distance=md,
                     ref_s=ref_s, ref_us=ref_us, point_index=pidx)
+        if certify and points is not None:
+            clr = self.pan.plan_clearance(out["opt_s"].detach(), points, velocities, n_points, threshold=self.collision_threshold)
+            info.update(clearance=clr["clearance"], nearest=clr["nearest"], unsafe_step=clr["first_violation"],
+                        collision=clr["clearance"][:, 0] <= 0)
         return act, info
 
     def scan_to_point(self, states, ranges, angle_min, angle_max, range_min, range_max, **kw):

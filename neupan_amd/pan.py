@@ -615,6 +615,60 @@ class PAN(torch.nn.Module):
         k = min(n, self.dune_max_num, self.nrmp_max_num)
         return self._last["nrmp_points"][0, :, :k].cpu().numpy()
 
+    # ------------------------------------------------------------------ exact clearance of a plan (npa_plan_clearance)
+    def plan_clearance(self, traj_s, points, velocities=None, n_points=None, threshold=0.0, out=None):
+        """The exact signed distance of the robot polygon to the WHOLE cloud at every step of a trajectory: one launch on the
+        current stream, no synchronisation.  traj_s (B,3,T+1): opt_s of a forward call, or ref_s / nom_s; points (B,2,N),
+        velocities (B,2,N)|None, n_points (B,) int32|None as forward_batch takes them -- but every one of the n_points[b]
+        points counts (dune_max_num does not apply).  Returns dict(clearance (B,T+1) float32: +inf for a scene without
+        points, negative = penetration depth; nearest (B,T+1) int32: the lowest index that attains it, -1 without points;
+        min_clearance (B,) float32; first_violation (B,) int32: the first step with clearance < threshold, -1 if none),
+        device tensors valid in stream order.  `out`: a dict this method returned earlier for the same B -- its tensors are
+        written again instead of allocating (the serving-loop form)."""
+        if self.no_obs or getattr(self, "_untrained", False) or not self._h.value:
+            raise NeupanAmdError("PAN.plan_clearance: this planner has no obstacle stage (nrmp_max_num == 0, dune_max_num == 0 or "
+                                 "no checkpoint yet), so it holds no device handle with the robot polygon's geometry to measure "
+                                 "a cloud against")
+        T, dev = self.T, self.device
+        traj_s = self._dev(traj_s)
+        if traj_s.dim() != 3:
+            raise ValueError(f"traj_s must have shape (B,3,{T + 1}), got {tuple(traj_s.shape)}")
+        B = traj_s.shape[0]
+        traj_s = self._dev(traj_s, (B, 3, T + 1))
+        points = self._dev(points)
+        if points.dim() != 3 or points.shape[0] != B or points.shape[1] != 2:
+            raise ValueError(f"points must have shape (B,2,N), got {tuple(points.shape)}")
+        N = points.shape[2]
+        if velocities is not None:
+            velocities = self._dev(velocities, (B, 2, N))
+        if n_points is not None:
+            n_points = torch.as_tensor(n_points).to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(n_points.shape) != (B,):
+                raise ValueError(f"n_points must have shape ({B},), got {tuple(n_points.shape)}")
+        shapes = dict(clearance=((B, T + 1), torch.float32), nearest=((B, T + 1), torch.int32),
+                      min_clearance=((B,), torch.float32), first_violation=((B,), torch.int32))
+        if out is None:
+            out = {k: torch.empty(s, dtype=dt, device=dev) for k, (s, dt) in shapes.items()}
+        else:
+            for k, (s, dt) in shapes.items():
+                t = out.get(k)
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != s or t.dtype != dt or not t.is_contiguous() or \
+                        t.device != traj_s.device:
+                    raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {s} on the planner's device")
+        with torch.cuda.device(dev):
+            if B == 0 or N == 0:                     # nothing to measure against: what the kernel writes for an empty scene
+                out["clearance"].fill_(inf); out["min_clearance"].fill_(inf)
+                out["nearest"].fill_(-1); out["first_violation"].fill_(-1)
+                return out
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            check(self._lib.npa_plan_clearance(self._h, B, N, _ptr(traj_s), _ptr(points), _ptr(velocities), _ptr(n_points),
+                                               float(threshold), _ptr(out["clearance"]), _ptr(out["nearest"]),
+                                               _ptr(out["min_clearance"]), _ptr(out["first_violation"]), C.c_void_p(stream)),
+                  "npa_plan_clearance")
+        # (the inputs may be temporaries of the conversions above: they are freed in stream order by the caching allocator of
+        # the stream the launch is on, which is the current one)
+        return out
+
     # ------------------------------------------------------------------ stage access (tests, profiling)
     def dune_stage(self, nom_s, points, velocities=None, n_points=None):
         T, M, E = self.T, self.nrmp_max_num, self.E
