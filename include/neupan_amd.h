@@ -443,6 +443,59 @@ int npa_plan_clearance(npa_handle *h, int batch, int n_stride, const float *traj
                        float *clearance, int32_t *nearest, float *min_clearance, int32_t *first_violation,
                        void *stream);
 
+/* ---- a lidar world on the device: ray-cast scans and the plant step of a closed loop (csrc/world.hip) -----------------
+ *
+ * The reference closes its loop through a simulator (example/run_exp.py: env.get_lidar_scan() -> scan_to_point ->
+ * neupan_planner(...) -> env.step(action)).  These two calls are that simulator's part for B robots, handle-free and
+ * stream-ordered: no workspace, no atomics, no host synchronisation.
+ *
+ * The world, float64 DEVICE arrays:
+ *   circles  [W][c_stride][6]  cx, cy, r, vx, vy, 0          segments [W][s_stride][6]  ax, ay, bx, by, vx, vy
+ *   n_circles [W], n_segments [W] int32 (clamped to their strides; entries at or beyond them are never read).
+ *   W = n_worlds is 1 (one world shared by every scene) or batch (scene b has world b).  Polygons and rectangles are their
+ *   edges.  Primitive indices: circles 0 .. C-1, segments C .. C+S-1 with C = n_circles[w].
+ *
+ * npa_world_scan (one launch): beam i < n_beams[b] of scene b starts at the sensor pose state o offset of params[b]
+ *   (composed as npa_scan_to_points composes them; used fields: state, offset, angle_min, angle_max, range_min, range_max --
+ *   angle_range and down_sample belong to npa_scan_to_points) at the angle numpy.linspace(angle_min, angle_max, n)[i], bit
+ *   for bit the value npa_scan_to_points uses.  ranges [B][beam_stride] = the smallest t >= 0 at which the ray meets a
+ *   primitive -- circle: the near root, 0 when the origin is inside; segment: the ray / segment intersection with the
+ *   segment parameter in [0, 1], parallel rays miss --, ties to the lowest primitive index.  A smallest t at or above
+ *   range_max, or no hit: ranges = range_max exactly, hit = -1, velocity 0.  Hits below range_min are reported as they are.
+ *   beam_vel [B][2][beam_stride] (nullable) = (vx, vy) of the primitive hit, hit [B][beam_stride] int32 (nullable) its index.
+ *   Columns at or beyond n_beams[b] (null: beam_stride) are not written.  skip [B][2] int32 (nullable): scene b's beams
+ *   ignore the SEGMENT indices skip[b][0] <= s < skip[b][1] (a robot's own edges, below).
+ *   Primitives are culled against the sensor's reach and cast in chunks of npa_world_list_capacity(); the result does not
+ *   depend on the chunking, and a scene's result does not depend on the batch it is in.
+ *
+ * npa_world_step (two launches; one when clearance is null):
+ *   1. plant: state [B][3] f64 is advanced in place by action [B][2] f32 over dt unless frozen[b] != 0 (frozen nullable).
+ *      diff and acker: motion_predict_model (initial_path.py:388-432) in the float32 / float64 mix of
+ *      npa_nominal_ref_states; omni: the action is (vx, vy) as neupan.forward returns it (neupan.py:158-164),
+ *      x += dt vx, y += dt vy in float64, heading unchanged.
+ *   2. world: every primitive with a non-zero velocity is translated by v dt, once per step.  bounds (HOST, xlo, ylo, xhi,
+ *      yhi; nullable): a circle whose centre has left the box gets the offending velocity component turned back inside.
+ *   3. peers (peer_base >= 0, n_worlds == 1): the edge_num edges of robot b's polygon (vertices: HOST [E][2] f64, robot
+ *      frame, counter-clockwise) at its new pose are written to segments[peer_base + b E + e], their velocity the robot's
+ *      displacement of this step / dt (0 when dt == 0).  With skip[b] = [peer_base + b E, peer_base + (b + 1) E) the robots
+ *      see each other in the next scan as moving obstacles.  The caller sizes n_segments to include this tail; the tail is
+ *      not translated by 2.
+ *   4. clearance [B] f64 (nullable): the exact signed distance of robot b's polygon at its new pose to the nearest primitive
+ *      of its world, its own edges excluded; +inf without primitives.  Circle: distance(centre, polygon) - r, the polygon
+ *      distance negative inside as in npa_plan_clearance.  Segment: 0 when it crosses an edge or has an end inside the
+ *      polygon, else the smaller of its ends' polygon distances and the vertices' point-segment distances.  <= 0: collided.
+ * NPA_E_ARG (before anything touches a device): a null required pointer, batch <= 0, n_worlds not in {1, batch}, dt < 0,
+ *   edge_num outside [3, NPA_MAX_E], peers or clearance without vertices, peers with n_worlds != 1 or a tail beyond s_stride. */
+int npa_world_list_capacity(void);
+int npa_world_scan(int batch, int n_worlds, int c_stride, int s_stride, const double *circles, const double *segments,
+                   const int32_t *n_circles, const int32_t *n_segments, const npa_scan_params *params,
+                   const int32_t *n_beams, int beam_stride, const int32_t *skip,
+                   double *ranges, double *beam_vel, int32_t *hit, void *stream);
+int npa_world_step(int batch, int n_worlds, int c_stride, int s_stride, double *circles, double *segments,
+                   const int32_t *n_circles, const int32_t *n_segments, double *state, const float *action,
+                   const int32_t *frozen, double dt, int kinematics, double wheelbase, const double *bounds,
+                   int edge_num, const double *vertices, int peer_base, double *clearance, void *stream);
+
 /* ---- DUNE training labels (offline) ---------------------------------------------------------------
  * npa_dune_labels replaces DUNETrain.prob_solve / generate_data_set
  *   (neupan/blocks/dune_train.py:82-99, :109-140): for every point p the maximiser mu of

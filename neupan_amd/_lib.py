@@ -79,6 +79,10 @@ SYMBOLS = {
     "npa_ingest_layout": (_I, [_I, _I, _I, _I, C.POINTER(C.c_size_t), _I]),
     "npa_ingest_unpack": (_I, [_I, _I, _I, _I, _P, _SZ] + [_P] * 8 + [_P]),
     "npa_plan_clearance": (_I, [_P, _I, _I, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
+    "npa_world_list_capacity": (_I, []),
+    "npa_world_scan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "npa_world_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_double, _I, C.c_double, C.POINTER(C.c_double), _I,
+                            C.POINTER(C.c_double), _I, _P, _P]),
     "npa_dune_labels": (_I, [_I, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "npa_profile_enable": (_I, [_P, _I]),
     "npa_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
