@@ -459,9 +459,11 @@ int npa_plan_clearance(npa_handle *h, int batch, int n_stride, const float *traj
  *   (composed as npa_scan_to_points composes them; used fields: state, offset, angle_min, angle_max, range_min, range_max --
  *   angle_range and down_sample belong to npa_scan_to_points) at the angle numpy.linspace(angle_min, angle_max, n)[i], bit
  *   for bit the value npa_scan_to_points uses.  ranges [B][beam_stride] = the smallest t >= 0 at which the ray meets a
- *   primitive -- circle: the near root, 0 when the origin is inside; segment: the ray / segment intersection with the
- *   segment parameter in [0, 1], parallel rays miss --, ties to the lowest primitive index.  A smallest t at or above
- *   range_max, or no hit: ranges = range_max exactly, hit = -1, velocity 0.  Hits below range_min are reported as they are.
+ *   primitive -- circle: the near root (a tangent ray hits), 0 when the origin is inside or on it, whichever way the ray
+ *   points; segment: the ray / segment intersection with the segment parameter in [0, 1], both ends included; parallel and
+ *   collinear rays and segments of zero length miss --, ties to the lowest primitive index.  The range is never -0.
+ *   A smallest t at or above range_max, or no hit: ranges = range_max exactly, hit = -1, velocity 0.  Hits below range_min
+ *   are reported as they are.
  *   beam_vel [B][2][beam_stride] (nullable) = (vx, vy) of the primitive hit, hit [B][beam_stride] int32 (nullable) its index.
  *   Columns at or beyond n_beams[b] (null: beam_stride) are not written.  skip [B][2] int32 (nullable): scene b's beams
  *   ignore the SEGMENT indices skip[b][0] <= s < skip[b][1] (a robot's own edges, below).
@@ -474,7 +476,8 @@ int npa_plan_clearance(npa_handle *h, int batch, int n_stride, const float *traj
  *      npa_nominal_ref_states; omni: the action is (vx, vy) as neupan.forward returns it (neupan.py:158-164),
  *      x += dt vx, y += dt vy in float64, heading unchanged.
  *   2. world: every primitive with a non-zero velocity is translated by v dt, once per step.  bounds (HOST, xlo, ylo, xhi,
- *      yhi; nullable): a circle whose centre has left the box gets the offending velocity component turned back inside.
+ *      yhi; nullable): a moving circle whose centre has left the box (a centre on a wall has not) gets the offending velocity
+ *      component turned back inside; segments and circles at rest are not turned.
  *   3. peers (peer_base >= 0, n_worlds == 1): the edge_num edges of robot b's polygon (vertices: HOST [E][2] f64, robot
  *      frame, counter-clockwise) at its new pose are written to segments[peer_base + b E + e], their velocity the robot's
  *      displacement of this step / dt (0 when dt == 0).  With skip[b] = [peer_base + b E, peer_base + (b + 1) E) the robots

@@ -183,9 +183,35 @@ class LidarWorld:
         st = st.to(device=self.device, dtype=torch.float64)
         return st.reshape(st.shape[0], -1)[:, :3].contiguous()
 
+    def _check_out(self, out, B, n_max):
+        """`out` = (ranges [B, R] f64, beam_vel [B, 2, R] f64, hit [B, R] int32), contiguous tensors on the world's device with
+        R >= n_max; returns R"""
+        if not isinstance(out, (tuple, list)) or len(out) != 3 or not all(isinstance(t, torch.Tensor) for t in out):
+            raise ValueError("out must be three tensors (ranges, beam_vel, hit)")
+        ranges, vel, hit = out
+        if ranges.dim() != 2 or ranges.shape[0] != B:
+            raise ValueError(f"out[0] (ranges) must be [{B}, R], not {list(ranges.shape)}")
+        R = int(ranges.shape[1])
+        if R < max(n_max, 1):
+            raise ValueError(f"out is {R} beams wide, the scan has {n_max}")
+        for t, shape, dtype, what in ((ranges, (B, R), torch.float64, "out[0] (ranges)"),
+                                      (vel, (B, 2, R), torch.float64, "out[1] (beam_vel)"),
+                                      (hit, (B, R), torch.int32, "out[2] (hit)")):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{what} must be {list(shape)}, not {list(t.shape)}")
+            if t.dtype != dtype:
+                raise ValueError(f"{what} must be {dtype}, not {t.dtype}")
+            if t.device.type != self.device.type or (self.device.index is not None and t.device.index != self.device.index):
+                raise ValueError(f"{what} is on {t.device}, the world on {self.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+        return R
+
     def scan(self, states, n_beams, angle_min, angle_max, range_min, range_max, scan_offset=(0.0, 0.0, 0.0), out=None):
         """Ray-cast the lidars of B robots.  states [B, 3] (host or device); n_beams an int, or [B] ints (ragged: columns at or
-        beyond n_beams[b] are not written; they keep what `out` = (ranges, beam_vel, hit) held, zeros without it).
+        beyond n_beams[b] are not written; they keep what `out` = (ranges, beam_vel, hit) held, zeros without it).  `out` may
+        be wider than the scan, also with an int n_beams: its width is the row stride; a mismatch in shape, dtype, device or
+        contiguity is a ValueError.
         Returns (ranges [B, R] f64, beam_vel [B, 2, R] f64, hit [B, R] int32) device tensors: the first two are what
         scan_to_point_batch / scan_to_point_velocity_batch take.  No host synchronisation."""
         lib, dev = _lib.load(), self.device
@@ -193,13 +219,15 @@ class LidarWorld:
         B = st.shape[0]
         if self.W not in (1, B):
             raise ValueError(f"{self.W} worlds for {B} robots")
-        nb = None
         if isinstance(n_beams, (int, np.integer)):
+            nb_h = None if out is None else np.full(B, int(n_beams), dtype=np.int32)
             R = int(n_beams)
         else:
             nb_h = np.asarray(n_beams, dtype=np.int32).reshape(B)
-            R = int(nb_h.max()) if out is None else int(out[0].shape[1])
-            nb = torch.from_numpy(nb_h).to(dev)
+            R = int(nb_h.max())
+        if out is not None:                    # the rows are as far apart as `out` is wide; the counts go in n_beams
+            R = self._check_out(out, B, R)
+        nb = None if nb_h is None else torch.from_numpy(nb_h).to(dev)
         par = torch.zeros((B, _PARAM_DOUBLES), dtype=torch.float64, device=dev)
         head = np.zeros((B, 4))
         for k, x in enumerate((angle_min, angle_max, range_min, range_max)):

@@ -205,3 +205,110 @@ def test_world_exports_refuse_bad_arguments_without_a_gpu(lib):
                 dict(V=(C.c_double * 8)(0, 0, 0, 0, 1, 1, -1, 1))):
         assert step(**bad) == -1, bad
         assert b"npa_world_step" in lib.npa_last_error()
+
+
+# ------------------------------------------------------------------- the tables of tests/test_world_edges_gpu.py (world_cases.py)
+def test_exact_ray_table_agrees_with_the_restatement_bitwise(lib):
+    """every literal of world_cases.exact_cases is what wr.scan gives, bit for bit, in each of the three ways the device runs
+    the table; and the restatement's exclusion rule marks the beams the table says it marks -- 19 of the 29, every tie, end,
+    tangent and range_max case: test_world_gpu.compare looks at none of those"""
+    import world_cases as wc
+    table = wc.exact_cases(lib.npa_world_list_capacity())
+    names = [k["name"] for k in table]
+    assert len(set(names)) == len(names) and all(k["promise"] for k in table)
+    for n, amin, amax, beam in wc.EXACT_WAYS.values():
+        _, d = wr.beam_directions((0.25, -1.5, 0.0), (0.0, 0.0, 0.0), n, amin, amax)
+        assert d[beam].tobytes() == np.array([1.0, 0.0]).tobytes()
+        for k in table:
+            r = wr.scan(k["circles"], k["segments"], (*k["origin"], 0.0), n, amin, amax, wc.RMAX_A)
+            got = (np.float64(r["ranges"][beam]).tobytes(), int(r["hit"][beam]), r["vel"][:, beam].tobytes())
+            want = (np.float64(k["range"]).tobytes(), k["hit"], np.array(k["vel"], dtype=np.float64).tobytes())
+            assert got == want, (k["name"], n, r["ranges"][beam], r["hit"][beam], r["vel"][:, beam])
+            assert bool(r["ill"][beam]) == k["ill"], (k["name"], n)
+    ill = {k["name"] for k in table if k["ill"]}
+    assert len(ill) == 19 and len(table) == 29 and {n for n in names if n.startswith(("tie_", "end_", "just_short", "wall_"))} <= ill
+    assert {"tangent", "near_root_at_range_max", "collinear_ahead", "parallel_beside", "origin_on_end_a"} <= ill
+
+
+def test_excluded_share_of_the_ragged_and_step_scans():
+    """the GPU tests of sections B and C may leave out the beams the restatement marks: at most 1 % of them, whatever the seeds"""
+    import world_cases as wc
+    marked = total = 0
+    for inp in wc.scan_inputs():
+        ref = wc.scan_reference(*inp)
+        marked, total = marked + int(ref["ill"].sum()), total + ref["ill"].size
+        print(inp[0], int(ref["ill"].sum()), "of", ref["ill"].size)
+    print("excluded", marked, "of", total)
+    assert total == 300 * (8 + 3 + 6) and marked <= 0.01 * total, (marked, total)
+
+
+def test_step_worlds_are_what_their_test_needs():
+    import world_cases as wc
+    V = wc.PENTAGON
+    D = np.roll(V, -1, axis=0) - V
+    assert (D[:, 0] * np.roll(D, -1, axis=0)[:, 1] - D[:, 1] * np.roll(D, -1, axis=0)[:, 0] > 0).all()       # convex, counter-clockwise
+    assert np.abs(V.mean(axis=0)).max() > 0.04
+    sts = wc.step_reference_states()
+    for variant in ("contact", "clear"):
+        S = wc.step_worlds(variant)
+        moving = [(S["circles"][w, :nc, 3:5] != 0).any(axis=1).sum() + (S["segments"][w, :ns, 4:6] != 0).any(axis=1).sum()
+                  for w, (nc, ns) in enumerate(S["counts"])]
+        assert 0.25 <= sum(moving) / S["counts"].sum() <= 0.45
+        hand = wc.STEP_HAND[variant]
+        for step, worlds in enumerate(wc.step_reference(S), start=1):
+            for w, (c, s) in enumerate(worlds):
+                dC, dS = wc.primitive_distances(c, s, V, sts[step][w])
+                d = {"c": dC, "s": dS}
+                kind, idx = hand[w]
+                rest = np.concatenate([np.delete(dC, idx) if kind == "c" else dC, np.delete(dS, idx) if kind == "s" else dS])
+                if variant == "contact":
+                    assert rest.min() >= 0.05
+                    assert (d[kind][idx] < -0.1) if w == 0 else (d[kind][idx] == 0.0)
+                else:
+                    assert 0.05 <= d[kind][idx] <= 0.45 and rest.min() >= 0.6        # the nearest row is the one placed by hand
+    # circles 0 - 4 of the wall set are outside after one step and inside after two; 5 - 8 sit on their wall after one
+    C1, _ = wr.move_world(wc.WALL_CIRCLES, NONE, wc.STEP_DT, bounds=wc.STEP_BOUNDS)
+    C2, _ = wr.move_world(C1, NONE, wc.STEP_DT, bounds=wc.STEP_BOUNDS)
+    inside = lambda q: (np.abs(q[:, 0:2]) <= 10.0).all(axis=1)
+    assert not inside(C1[:5]).any() and inside(C2[:5]).all()
+    np.testing.assert_array_equal(np.abs(C1[5:9, 0:2]).max(axis=1), 10.0)
+    np.testing.assert_array_equal(C1[5:9, 3:5], wc.WALL_CIRCLES[5:9, 3:5])           # on the wall: not turned yet
+    np.testing.assert_array_equal(C2[5:9, 3:5], -wc.WALL_CIRCLES[5:9, 3:5])
+    np.testing.assert_array_equal(C2[9], wc.WALL_CIRCLES[9])
+    assert C2[10, 3] == 1.0 and (C1[4, 3:5] == -1.0).all()
+
+
+@pytest.mark.parametrize("poly", ["triangle", "pentagon", "hull8"])
+def test_feature_cases_reach_every_edge_and_vertex(poly):
+    import world_cases as wc
+    V = wc.POLYGONS[poly]
+    cases = wc.feature_cases(V)
+    got = wc.features_by_the_reference(V, cases)
+    assert got == [(k["kind"], k["feature"]) for k in cases]
+    E = len(V)
+    assert {g for g in got} == ({(kind, ("edge", e)) for kind in ("circle", "end") for e in range(E)}
+                                | {(kind, ("vertex", v)) for kind in ("circle", "end", "inside") for v in range(E)})
+
+
+def test_scan_validates_out_before_it_touches_a_device(lib):
+    import torch
+    from neupan_amd.world import LidarWorld
+    w = LidarWorld(np.array([[5.0, 0.0, 1.0]]), device="cpu")
+    st = np.zeros((2, 3))
+    good = lambda R=8: [torch.zeros((2, R), dtype=torch.float64), torch.zeros((2, 2, R), dtype=torch.float64),
+                        torch.zeros((2, R), dtype=torch.int32)]
+    bad = []
+    for k, t in enumerate((torch.zeros((3, 8), dtype=torch.float64), torch.zeros((2, 8), dtype=torch.float32),
+                           torch.zeros((2, 16), dtype=torch.float64)[:, ::2], torch.zeros((2, 8), dtype=torch.float64, device="meta"),
+                           torch.zeros((16,), dtype=torch.float64))):
+        o = good(); o[0] = t; bad.append(o)
+    o = good(); o[1] = torch.zeros((2, 8, 2), dtype=torch.float64); bad.append(o)
+    o = good(); o[1] = torch.zeros((2, 2, 8), dtype=torch.float32); bad.append(o)
+    o = good(); o[2] = torch.zeros((2, 8), dtype=torch.int64); bad.append(o)
+    o = good(); o[2] = torch.zeros((2, 9), dtype=torch.int32); bad.append(o)
+    o = good(); o[2] = torch.zeros((8, 2), dtype=torch.int32).t(); bad.append(o)
+    bad += [good()[:2], good(4), [t.numpy() for t in good()]]
+    for o in bad:
+        for n_beams in (5, [5, 3]):
+            with pytest.raises(ValueError, match="out"):
+                w.scan(st, n_beams, -pi, pi, 0.0, 10.0, out=o)
