@@ -499,6 +499,58 @@ int npa_world_step(int batch, int n_worlds, int c_stride, int s_stride, double *
                    const int32_t *frozen, double dt, int kinematics, double wheelbase, const double *bounds,
                    int edge_num, const double *vertices, int peer_base, double *clearance, void *stream);
 
+/* ---- the bookkeeping of a device-resident closed loop (csrc/cycle.hip) -----------------------------------------------
+ *
+ * What the host does between the kernels of a control cycle, as three calls: handle-free, stream-ordered, one thread per
+ * robot, no workspace, no atomics, nothing allocated, no host synchronisation.  They only select and copy, so a cycle
+ *     npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states -> npa_forward_batch
+ *     [-> npa_plan_clearance] -> npa_cycle_act -> npa_world_step -> npa_cycle_commit
+ * on one stream over buffers that stay where they are gives the bits of the same cycle paced by the host.
+ *
+ * The curve table holds ALL curves of all robots: path [rows][4] f64 rows (x, y, theta, gear), curve c owns rows
+ * curve_off[c] .. curve_off[c] + curve_len[c] - 1, robot b owns the curves robot_first[b] .. robot_first[b + 1] - 1
+ * (robot_first [B + 1]; every robot has at least one curve of at least one point).  Per-robot state, device int32 [B]:
+ * curve_index (into the robot's curves), cur_off / cur_len (= the table's entry of the current curve: the curve arguments
+ * of npa_nominal_ref_states), point_index, arrived (a latch: 0 / 1).  The caller initialises them once: curve_index = 0,
+ * cur_off / cur_len = the robot's first curve, point_index = 0, arrived = 0.
+ *
+ * npa_cycle_progress replaces check_arrive and the curve switching around it (neupan/blocks/initial_path.py:247-315, called
+ *   at neupan/neupan.py:113).  Two launches: npa_path_progress's kernel on (cur_off, cur_len, point_index) -- the same
+ *   arithmetic, curve_arrived [B] receives its arrival flags --, then for a robot that reports arrival and is not latched:
+ *   on its last curve with loop != 0 curve_index = 0 and point_index = 0; on its last curve without loop arrived = 1;
+ *   otherwise curve_index += 1 and point_index = 0.  cur_off / cur_len follow curve_index.  state [B][3] f64 is also written
+ *   into the `state` field of params_a[b] and params_b[b] (the rows npa_world_scan and npa_scan_to_points read; the two may
+ *   be the same block).
+ *
+ * npa_cycle_act replaces the tail of neupan.forward behind the PAN call (neupan/neupan.py:137 and :150-164) and the driver's
+ *   freeze, in this order.  done = arrived[b] != 0.  cur_vel [B][2][T] <- opt_u [B][2][T] unless done (first_cycle != 0: for
+ *   every robot -- the reference's cur_vel_array of zeros has just been consumed).  stop = min_distance[b] <
+ *   collision_threshold (f32).  The action is opt_u[b][:][0]; kinematics 2 (omni): (v cos phi, v sin phi) in f32.  It is
+ *   zeroed where done or stop; then override_row [B][2] f32 (nullable) replaces the entries it holds that are not NaN; then
+ *   frozen[b] = arrived[b] | collided[b] and the action is zeroed where frozen.  Outputs: action [B][2] f32 and frozen [B]
+ *   int32 (npa_world_step's arguments), stop [B] uint8 = stop and not done, and row `cycle` of the logs (each nullable):
+ *   log_actions [cycles][B][2] f32, log_stop [cycles][B] uint8, log_controls [cycles][B][2][T] f32 (opt_u), log_n_points
+ *   [cycles][B] int32 (n_points [B], nullable: zeros).  `cycle` travels by value: there is no device-side counter.
+ *
+ * npa_cycle_commit runs behind npa_world_step: collided[b] |= clearance[b] <= 0 (clearance [B] f64), and the cycle's rows of
+ *   the logs (nullable): log_clearance [cycles][B] f64 row `cycle`, log_states [cycles + 1][B][3] f64 row `cycle + 1` (row 0
+ *   is the caller's: the initial poses).
+ *
+ * NPA_E_ARG (before anything touches a device): a null required pointer, batch < 1, cycle < 0, ind_range < 1, receding
+ *   outside [1, NPA_MAX_T], kinematics outside 0..2. */
+int npa_cycle_progress(int batch, const double *state, const double *path, const int32_t *curve_off,
+                       const int32_t *curve_len, const int32_t *robot_first, int loop, double close_threshold,
+                       int ind_range, double arrive_threshold, int arrive_index_threshold, int32_t *curve_index,
+                       int32_t *cur_off, int32_t *cur_len, int32_t *point_index, int32_t *curve_arrived,
+                       int32_t *arrived, npa_scan_params *params_a, npa_scan_params *params_b, void *stream);
+int npa_cycle_act(int batch, int receding, int kinematics, int first_cycle, int cycle, const float *opt_u,
+                  const float *min_distance, float collision_threshold, const int32_t *arrived,
+                  const int32_t *collided, const float *override_row, const int32_t *n_points, float *cur_vel,
+                  float *action, uint8_t *stop, int32_t *frozen, float *log_actions, uint8_t *log_stop,
+                  float *log_controls, int32_t *log_n_points, void *stream);
+int npa_cycle_commit(int batch, int cycle, const double *state, const double *clearance, int32_t *collided,
+                     double *log_states, double *log_clearance, void *stream);
+
 /* ---- DUNE training labels (offline) ---------------------------------------------------------------
  * npa_dune_labels replaces DUNETrain.prob_solve / generate_data_set
  *   (neupan/blocks/dune_train.py:82-99, :109-140): for every point p the maximiser mu of

@@ -83,6 +83,9 @@ SYMBOLS = {
     "npa_world_scan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "npa_world_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_double, _I, C.c_double, C.POINTER(C.c_double), _I,
                             C.POINTER(C.c_double), _I, _P, _P]),
+    "npa_cycle_progress": (_I, [_I, _P, _P, _P, _P, _P, _I, C.c_double, _I, C.c_double, _I] + [_P] * 8 + [_P]),
+    "npa_cycle_act": (_I, [_I, _I, _I, _I, _I, _P, _P, C.c_float] + [_P] * 12 + [_P]),
+    "npa_cycle_commit": (_I, [_I, _I, _P, _P, _P, _P, _P, _P]),
     "npa_dune_labels": (_I, [_I, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "npa_profile_enable": (_I, [_P, _I]),
     "npa_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

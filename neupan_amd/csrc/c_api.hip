@@ -68,7 +68,7 @@ extern "C" hipError_t npa_launch_ingest_unpack(int batch, int T, int n_stride, i
                                                hipStream_t stream);
 
 extern "C" const char* npa_last_error(void) { return g_err.c_str(); }
-extern "C" const char* npa_version(void) { return "neupan_amd 0.5 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
+extern "C" const char* npa_version(void) { return "neupan_amd 0.5.1 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
 // per-slice stride of the key buffer inside the workspace: none with geometric keys (select_kernel keeps them in LDS)
 static int kstride(const npa_handle* h) { return h->key_terms == 4 ? 0 : h->P.key_stride; }
 
@@ -671,6 +671,57 @@ extern "C" int npa_scan_to_points(int batch, int beam_stride, const double* rang
   if (mode != 0 && mode != 1) return fail(NPA_E_ARG, "npa_scan_to_points: mode must be 0 or 1");
   HIP_TRY(npa_launch_scan(batch, beam_stride, ranges, beam_vel, n_beams, params, mode, out_stride, points, velocities,
                           count, (hipStream_t)stream));
+  return NPA_OK;
+}
+
+// ---- the bookkeeping of a device-resident closed loop (cycle.hip) ------------------------------------
+extern "C" hipError_t npa_launch_cycle_switch(int batch, int loop, const double* state, const int* curve_arrived,
+                                              const int* curve_off, const int* curve_len, const int* robot_first,
+                                              int* curve_index, int* cur_off, int* cur_len, int* point_index, int* arrived,
+                                              npa_scan_params* params_a, npa_scan_params* params_b, hipStream_t stream);
+extern "C" hipError_t npa_launch_cycle_act(int batch, int T, int kin, int first_cycle, int cycle, const float* opt_u,
+                                           const float* min_distance, float threshold, const int* arrived, const int* collided,
+                                           const float* override_row, const int* n_points, float* cur_vel, float* action,
+                                           uint8_t* stop, int* frozen, float* log_actions, uint8_t* log_stop,
+                                           float* log_controls, int* log_n_points, hipStream_t stream);
+extern "C" hipError_t npa_launch_cycle_commit(int batch, int cycle, const double* state, const double* clearance, int* collided,
+                                              double* log_states, double* log_clearance, hipStream_t stream);
+
+extern "C" int npa_cycle_progress(int batch, const double* state, const double* path, const int32_t* curve_off,
+                                  const int32_t* curve_len, const int32_t* robot_first, int loop, double close_threshold,
+                                  int ind_range, double arrive_threshold, int arrive_index_threshold, int32_t* curve_index,
+                                  int32_t* cur_off, int32_t* cur_len, int32_t* point_index, int32_t* curve_arrived,
+                                  int32_t* arrived, npa_scan_params* params_a, npa_scan_params* params_b, void* stream) {
+  if (batch < 1 || !state || !path || !curve_off || !curve_len || !robot_first || !curve_index || !cur_off || !cur_len ||
+      !point_index || !curve_arrived || !arrived || !params_a || !params_b || ind_range < 1)
+    return fail(NPA_E_ARG, "npa_cycle_progress: bad argument");
+  // the arithmetic of the progress is progress_kernel's own, on every robot's CURRENT curve; the switch runs behind it
+  HIP_TRY(npa_launch_progress(batch, state, path, cur_off, cur_len, point_index, close_threshold, ind_range, arrive_threshold,
+                              arrive_index_threshold, nullptr, curve_arrived, (hipStream_t)stream));
+  HIP_TRY(npa_launch_cycle_switch(batch, loop, state, curve_arrived, curve_off, curve_len, robot_first, curve_index, cur_off,
+                                  cur_len, point_index, arrived, params_a, params_b, (hipStream_t)stream));
+  return NPA_OK;
+}
+
+extern "C" int npa_cycle_act(int batch, int receding, int kinematics, int first_cycle, int cycle, const float* opt_u,
+                             const float* min_distance, float collision_threshold, const int32_t* arrived,
+                             const int32_t* collided, const float* override_row, const int32_t* n_points, float* cur_vel,
+                             float* action, uint8_t* stop, int32_t* frozen, float* log_actions, uint8_t* log_stop,
+                             float* log_controls, int32_t* log_n_points, void* stream) {
+  if (batch < 1 || cycle < 0 || !opt_u || !min_distance || !arrived || !collided || !cur_vel || !action || !stop || !frozen)
+    return fail(NPA_E_ARG, "npa_cycle_act: bad argument");
+  if (receding < 1 || receding > NPA_MAX_T) return fail(NPA_E_ARG, "npa_cycle_act: receding outside [1,NPA_MAX_T]");
+  if (kinematics < 0 || kinematics > 2) return fail(NPA_E_ARG, "npa_cycle_act: unknown kinematics");
+  HIP_TRY(npa_launch_cycle_act(batch, receding, kinematics, first_cycle, cycle, opt_u, min_distance, collision_threshold, arrived,
+                               collided, override_row, n_points, cur_vel, action, stop, frozen, log_actions, log_stop,
+                               log_controls, log_n_points, (hipStream_t)stream));
+  return NPA_OK;
+}
+
+extern "C" int npa_cycle_commit(int batch, int cycle, const double* state, const double* clearance, int32_t* collided,
+                                double* log_states, double* log_clearance, void* stream) {
+  if (batch < 1 || cycle < 0 || !state || !clearance || !collided) return fail(NPA_E_ARG, "npa_cycle_commit: bad argument");
+  HIP_TRY(npa_launch_cycle_commit(batch, cycle, state, clearance, collided, log_states, log_clearance, (hipStream_t)stream));
   return NPA_OK;
 }
 

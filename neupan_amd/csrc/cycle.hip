@@ -1,0 +1,134 @@
+// The bookkeeping between the kernels of a closed-loop control cycle, on the device (gfx950 only):
+//   cycle_switch_kernel  curve switching and the arrival latch behind progress_kernel   initial_path.py:247-315
+//   cycle_act_kernel     warm start, stop test, action, scripted override, freeze       neupan.py:137, :150-164
+//   cycle_commit_kernel  the collision latch and the cycle's log rows behind the plant step
+// One thread per robot, no workspace, no atomics; handle-free and stream-ordered like frontend.hip.  Every per-robot decision
+// is a select and every loop bound is a launch argument: the kernels only choose and copy, so a loop built from them gives
+// the bits of the host-paced loop (FleetPlanner.forward + run_closed_loop) whose rules they restate.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/neupan_amd.h"
+
+namespace {
+
+constexpr int CY_THREADS = 64;
+
+// FleetPlanner.forward's rule for a robot whose progress reports arrival and that is not latched: on its last curve it starts
+// over (`loop`) or latches, else it moves to its next curve; a robot that moves starts the new curve at point 0.  The pose
+// goes into the `state` field of the two parameter blocks the scans of this cycle read.
+__global__ __launch_bounds__(CY_THREADS) void cycle_switch_kernel(
+    int batch, int loop, const double* __restrict__ state, const int* __restrict__ curve_arrived,
+    const int* __restrict__ curve_off, const int* __restrict__ curve_len, const int* __restrict__ robot_first,
+    int* __restrict__ curve_index, int* __restrict__ cur_off, int* __restrict__ cur_len, int* __restrict__ point_index,
+    int* __restrict__ arrived, npa_scan_params* __restrict__ par_a, npa_scan_params* __restrict__ par_b) {
+  const int b = blockIdx.x * CY_THREADS + threadIdx.x;
+  if (b >= batch) return;
+  const int first = robot_first[b], count = robot_first[b + 1] - first;
+  const int ci = curve_index[b], latched = arrived[b];
+  const bool now = curve_arrived[b] != 0 && latched == 0;
+  const bool last = ci + 1 >= count;
+  const bool move = now && (!last || loop != 0);
+  int next = last ? 0 : ci + 1;
+  next = move ? next : ci;
+  next = next < 0 ? 0 : (next > count - 1 ? count - 1 : next);       // (a table entry is read: never outside the robot's curves)
+  curve_index[b] = next;
+  cur_off[b] = curve_off[first + next];
+  cur_len[b] = curve_len[first + next];
+  point_index[b] = move ? 0 : point_index[b];
+  arrived[b] = (latched != 0 || (now && last && loop == 0)) ? 1 : 0;
+  const double x = state[b * 3 + 0], y = state[b * 3 + 1], th = state[b * 3 + 2];
+  par_a[b].state[0] = x; par_a[b].state[1] = y; par_a[b].state[2] = th;
+  par_b[b].state[0] = x; par_b[b].state[1] = y; par_b[b].state[2] = th;
+}
+
+__global__ __launch_bounds__(CY_THREADS) void cycle_act_kernel(
+    int batch, int T, int kin, int first_cycle, int cycle, const float* __restrict__ opt_u, const float* __restrict__ min_distance,
+    float threshold, const int* __restrict__ arrived, const int* __restrict__ collided, const float* __restrict__ override_row,
+    const int* __restrict__ n_points, float* __restrict__ cur_vel, float* __restrict__ action, uint8_t* __restrict__ stop_out,
+    int* __restrict__ frozen, float* __restrict__ log_actions, uint8_t* __restrict__ log_stop, float* __restrict__ log_controls,
+    int* __restrict__ log_n_points) {
+  const int b = blockIdx.x * CY_THREADS + threadIdx.x;
+  if (b >= batch) return;
+  const bool done = arrived[b] != 0;
+  const bool keep = done && first_cycle == 0;                 // neupan.py:137 is not reached by a robot that has arrived
+  const float* u = opt_u + (size_t)b * 2 * T;
+  float* cv = cur_vel + (size_t)b * 2 * T;
+  float* lc = log_controls ? log_controls + ((size_t)cycle * batch + b) * 2 * T : nullptr;
+  for (int i = 0; i < 2 * T; ++i) {
+    const float ui = u[i], old = cv[i];
+    cv[i] = keep ? old : ui;
+    if (lc) lc[i] = ui;
+  }
+  const bool stop = min_distance[b] < threshold;              // neupan.py:150-154, :169
+  const float v = u[0], w = u[T];
+  float a0 = v, a1 = w;
+  if (kin == NPA_KIN_OMNI) {                                  // neupan.py:158-164
+    a0 = v * cosf(w);
+    a1 = v * sinf(w);
+  }
+  const bool zero = done || stop;
+  a0 = zero ? 0.f : a0;
+  a1 = zero ? 0.f : a1;
+  if (override_row) {                                         // scripted robots: entries that are not NaN replace the action
+    const float o0 = override_row[b * 2 + 0], o1 = override_row[b * 2 + 1];
+    a0 = o0 != o0 ? a0 : o0;
+    a1 = o1 != o1 ? a1 : o1;
+  }
+  const bool frz = done || collided[b] != 0;
+  a0 = frz ? 0.f : a0;
+  a1 = frz ? 0.f : a1;
+  const uint8_t s = (stop && !done) ? 1 : 0;
+  action[b * 2 + 0] = a0;
+  action[b * 2 + 1] = a1;
+  stop_out[b] = s;
+  frozen[b] = frz ? 1 : 0;
+  const size_t row = (size_t)cycle * batch + b;
+  if (log_actions) { log_actions[row * 2 + 0] = a0; log_actions[row * 2 + 1] = a1; }
+  if (log_stop) log_stop[row] = s;
+  if (log_n_points) log_n_points[row] = n_points ? n_points[b] : 0;
+}
+
+__global__ __launch_bounds__(CY_THREADS) void cycle_commit_kernel(
+    int batch, int cycle, const double* __restrict__ state, const double* __restrict__ clearance, int* __restrict__ collided,
+    double* __restrict__ log_states, double* __restrict__ log_clearance) {
+  const int b = blockIdx.x * CY_THREADS + threadIdx.x;
+  if (b >= batch) return;
+  const double c = clearance[b];
+  collided[b] = (collided[b] != 0 || c <= 0.0) ? 1 : 0;
+  if (log_clearance) log_clearance[(size_t)cycle * batch + b] = c;
+  if (log_states) {
+    double* row = log_states + ((size_t)(cycle + 1) * batch + b) * 3;
+    row[0] = state[b * 3 + 0]; row[1] = state[b * 3 + 1]; row[2] = state[b * 3 + 2];
+  }
+}
+
+}  // namespace
+
+extern "C" hipError_t npa_launch_cycle_switch(int batch, int loop, const double* state, const int* curve_arrived,
+                                              const int* curve_off, const int* curve_len, const int* robot_first,
+                                              int* curve_index, int* cur_off, int* cur_len, int* point_index, int* arrived,
+                                              npa_scan_params* params_a, npa_scan_params* params_b, hipStream_t stream) {
+  hipLaunchKernelGGL(cycle_switch_kernel, dim3((batch + CY_THREADS - 1) / CY_THREADS), dim3(CY_THREADS), 0, stream, batch, loop,
+                     state, curve_arrived, curve_off, curve_len, robot_first, curve_index, cur_off, cur_len, point_index, arrived,
+                     params_a, params_b);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t npa_launch_cycle_act(int batch, int T, int kin, int first_cycle, int cycle, const float* opt_u,
+                                           const float* min_distance, float threshold, const int* arrived, const int* collided,
+                                           const float* override_row, const int* n_points, float* cur_vel, float* action,
+                                           uint8_t* stop, int* frozen, float* log_actions, uint8_t* log_stop,
+                                           float* log_controls, int* log_n_points, hipStream_t stream) {
+  hipLaunchKernelGGL(cycle_act_kernel, dim3((batch + CY_THREADS - 1) / CY_THREADS), dim3(CY_THREADS), 0, stream, batch, T, kin,
+                     first_cycle, cycle, opt_u, min_distance, threshold, arrived, collided, override_row, n_points, cur_vel,
+                     action, stop, frozen, log_actions, log_stop, log_controls, log_n_points);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t npa_launch_cycle_commit(int batch, int cycle, const double* state, const double* clearance, int* collided,
+                                              double* log_states, double* log_clearance, hipStream_t stream) {
+  hipLaunchKernelGGL(cycle_commit_kernel, dim3((batch + CY_THREADS - 1) / CY_THREADS), dim3(CY_THREADS), 0, stream, batch, cycle,
+                     state, clearance, collided, log_states, log_clearance);
+  return hipGetLastError();
+}

@@ -6,6 +6,8 @@ simulator plays (example/run_exp.py: env.get_lidar_scan() -> scan_to_point -> ne
                       robot's exact clearance to the world (npa_world_step).  `from_yaml` reads the `obstacle:` list of an
                       IR-SIM environment file.
 * `run_closed_loop`   scan -> scan_to_point[_velocity]_batch -> FleetPlanner.forward -> step, for B robots and a number of cycles.
+* `ResidentLoop`      the same cycle as a fixed sequence of launches over buffers that never move: the path bookkeeping, the action
+                      and the latches are kernels too (csrc/cycle.hip), so the host neither reads the device nor allocates.
 
 There is no CPU fallback: scan and step are the HIP kernels of csrc/world.hip behind the C ABI (include/neupan_amd.h).
 What IR-SIM does and this does not: sensor noise, obstacle behaviours (rvo, ...), rendering.
@@ -20,8 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import KIN, check
-from .frontend import _SCAN_DTYPE, _ptr, _stream, scan_to_point_batch, scan_to_point_velocity_batch
+from ._lib import KIN, NeupanAmdError, check
+from .frontend import _SCAN_DTYPE, _bcast, _ptr, _stream, scan_to_point_batch, scan_to_point_velocity_batch
 
 _PARAM_DOUBLES = _SCAN_DTYPE.itemsize // 8         # npa_scan_params as a row of float64 words (13; the last holds two int32)
 assert _SCAN_DTYPE.itemsize % 8 == 0
@@ -388,3 +390,279 @@ def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=Fa
     if certify and cycles > 0:
         out["plan_clearance"] = last_info["clearance"]
     return out
+
+
+def curve_table(curve_lists):
+    """All curves of all robots as one table: `curve_lists[b]` = robot b's curves in driving order, arrays [P, 4] of rows
+    x, y, theta, gear (FleetPlanner.curve_lists: what `_split_by_gear` makes of a path).  Returns numpy arrays (path [rows, 4]
+    float64: the curves back to back; curve_off [C] and curve_len [C] int32: curve c owns rows curve_off[c] .. curve_off[c] +
+    curve_len[c] - 1; robot_first [B + 1] int32: robot b owns curves robot_first[b] .. robot_first[b + 1] - 1) -- the layout
+    npa_cycle_progress reads (include/neupan_amd.h)."""
+    rows, off, ln, first = [], [], [], [0]
+    o = 0
+    for b, curves in enumerate(curve_lists):
+        if len(curves) < 1:
+            raise ValueError(f"robot {b} has no curve")
+        for c in curves:
+            a = np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(-1, 4))
+            if a.shape[0] < 1:
+                raise ValueError(f"robot {b} has an empty curve")
+            rows.append(a); off.append(o); ln.append(a.shape[0]); o += a.shape[0]
+        first.append(len(off))
+    if not rows:
+        raise ValueError("no robots")
+    return (np.ascontiguousarray(np.concatenate(rows, axis=0)), np.asarray(off, dtype=np.int32), np.asarray(ln, dtype=np.int32),
+            np.asarray(first, dtype=np.int32))
+
+
+class ResidentLoop:
+    """`run_closed_loop` with every buffer allocated once and all per-robot bookkeeping on the device.  One cycle is this launch
+    sequence on the current stream, with no host synchronisation and no allocation:
+
+        npa_cycle_progress (path progress, curve switch, arrival latch, poses -> both scan parameter blocks)
+        -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states -> npa_forward_batch_flags
+        [-> npa_plan_clearance] -> npa_cycle_act (warm start, stop, action, override, freeze) -> npa_world_step
+        -> npa_cycle_commit (collision latch, log rows)
+
+    The arguments are `run_closed_loop`'s.  `fleet` must be fresh from `set_paths` (its host bookkeeping -- curve_index, arrived,
+    cur_vel -- is not used again: this object owns the device copy, and `fleet.forward` must not be mixed in until the next
+    `set_paths`); its adjust parameters must not require gradients (that path is `fleet.forward`'s).  A per-scene block from
+    `fleet.set_adjust` is read by the kernels at run time: rewrite it in place between cycles.  `world` must not be rebuilt
+    (add_polygon) while the loop lives: its device arrays are held by address.
+    No priming forward runs here: the first cycle plans from the state a fresh FleetPlanner plans its first cycle from (the
+    planner's state record as it is, cur_vel zeros, min_distance as the kernels persist it).
+    Columns of the cloud at or beyond n_points[b] keep what an earlier cycle left; the selection and the clearance kernel bound
+    their reads by n_points.
+    Attributes (device tensors, valid in stream order, the same objects for the life of the loop): states [B, 3] f64, action
+    [B, 2] f32, stop [B] uint8, frozen / arrived / collided [B] int32, clearance [B] f64, points, point_velocities, n_points,
+    out (the plan's dict as PAN.forward_batch returns it), plan_clearance (with certify: PAN.plan_clearance's dict)."""
+
+    def __init__(self, fleet, world, states, scan=None, point_velocities=False, certify=False, peers=False, max_points=None):
+        if getattr(fleet, "B", 0) < 1:
+            raise ValueError("ResidentLoop: the fleet has no paths (set_paths first)")
+        if fleet.cur_vel is not None:
+            raise ValueError("ResidentLoop: the fleet has already planned a cycle (cur_vel is set): its warm start and its path "
+                             "bookkeeping live on the host and cannot be taken over -- call set_paths again")
+        pan = fleet.pan
+        if any(p.requires_grad for p in pan.nrmp_layer.adjust_parameters):
+            raise ValueError("ResidentLoop: an adjust parameter requires a gradient; the plan would be cut off from it here -- "
+                             "the gradient path is FleetPlanner.forward")
+        if getattr(pan, "_untrained", False) or not pan._h.value:
+            raise NeupanAmdError("ResidentLoop: the planner has no kernel handle (no DUNE checkpoint yet)")
+        if pan.iter_num != pan._cfg.iter_num:
+            raise ValueError(f"ResidentLoop: PAN.iter_num was changed to {pan.iter_num} after the planner was made with "
+                             f"{pan._cfg.iter_num}; the prepared plan call runs the handle's count")
+        if certify and pan.no_obs:
+            raise NeupanAmdError("ResidentLoop: certify needs the planner's obstacle stage (PAN.plan_clearance)")
+        sp = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0)
+        sp.update(scan or {})
+        lib, dev = _lib.load(), world.device
+        if torch.device(fleet.device).type != dev.type:
+            raise ValueError(f"ResidentLoop: the fleet is on {fleet.device}, the world on {dev}")
+        self._lib, self.device, self.fleet, self.world = lib, dev, fleet, world
+        self._idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        B, T = fleet.B, fleet.T
+        st = world._states(states).clone()
+        if st.shape[0] != B:
+            raise ValueError(f"ResidentLoop: {st.shape[0]} poses for {B} robots")
+        if world.W not in (1, B):
+            raise ValueError(f"{world.W} worlds for {B} robots")
+        V = np.ascontiguousarray(robot_vertices(fleet.robot))
+        kin, L = fleet.robot.kinematics, getattr(fleet.robot, "L", 0.0) or 0.0
+        if peers:
+            world.set_peers(st, V)
+        self.B, self.T, self.certify, self.cycles_done = B, T, bool(certify), 0
+        self.states = st
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+        empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        # ---- the curve table and the per-robot path state
+        path, off, ln, first = curve_table(fleet.curve_lists)
+        self._table = (torch.from_numpy(path).to(dev), i32(off), i32(ln), i32(first))
+        self.curve_index = zeros((B,), torch.int32)
+        self.cur_off, self.cur_len = i32(off[first[:-1]]), i32(ln[first[:-1]])
+        self.point_index, self.arrived, self.collided = zeros((B,), torch.int32), zeros((B,), torch.int32), zeros((B,), torch.int32)
+        self._curve_arrived = zeros((B,), torch.int32)
+        # ---- the two parameter blocks: the world scan's (as LidarWorld.scan fills it) and npa_scan_to_points' (as _scan does)
+        offset = sp.get("scan_offset", (0.0, 0.0, 0.0))
+        if isinstance(sp["n_beams"], (int, np.integer)):
+            R, nb = int(sp["n_beams"]), None
+        else:
+            nb_h = np.asarray(sp["n_beams"], dtype=np.int32).reshape(B)
+            R, nb = int(nb_h.max()), i32(nb_h)
+        if R < 1:
+            raise ValueError("ResidentLoop: a scan needs at least one beam")
+        par_w = zeros((B, _PARAM_DOUBLES), torch.float64)
+        head = np.zeros((B, 4))
+        for k, key in enumerate(("angle_min", "angle_max", "range_min", "range_max")):
+            head[:, k] = np.broadcast_to(np.asarray(sp[key], dtype=np.float64), (B,))
+        par_w[:, 0:4] = torch.from_numpy(head).to(dev)
+        par_w[:, 4:7] = st
+        par_w[:, 7:10] = torch.from_numpy(np.broadcast_to(np.asarray(offset, dtype=np.float64), (B, 3)).copy()).to(dev)
+        par = np.zeros(B, dtype=_SCAN_DTYPE)
+        par["angle_min"], par["angle_max"] = head[:, 0], head[:, 1]
+        par["range_min"], par["range_max"] = head[:, 2], head[:, 3]
+        par["state"] = st.cpu().numpy()
+        par["offset"] = _bcast(offset, B, 3)
+        par["angle_range"] = _bcast(sp.get("angle_range", (-pi, pi)), B, 2)
+        par["down_sample"] = np.broadcast_to(np.asarray(sp.get("down_sample", 1), dtype=np.int32), (B,))
+        if (par["down_sample"] < 1).any():
+            raise ValueError("down_sample must be >= 1")
+        par_s = torch.from_numpy(par.view(np.uint8).reshape(B, -1).copy()).to(dev)
+        self._params = (par_w, par_s)
+        # ---- scan outputs and the cloud
+        self.ranges, self.beam_vel, self.hit = zeros((B, R), torch.float64), zeros((B, 2, R), torch.float64), zeros((B, R), torch.int32)
+        N = int(max_points) if max_points else R
+        self.points = zeros((B, 2, N), torch.float32)
+        self.point_velocities = zeros((B, 2, N), torch.float32) if point_velocities else None
+        self.n_points = zeros((B,), torch.int32)
+        c, s, nc, ns = world._upload()
+        skip = world.skip if (world.skip is not None and world.skip.shape[0] == B) else None
+        # ---- nominal / reference
+        nbt = fleet.nb
+        self.cur_vel = zeros((B, 2, T), torch.float32)              # (zeros on the first cycle: neupan.py:73)
+        spd = torch.from_numpy(_bcast(fleet.ref_speed, B)).to(dev)
+        itv = torch.from_numpy(_bcast(fleet.intervals, B)).to(dev)
+        nom_s, ref_s = empty((B, 3, T + 1), torch.float32), empty((B, 3, T + 1), torch.float32)
+        nom_u, ref_us = empty((B, 2, T), torch.float32), empty((B, T), torch.float32)
+        self.nominal = (nom_s, nom_u, ref_s, ref_us)
+        # ---- the plan: npa_forward_batch_flags over these tensors, as PAN.forward_begin stages it
+        M = pan.nrmp_max_num
+        use_pts = not pan.no_obs
+        p_pts, p_vel, p_np = (self.points, self.point_velocities, self.n_points) if use_pts else (None, None, None)
+        ws, state = pan._get_buffers(B)
+        out = dict(opt_s=empty((B, 3, T + 1), torch.float32), opt_u=empty((B, 2, T), torch.float32),
+                   opt_d=empty((B, 1, max(T, 1)), torch.float32) if M > 0 and pan.dune_max_num > 0 else None,
+                   min_distance=empty((B,), torch.float32), iters=empty((B,), torch.int32),
+                   nrmp_points=empty((B, 2, M), torch.float32) if not pan.no_obs else None)
+        self.out = out
+        self._pan_last = dict(points=p_pts, velocities=p_vel, n_points=p_np, min_distance=out["min_distance"],
+                              nrmp_points=out["nrmp_points"], used_points=use_pts, hold=self.nominal)
+        self._plan = (pan._h, B, N if use_pts else 1, _ptr(nom_s), _ptr(nom_u), _ptr(ref_s), _ptr(ref_us), _ptr(p_pts), _ptr(p_vel),
+                      _ptr(p_np), _ptr(out["opt_s"]), _ptr(out["opt_u"]), _ptr(out["opt_d"]), _ptr(out["min_distance"]),
+                      _ptr(out["iters"]), _ptr(out["nrmp_points"]), _ptr(ws), ws.numel(), _ptr(state), state.numel())
+        self._held = (ws, state, c, s, nc, ns, skip, nb, spd, itv, V)
+        self._held_ptrs = (ws.data_ptr(), state.data_ptr())
+        self.plan_clearance = None
+        self._certify = None
+        if certify:
+            self.plan_clearance = dict(clearance=empty((B, T + 1), torch.float32), nearest=empty((B, T + 1), torch.int32),
+                                       min_clearance=empty((B,), torch.float32), first_violation=empty((B,), torch.int32))
+            pc = self.plan_clearance
+            self._certify = (pan._h, B, N, _ptr(out["opt_s"]), _ptr(self.points), _ptr(self.point_velocities), _ptr(self.n_points),
+                             float(fleet.collision_threshold), _ptr(pc["clearance"]), _ptr(pc["nearest"]), _ptr(pc["min_clearance"]),
+                             _ptr(pc["first_violation"]))
+        # ---- act, step, commit
+        self.action, self.stop = zeros((B, 2), torch.float32), zeros((B,), torch.uint8)
+        self.frozen, self.clearance = zeros((B,), torch.int32), empty((B,), torch.float64)
+        path_d, off_d, len_d, first_d = self._table
+        self._front = (
+            ("npa_cycle_progress", lib.npa_cycle_progress,
+             (B, _ptr(st), _ptr(path_d), _ptr(off_d), _ptr(len_d), _ptr(first_d), 1 if fleet.loop else 0, fleet.close_threshold,
+              fleet.ind_range, fleet.arrive_threshold, fleet.arrive_index_threshold, _ptr(self.curve_index), _ptr(self.cur_off),
+              _ptr(self.cur_len), _ptr(self.point_index), _ptr(self._curve_arrived), _ptr(self.arrived), _ptr(par_w), _ptr(par_s))),
+            ("npa_world_scan", lib.npa_world_scan,
+             (B, world.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par_w), _ptr(nb), R, _ptr(skip),
+              _ptr(self.ranges), _ptr(self.beam_vel), _ptr(self.hit))),
+            ("npa_scan_to_points", lib.npa_scan_to_points,
+             (B, R, _ptr(self.ranges), _ptr(self.beam_vel) if point_velocities else None, None, _ptr(par_s),
+              1 if point_velocities else 0, N, _ptr(self.points), _ptr(self.point_velocities), _ptr(self.n_points))),
+            ("npa_nominal_ref_states", lib.npa_nominal_ref_states,
+             (B, T, KIN[kin], fleet.dt, nbt.L, _ptr(st), _ptr(self.cur_vel), _ptr(spd), _ptr(path_d), _ptr(self.cur_off),
+              _ptr(self.cur_len), _ptr(self.point_index), _ptr(itv), _ptr(nom_s), _ptr(nom_u), _ptr(ref_s), _ptr(ref_us))))
+        self._act = (_ptr(out["opt_u"]), _ptr(out["min_distance"]), float(fleet.collision_threshold), _ptr(self.arrived),
+                     _ptr(self.collided))
+        self._act_out = (_ptr(self.n_points), _ptr(self.cur_vel), _ptr(self.action), _ptr(self.stop), _ptr(self.frozen))
+        self._kin = KIN[kin]
+        self._step = (B, world.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(st), _ptr(self.action),
+                      _ptr(self.frozen), float(fleet.dt), KIN[kin], float(L), world.bounds, len(V),
+                      V.ctypes.data_as(C.POINTER(C.c_double)), world.peer_base if peers else -1, _ptr(self.clearance))
+        self._commit = (_ptr(st), _ptr(self.clearance), _ptr(self.collided))
+        fleet.cur_vel = self.cur_vel                 # (the fleet has planned from here on: a second loop needs set_paths)
+
+    # ------------------------------------------------------------------ one cycle
+    def _issue(self, override, logs, row):
+        """the nine calls of one cycle; override: a device address or None; logs: six device addresses (actions, stop, controls,
+        n_points, states, clearance) or None; row: the cycle's row in them"""
+        lib, pan = self._lib, self.fleet.pan
+        ws, state = pan._ws, pan._state
+        if ws is None or state is None or (ws.data_ptr(), state.data_ptr()) != self._held_ptrs:
+            raise NeupanAmdError("ResidentLoop: the planner's workspace was re-made since the loop was prepared (another batch "
+                                 "size planned on the same PAN): make the loop again")
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        for name, fn, args in self._front:
+            rc = fn(*args, stream)
+            if rc:
+                check(rc, name)
+        rc = lib.npa_forward_batch_flags(*self._plan, stream, 0)
+        if rc:
+            check(rc, "npa_forward_batch_flags")
+        if self._certify is not None:
+            rc = lib.npa_plan_clearance(*self._certify, stream)
+            if rc:
+                check(rc, "npa_plan_clearance")
+        la, ls, lc, ln, lh, lr = logs if logs is not None else (None,) * 6
+        rc = lib.npa_cycle_act(self.B, self.T, self._kin, 1 if self.cycles_done == 0 else 0, row, *self._act, override,
+                               *self._act_out, la, ls, lc, ln, stream)
+        if rc:
+            check(rc, "npa_cycle_act")
+        rc = lib.npa_world_step(*self._step, stream)
+        if rc:
+            check(rc, "npa_world_step")
+        rc = lib.npa_cycle_commit(self.B, row, *self._commit, lh, lr, stream)
+        if rc:
+            check(rc, "npa_cycle_commit")
+        pan._last, pan.last_out = self._pan_last, self.out
+        self.cycles_done += 1
+        if (self.cycles_done & 63) == 0:             # (a host read of one pinned word: no synchronisation)
+            pan.check_audit()
+
+    def _on_device(self, override, logs, row):
+        if torch.cuda.current_device() != self._idx:   # the launches must see the device of the handle
+            with torch.cuda.device(self.device):
+                self._issue(override, logs, row)
+        else:
+            self._issue(override, logs, row)
+
+    def cycle(self, actions_row=None):
+        """One control cycle on the current stream.  actions_row: a contiguous float32 DEVICE tensor [B, 2] whose entries that
+        are not NaN replace the planner's action (anything else is converted first, which allocates).  Returns `action`, the
+        loop's own [B, 2] tensor: valid in stream order, overwritten by the next cycle."""
+        ov = None
+        if actions_row is not None:
+            t = actions_row
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.states.device
+                    and tuple(t.shape) == (self.B, 2) and t.is_contiguous()):
+                t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32).reshape(self.B, 2).contiguous()
+            self._override = t                       # (held until the next cycle)
+            ov = _ptr(t)
+        self._on_device(ov, None, 0)
+        return self.action
+
+    def run(self, cycles, actions=None):
+        """`cycles` cycles; returns the dict run_closed_loop returns (same keys, shapes and dtypes; states[0] = the poses at the
+        call).  `actions` [cycles, B, 2] as there.  The logs are allocated here, once; nothing is read back."""
+        B, T, dev = self.B, self.T, self.device
+        cycles = int(cycles)
+        hist = torch.empty((cycles + 1, B, 3), dtype=torch.float64, device=dev)
+        acts = torch.zeros((cycles, B, 2), dtype=torch.float32, device=dev)
+        stops = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
+        clrs = torch.full((cycles, B), float("inf"), dtype=torch.float64, device=dev)
+        ctrl = torch.zeros((cycles, B, 2, T), dtype=torch.float32, device=dev)
+        npt = torch.zeros((cycles, B), dtype=torch.int32, device=dev)
+        hist[0].copy_(self.states)
+        override, base = None, 0
+        if actions is not None:
+            override = torch.as_tensor(actions).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(override.shape) != (cycles, B, 2):
+                raise ValueError(f"actions must be [{cycles}, {B}, 2], not {list(override.shape)}")
+            base = override.data_ptr()
+        logs = (_ptr(acts), _ptr(stops), _ptr(ctrl), _ptr(npt), _ptr(hist), _ptr(clrs)) if cycles > 0 else None
+        for i in range(cycles):
+            self._on_device(C.c_void_p(base + i * B * 2 * 4) if override is not None else None, logs, i)
+        self._override = override                    # (held: the last launches may still read it)
+        out = dict(states=hist, actions=acts, arrive=self.arrived != 0, stop=stops, collided=self.collided != 0, clearance=clrs,
+                   controls=ctrl, n_points=npt)
+        if self.certify and cycles > 0:
+            out["plan_clearance"] = self.plan_clearance["clearance"].clone()
+        return out
