@@ -347,13 +347,27 @@ int npa_profile_read_aset(npa_handle *h, double *aset_ms_avg, int64_t *launches)
  *   curve_off[b] .. curve_off[b]+curve_len[b]-1; point_index [B] (closest_point's result,
  *   :160-181); interval [B] f64 (:56, :139).  The path is not modified (the reference writes
  *   2*pi-equivalent headings back into it, :111-112, :190-192).
+ *   The index increment: with fwd = ref_speed * step_time >= interval the reference adds
+ *   int(fwd / interval), a Python integer without an upper end, and any index past the curve's end
+ *   becomes the last point with gear 0 (:93-101).  Here the quotient is compared in double first: a
+ *   quotient >= curve_len - index, or one that is not finite (interval == 0), is that clamp, and only a
+ *   smaller one is converted to an integer.  So an interval as small as 1e-10, or the 0.0 an average over
+ *   a one-point path gives, is the last point with gear 0 and never an index outside the curve.
+ *   Preconditions the ABI cannot check, because the arrays live on the device: curve_len[b] >= 1,
+ *   0 <= point_index[b] < curve_len[b], rows curve_off[b] .. curve_off[b]+curve_len[b]-1 inside `path`,
+ *   interval[b] >= 0.  Outputs: scene b's rows of nom_s / ref_s [B][3][T+1], nom_u [B][2][T],
+ *   ref_us [B][T] and nothing else.
  *
  * npa_scan_to_points replaces neupan.scan_to_point (mode 0, neupan/neupan.py:173-222) and
  *   neupan.scan_to_point_velocity (mode 1, :224-281): range/angle filter, polar -> sensor frame ->
  *   robot frame -> world frame, ordered compaction, down-sampling of the kept list.
  *   ranges [B][beam_stride] f64, beam_vel [B][2][beam_stride] f64 or NULL, n_beams [B] or NULL
  *   (= beam_stride); points / velocities [B][2][out_stride] f32 (velocities may be NULL), count [B]
- *   (0 where the reference returns None).  Beams beyond out_stride kept points are dropped. */
+ *   (0 where the reference returns None).  Beams beyond out_stride kept points are dropped.
+ *   n_beams[b] is clamped to [0, beam_stride] (the rule of npa_world_scan, which a closed loop feeds from
+ *   the same array): a count of 0 or below gives count[b] = 0, a count above the stride is the scan of
+ *   beam_stride beams, and no read leaves scene b's rows.  velocities, when given, is filled in both
+ *   modes (zeros without beam_vel).  Columns at or beyond count[b] are not written. */
 typedef struct npa_scan_params {
   double angle_min, angle_max;   /* scan["angle_min"], scan["angle_max"]                         */
   double range_min, range_max;   /* scan["range_min"], scan["range_max"]                         */
@@ -374,7 +388,9 @@ int npa_nominal_ref_states(int batch, int receding, int kinematics, double step_
  *   point_index [B] is advanced to the closest of the next `ind_range` path points (first one closer than
  *   close_threshold wins), arrived [B] = 1 when the pose is within arrive_threshold of the curve's last
  *   point and point_index >= len - arrive_index_threshold - 2.  min_dis [B] f32 may be NULL.  Switching
- *   to the next curve / gear stays with the host. */
+ *   to the next curve / gear stays with the host.  The same device-side preconditions as above:
+ *   curve_len[b] >= 1 and 0 <= point_index[b] < curve_len[b] are not checked.  Ties go to the lower index; a distance
+ *   equal to close_threshold does not end the search, one equal to arrive_threshold has not arrived. */
 int npa_path_progress(int batch, const double *state, const double *path, const int32_t *curve_off,
                       const int32_t *curve_len, int32_t *point_index, double close_threshold, int ind_range,
                       double arrive_threshold, int arrive_index_threshold, float *min_dis, int32_t *arrived,
@@ -559,7 +575,14 @@ int npa_cycle_commit(int batch, int cycle, const double *state, const double *cl
  *   G [E][2], h [E]: HOST arrays (float64), consecutive counter-clockwise edges as
  *   gen_inequal_from_vertex produces them (util/__init__.py:161-206);
  *   points [n][2] f64 (device); mu [n][E] f32, dist [n] f32 (device; the reference stores float32
- *   tensors, dune_train.py:101-107). */
+ *   tensors, dune_train.py:101-107).
+ *   A point with max_e (G_e p - h_e) <= 0 (inside or on the polygon) gets zeros.  Outside, mu has one
+ *   entry (1/|G_e|, the nearest point inside edge e) or the two of the edges at the nearest vertex; where
+ *   the vertex solve does not give two positive entries (the point on the boundary of the vertex's normal
+ *   cone, or within rounding of the vertex) it is the one entry of the edge the direction leans to, so
+ *   |G^T mu| = 1 always.  NPA_E_ARG: G, h NULL, n < 0, a NULL array with n > 0; NPA_E_UNSUPPORTED:
+ *   edge_num outside [3, NPA_MAX_E]; NPA_E_HIP ("invalid argument", before any launch): parallel
+ *   consecutive rows or a zero row in G.  n == 0 returns NPA_OK without a launch. */
 int npa_dune_labels(int edge_num, const double *G, const double *h, int64_t n, const double *points,
                     float *mu, float *dist, void *stream);
 

@@ -54,7 +54,7 @@ __global__ void label_kernel(Polygon Q, long long n, const double* __restrict__ 
     if (bt > 0.0 && bt < 1.0) {                            // nearest point interior to edge be
       mu[be] = Q.inv_norm[be];
       dist = ((Q.G[be][0] * px + Q.G[be][1] * py) - Q.h[be]) * Q.inv_norm[be];
-    } else {                                               // a vertex: the two edges meeting there
+    } else if (best > 0.0) {                               // a vertex: the two edges meeting there
       const int i = bt == 0.0 ? (be == 0 ? E - 1 : be - 1) : be;
       const int j = bt == 0.0 ? be : (be + 1 == E ? 0 : be + 1);
       const double nx = (px - bqx) / dist, ny = (py - bqy) / dist;
@@ -62,9 +62,17 @@ __global__ void label_kernel(Polygon Q, long long n, const double* __restrict__ 
       const double a = Q.G[i][0], b = Q.G[j][0], c = Q.G[i][1], d = Q.G[j][1];
       const double det = a * d - b * c;
       const double mi = (nx * d - b * ny) / det, mj = (a * ny - nx * c) / det;
-      mu[i] = mi > 0.0 ? mi : 0.0;
-      mu[j] = mj > 0.0 ? mj : 0.0;
-    }
+      if (mi > 0.0 && mj > 0.0) {
+        mu[i] = mi;
+        mu[j] = mj;
+      } else {
+        // n is on or outside the normal cone of the vertex: exactly on its boundary, or the point is within rounding of the
+        // vertex and n is made of the last bits of q.  The dual point of the one edge n leans to is feasible (|G^T mu| = 1)
+        // whatever n is; a clamped (mi, mj) is not.
+        const int e = mi >= mj ? i : j;
+        mu[e] = Q.inv_norm[e];
+      }
+    }                                                      // (best == 0: outside by s, on the boundary by q: zeros)
   }
 #pragma unroll
   for (int e = 0; e < NPA_MAX_E; ++e)

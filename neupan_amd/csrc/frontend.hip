@@ -73,8 +73,12 @@ __global__ void nominal_kernel(int batch, int T, int kin, double dt, double L, c
 
     double gear = gear0;
     if (fwd >= itv) {                                                               // :93-101
-      ref_index = ref_index + (int)(fwd / itv);
-      if (ref_index > n - 1) { ref_index = n - 1; gear = 0.0; }
+      // The reference adds int(fwd / interval) as a Python integer, which has no upper end: decide in double whether
+      // the increment passes the curve's end (q >= n - ref_index <=> ref_index + int(q) > n - 1) and convert only a
+      // quotient that does not.  A quotient that is not finite (interval == 0) clamps as well.
+      const double q = fwd / itv;
+      if (!(q < (double)(n - ref_index))) { ref_index = n - 1; gear = 0.0; }
+      else ref_index = ref_index + (int)q;
       rx = cv[ref_index * 4 + 0]; ry = cv[ref_index * 4 + 1]; rth = cv[ref_index * 4 + 2];
     } else {                                                                        // :103-109, :183-207
       const double cx = rx, cy = ry;                 // circle centre: the previous reference point
@@ -156,7 +160,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(
   __shared__ int wave_tot[SCAN_THREADS / 64];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const npa_scan_params P = params[b];
-  const int n = n_beams ? n_beams[b] : beam_stride;
+  int n = n_beams ? n_beams[b] : beam_stride;
+  n = n < 0 ? 0 : (n > beam_stride ? beam_stride : n);      // the rule of world_scan_kernel: a scene's row is beam_stride wide
   const double* rg = ranges + (size_t)b * beam_stride;
   const double* bvx = beam_vel ? beam_vel + (size_t)b * 2 * beam_stride : nullptr;
   const double* bvy = bvx ? bvx + beam_stride : nullptr;

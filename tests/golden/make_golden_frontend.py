@@ -9,6 +9,8 @@
                         (neupan/neupan.py:173-281), called unbound (they do not touch `self`)
 
 * frontend_progress.npz `InitialPath.closest_point` + `check_curve_arrive` (initial_path.py:160-181, :279-287)
+* frontend_edges.npz    the same reference functions on the inputs of the decided tables of tests/frontend_cases.py (rollouts,
+                        path progress, scan filter); `--only-edges` writes this file alone
 * dune_train_losses.npz the loss terms of the reference's `DUNETrain.train_one_epoch` (dune_train.py:302-366)
 
 The reference functions execute unmodified (numpy 2.2 in this container: NEP-50 scalar promotion).
@@ -253,10 +255,56 @@ def run_pathbook():
     print("frontend_pathbook.npz:", len(names), "cases")
 
 
+def run_edges():
+    """frontend_edges.npz: what the unmodified reference answers on the decided tables of tests/frontend_cases.py.  Outputs only,
+    keyed by table and case name; the inputs are the tables' own (tests/test_frontend.py compares literal, oracle and this)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import frontend_cases as fc
+    out = {}
+    robot = types.SimpleNamespace(kinematics="diff", L=0.0, max_speed=[8.0, 1.0])
+    for c in fc.nominal_cases():
+        ip = InitialPath(c["T"], fc.DT_A, c["ref_speed"], robot)
+        ip.set_initial_path([row.reshape(4, 1).copy() for row in c["curve"]])
+        assert len(ip.curve_list) == 1
+        ip.interval, ip.point_index = c["interval"], c["point_index"]
+        vel = np.zeros((2, c["T"]), dtype=np.float32) if c["vel"] is None else c["vel"].copy()
+        nom_s, nom_u, ref_s, ref_us = ip.generate_nom_ref_state(c["state"].reshape(3, 1).copy(), vel, c["ref_speed"])
+        for key, val in (("nom_s", nom_s), ("nom_u", nom_u), ("ref_s", ref_s), ("ref_us", ref_us)):
+            out[f"nominal/{c['name']}/{key}"] = np.asarray(val, dtype=np.float64)
+    rows = []
+    for c in fc.progress_cases():
+        ip = InitialPath(10, 0.1, 4.0, robot)
+        ip.set_initial_path([row.reshape(4, 1).copy() for row in c["curve"]])
+        assert len(ip.curve_list) == 1
+        ip.point_index = c["point_index"]
+        st = c["state"].reshape(3, 1)
+        md = ip.closest_point(st, c["params"][0], c["params"][1])
+        arr = ip.check_curve_arrive(st, c["params"][2], c["params"][3])
+        rows.append([ip.point_index, md, float(bool(arr))])
+    out["progress/names"] = np.array([c["name"] for c in fc.progress_cases()])
+    out["progress/rows"] = np.array(rows, dtype=np.float64)
+    st = np.asarray(fc.SCAN_STATE, dtype=np.float64).reshape(3, 1)
+    for c in fc.filter_cases():
+        n = len(c["ranges"])
+        scan = dict(ranges=c["ranges"].tolist(), angle_min=c["angle_min"], angle_max=c["angle_max"], range_min=fc.RMIN_C,
+                    range_max=fc.RMAXP_C, velocity=np.stack([np.arange(n, dtype=np.float64), -np.arange(n, dtype=np.float64)]))
+        p = RefNeupan.scan_to_point(None, st, scan, list(fc.SCAN_OFFSET), list(c["angle_range"]), 1)
+        pv, vv = RefNeupan.scan_to_point_velocity(None, st, scan, list(fc.SCAN_OFFSET), list(c["angle_range"]), 1)
+        out[f"filter/{c['name']}/points"] = np.zeros((2, 0)) if p is None else np.asarray(p, dtype=np.float64)
+        out[f"filter/{c['name']}/points_v"] = np.zeros((2, 0)) if pv is None else np.asarray(pv, dtype=np.float64)
+        out[f"filter/{c['name']}/velocity_v"] = np.zeros((2, 0)) if vv is None else np.asarray(vv, dtype=np.float64)
+    np.savez_compressed(os.path.join(HERE, "frontend_edges.npz"), **out)
+    print("frontend_edges.npz:", len(out), "arrays")
+
+
 if __name__ == "__main__":
+    if "--only-edges" in sys.argv:
+        run_edges()
+        sys.exit(0)
     run_pathbook()
     if "--only-pathbook" in sys.argv:
         sys.exit(0)
+    run_edges()
     run_nominal()
     run_scan()
     run_progress()

@@ -89,6 +89,88 @@ def test_argument_validation_without_gpu(lib):
     assert lib.npa_workspace_bytes(None, 4) == 0 and lib.npa_destroy(None) == 0
 
 
+def test_frontend_and_label_argument_validation_without_gpu(lib):
+    """npa_nominal_ref_states, npa_path_progress, npa_scan_to_points, npa_dune_labels: every argument the header forbids is
+    refused with its code and a message before anything touches a device (the pointers here are never dereferenced)."""
+    from neupan_amd._lib import NPA_MAX_E
+    ARG, HIP, UNSUPPORTED = -1, -2, -3
+    P = C.c_void_p(0x1000)
+    MAX_T = int(re.search(r"#define NPA_MAX_T (\d+)", open(os.path.join(ROOT, "include", "neupan_amd.h")).read()).group(1))
+
+    def refused(rc, code, word):
+        assert rc == code, (rc, code, word)
+        msg = lib.npa_last_error()
+        assert msg and word in msg, msg
+
+    # ---- npa_nominal_ref_states(batch, receding, kinematics, step_time, wheelbase, state, cur_vel, ref_speed, path, curve_off,
+    #      curve_len, point_index, interval, nom_s, nom_u, ref_s, ref_us, stream)
+    def nominal(batch=4, T=10, kin=0, L=0.0, null=None):
+        ptr = [P] * 12
+        if null is not None:
+            ptr[null] = None
+        return lib.npa_nominal_ref_states(batch, T, kin, 0.1, L, *ptr, None)
+
+    for k in range(12):
+        if k == 1:
+            continue                                          # cur_vel may be NULL (zeros): not a validation error
+        refused(nominal(null=k), ARG, b"npa_nominal_ref_states")
+    refused(nominal(batch=0), ARG, b"npa_nominal_ref_states")
+    refused(nominal(batch=-3), ARG, b"npa_nominal_ref_states")
+    refused(nominal(T=0), UNSUPPORTED, b"receding")
+    refused(nominal(T=MAX_T + 1), UNSUPPORTED, b"receding")
+    refused(nominal(kin=3), ARG, b"kinematics")
+    refused(nominal(kin=-1), ARG, b"kinematics")
+    refused(nominal(kin=1, L=0.0), ARG, b"wheelbase")
+    refused(nominal(kin=1, L=-2.0), ARG, b"wheelbase")
+    refused(nominal(kin=1, L=float("nan")), ARG, b"wheelbase")
+
+    # ---- npa_path_progress(batch, state, path, curve_off, curve_len, point_index, close_threshold, ind_range, arrive_threshold,
+    #      arrive_index_threshold, min_dis, arrived, stream)
+    def progress(batch=4, ind_range=10, null=None, arrived=P):
+        ptr = [P] * 5
+        if null is not None:
+            ptr[null] = None
+        return lib.npa_path_progress(batch, *ptr, 0.1, ind_range, 0.1, 1, None, arrived, None)       # (min_dis may be NULL)
+
+    for k in range(5):
+        refused(progress(null=k), ARG, b"npa_path_progress")
+    refused(progress(arrived=None), ARG, b"npa_path_progress")
+    refused(progress(batch=0), ARG, b"npa_path_progress")
+    refused(progress(ind_range=0), ARG, b"npa_path_progress")
+    refused(progress(ind_range=-1), ARG, b"npa_path_progress")
+
+    # ---- npa_scan_to_points(batch, beam_stride, ranges, beam_vel, n_beams, params, mode, out_stride, points, velocities, count, stream)
+    def scan(batch=4, beam_stride=360, ranges=P, params=P, mode=0, out_stride=360, points=P, count=P):
+        return lib.npa_scan_to_points(batch, beam_stride, ranges, None, None, params, mode, out_stride, points, None, count, None)
+
+    for kw in (dict(ranges=None), dict(params=None), dict(points=None), dict(count=None), dict(batch=0), dict(beam_stride=0),
+               dict(out_stride=0), dict(out_stride=-1)):
+        refused(scan(**kw), ARG, b"npa_scan_to_points")
+    refused(scan(mode=2), ARG, b"mode")
+    refused(scan(mode=-1), ARG, b"mode")
+
+    # ---- npa_dune_labels(edge_num, G, h, n, points, mu, dist, stream): G and h are HOST arrays and are read
+    G = np.array([[0, -1.6], [2, 0], [0, 1.6], [-2, 0]], dtype=np.float64)
+    h = np.full(4, 1.6)
+    gp, hp = G.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p)
+    refused(lib.npa_dune_labels(4, None, hp, 8, P, P, P, None), ARG, b"npa_dune_labels")
+    refused(lib.npa_dune_labels(4, gp, None, 8, P, P, P, None), ARG, b"npa_dune_labels")
+    refused(lib.npa_dune_labels(4, gp, hp, -1, P, P, P, None), ARG, b"npa_dune_labels")
+    refused(lib.npa_dune_labels(4, gp, hp, 8, None, P, P, None), ARG, b"npa_dune_labels")
+    refused(lib.npa_dune_labels(4, gp, hp, 8, P, None, P, None), ARG, b"npa_dune_labels")
+    refused(lib.npa_dune_labels(4, gp, hp, 8, P, P, None, None), ARG, b"npa_dune_labels")
+    refused(lib.npa_dune_labels(2, gp, hp, 8, P, P, P, None), UNSUPPORTED, b"edge_num")
+    refused(lib.npa_dune_labels(NPA_MAX_E + 1, gp, hp, 8, P, P, P, None), UNSUPPORTED, b"edge_num")
+    # parallel consecutive edges (a degenerate quadrilateral: rows 1 and 2 are parallel) and a zero row: the launcher refuses them
+    # on the host, before any launch
+    Gp = np.array([[0, -1.6], [2, 0], [4, 0], [-2, 0]], dtype=np.float64)
+    refused(lib.npa_dune_labels(4, Gp.ctypes.data_as(C.c_void_p), hp, 8, P, P, P, None), HIP, b"npa_launch_labels")
+    Gz = np.array([[0, -1.6], [2, 0], [0, 0], [-2, 0]], dtype=np.float64)
+    refused(lib.npa_dune_labels(4, Gz.ctypes.data_as(C.c_void_p), hp, 8, P, P, P, None), HIP, b"npa_launch_labels")
+    # n == 0 with a sound polygon: nothing to do, no launch, no pointers needed
+    assert lib.npa_dune_labels(4, gp, hp, 0, None, None, None, None) == 0
+
+
 def test_qp_scene_block_fits_the_residency_the_design_counts_on(lib):
     """LDS per scene of the QP kernel (the launcher's own size function): 8 scenes per CU at (T, M) = (10, 10) -- the
     block is what limits how many solves a CU holds --, 4 at T = 20 (one wave per SIMD; round 5's 51 KB block

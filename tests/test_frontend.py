@@ -7,10 +7,12 @@ Tolerances: the reference computes in float64 and casts to float32 at the PAN bo
 (neupan.py:121).  The oracle must agree to 1e-12 (same operations; only libm/BLAS rounding may
 differ); the HIP path emits float32 and must agree to 1 float32 ulp of the value's magnitude."""
 import os
+import re
 
 import numpy as np
 import pytest
 
+import frontend_cases as fc
 from oracle import frontend_oracle as fo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -257,3 +259,184 @@ def test_path_bookkeeping_matches_reference():
         assert FleetPlanner._average_interval(path) == float(g[name + "/interval"]), name
         _consistent_angles(path)
         assert np.array_equal(np.hstack(path).T, g[name + "/consistent"]), name
+
+
+# ------------------------------------------------- the decided tables of tests/frontend_cases.py, guarded on the CPU
+# literal == oracle == the recorded reference (frontend_edges.npz), bit for bit, and every case takes the branch it is named for.
+# tests/test_frontend_edges_gpu.py runs the kernels against these tables.
+EDGES = np.load(os.path.join(HERE, "golden", "frontend_edges.npz"))
+A_TABLE, B_TABLE, C_TABLE = fc.nominal_cases(), fc.progress_cases(), fc.filter_cases()
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def test_tables_hold_every_named_case():
+    assert [c["name"] for c in A_TABLE] == fc.NOMINAL_NAMES
+    assert [c["name"] for c in B_TABLE] == fc.PROGRESS_NAMES and list(EDGES["progress/names"]) == fc.PROGRESS_NAMES
+    assert [c["name"] for c in C_TABLE] == fc.FILTER_NAMES
+    assert all(c["promise"] for c in A_TABLE + B_TABLE + C_TABLE)
+    assert fc.REPLICATED_CASE in fc.NOMINAL_NAMES and set(fc.HORIZON_CASES) <= set(fc.NOMINAL_NAMES)
+    assert {T for T, _, _ in fc.HORIZON_RUNS} == {1, fc.NPA_MAX_T} and {k for _, k, _ in fc.HORIZON_RUNS} == {"diff", "acker", "omni"}
+    hdr = open(os.path.join(os.path.dirname(HERE), "include", "neupan_amd.h")).read()
+    assert re.search(rf"#define NPA_MAX_T {fc.NPA_MAX_T}\b", hdr)
+
+
+@pytest.mark.parametrize("c", A_TABLE, ids=fc.NOMINAL_NAMES)
+def test_nominal_table_literal_oracle_reference(c):
+    """bit for bit in float64: the literals of the table, the oracle, the unmodified reference; and the branch is reached"""
+    nom_s, nom_u, ref_s, ref_us = fc.oracle_nominal(c)
+    assert same_bits(nom_s, c["nom_s"]) and same_bits(ref_s, c["ref_s"]) and same_bits(ref_us, c["ref_us"]), (nom_s, ref_s, ref_us)
+    key = "nominal/" + c["name"]
+    assert same_bits(EDGES[key + "/nom_s"], c["nom_s"]) and same_bits(EDGES[key + "/ref_s"], c["ref_s"])
+    assert same_bits(EDGES[key + "/ref_us"], c["ref_us"])
+    if c["vel"] is not None:
+        assert np.array_equal(EDGES[key + "/nom_u"], c["vel"])
+    steps, xy = fc.nominal_trace(c)
+    assert same_bits(np.array(xy).T, c["ref_s"][:2])
+    assert c["reach"](steps), steps
+    # every finite input is a multiple of 2^-10 (headings apart): the products and sums of the rollout are exact
+    fin = c["curve"][:, :2][np.isfinite(c["curve"][:, :2])]
+    assert (fin * 1024 == np.round(fin * 1024)).all() and (c["state"] * 1024 == np.round(c["state"] * 1024)).all()
+
+
+def test_index_increment_rule_is_the_references_for_every_quotient():
+    """The kernel decides in double: q >= n - ref_index (or q not finite) clamps with gear 0, otherwise ref_index + (int)q.  This
+    is Python's unbounded int(q) followed by `ref_index > n - 1` for every finite q >= 0; converting first is not: above 2^31
+    the conversion saturates and the sum wraps to a negative index (the interval_1e-10 case is such a quotient)."""
+    def rule(q, n, k):
+        return (n - 1, True) if not (q < n - k) else (k + int(q), False)
+
+    def reference(q, n, k):
+        k = k + int(q)
+        return (n - 1, True) if k > n - 1 else (k, False)
+
+    def int32_first(q, n, k):
+        k = k + min(int(q), 2 ** 31 - 1)
+        k = (k + 2 ** 31) % 2 ** 32 - 2 ** 31                    # the int sum wraps
+        return (n - 1, True) if k > n - 1 else (k, False)
+
+    qs = [0.0, 0.5, 1.0, float(np.nextafter(2.0, 0)), 2.0, 4.0, 5.0, 5.999999, 6.0, 250000.0, 2.0 ** 31 - 1, 2.0 ** 31, 2.5e9, 1e300]
+    for n, k in ((6, 0), (6, 1), (6, 5), (1, 0), (2, 0)):
+        for q in qs:
+            assert rule(q, n, k) == reference(q, n, k), (q, n, k)
+    assert rule(float("inf"), 6, 1) == (5, True) and rule(float("nan"), 6, 1) == (5, True)
+    c = A_TABLE[fc.NOMINAL_NAMES.index("interval_1e-10")]
+    q = c["ref_speed"] * fc.DT_A / c["interval"]
+    assert int32_first(q, len(c["curve"]), c["point_index"])[0] < 0 and reference(q, len(c["curve"]), c["point_index"]) == (5, True)
+
+
+def test_nominal_batch_layouts_of_the_table():
+    """the three batch layouts the GPU test runs: offsets and lengths address the same rows, the gaps are NaN"""
+    for gap in (0, 3):
+        path, off, ln = fc.pack_curves(A_TABLE, gap=gap)
+        for c, o, n in zip(A_TABLE, off, ln):
+            assert same_bits(path[o:o + n], c["curve"])
+            assert gap == 0 or np.isnan(path[o - gap:o]).all()
+    order = fc.replicated_order(len(A_TABLE), fc.NOMINAL_NAMES.index(fc.REPLICATED_CASE))
+    assert len(order) == fc.REPLICATED_B == 130 and set(order) == set(range(len(A_TABLE)))
+    assert all(A_TABLE[order[b]]["name"] == fc.REPLICATED_CASE for b in fc.REPLICATED_AT) and fc.REPLICATED_AT == (0, 63, 64, 129)
+
+
+def test_horizon_references_of_the_table():
+    """the oracle's answer for every run of the shortest and the longest horizon the device test makes: finite, of the right shape"""
+    for T, kin, L in fc.HORIZON_RUNS:
+        for k, name in enumerate(fc.HORIZON_CASES):
+            c = A_TABLE[fc.NOMINAL_NAMES.index(name)]
+            vel = fc.horizon_velocities(T, seed=k)
+            nom_s, nom_u, ref_s, ref_us = fc.oracle_nominal(c, T=T, kin=kin, L=L, vel=vel)
+            assert nom_s.shape == ref_s.shape == (3, T + 1) and ref_us.shape == (T,) and vel.shape == (2, T) and vel.dtype == np.float32
+            assert np.isfinite(nom_s).all() and np.isfinite(ref_s).all() and (np.abs(nom_s[:2] - c["state"][:2, None]) > 0).any()
+
+
+@pytest.mark.parametrize("c", B_TABLE, ids=fc.PROGRESS_NAMES)
+def test_progress_table_literal_oracle_reference(c):
+    idx, md, arr = fo.path_progress(c["curve"], c["point_index"], c["state"], *c["params"])
+    assert (idx, int(arr)) == (c["want"][0], c["want"][2]) and same_bits(md, c["want"][1]), (idx, md, arr)
+    r = EDGES["progress/rows"][fc.PROGRESS_NAMES.index(c["name"])]
+    assert (int(r[0]), int(r[2])) == (c["want"][0], c["want"][2]) and same_bits(r[1], c["want"][1]), r
+    dists, seen = fc.progress_trace(c)
+    assert c["reach"](dists, seen), (dists, seen)
+    assert dict(dists)[c["want"][0]] == c["want"][1] and c["want"][1] * 2 ** 12 == round(c["want"][1] * 2 ** 12)     # exact
+
+
+def test_progress_table_reaches_the_arrival_boundaries():
+    by = {c["name"]: c for c in B_TABLE}
+    c = by["arrive_distance_equals_threshold"]
+    assert float(np.hypot(*(c["curve"][-1, :2] - c["state"][:2]))) == c["params"][2] and c["want"][2] == 0
+    c = by["arrive_index_at_bound"]
+    assert c["want"][0] == len(c["curve"]) - c["params"][3] - 2 and c["want"][2] == 1
+    c = by["arrive_index_below_bound"]
+    assert c["want"][0] == len(c["curve"]) - c["params"][3] - 3 and c["want"][2] == 0
+    c = by["arrive_index_threshold_above_n"]
+    assert c["params"][3] > len(c["curve"]) and c["want"][2] == 1
+    assert len(by["one_point_curve"]["curve"]) == 1
+
+
+def test_progress_ragged_generator():
+    D = fc.progress_ragged()
+    assert len(D["curves"]) == fc.PROGRESS_RAGGED_B == 130
+    assert D["len"].min() == 1 and D["len"].max() == 60 and (D["pidx"] < D["len"]).all() and (D["pidx"] >= 0).all()
+    for b in (0, 64, 129):
+        assert same_bits(D["path"][D["off"][b]:D["off"][b] + D["len"][b]], D["curves"][b]) and np.isnan(D["path"][D["off"][b] - 3:D["off"][b]]).all()
+    got = [fo.path_progress(D["curves"][b], D["pidx"][b], D["states"][b], *fc.PROGRESS_RAGGED_PARAMS) for b in range(130)]
+    assert 10 <= sum(g[2] for g in got) <= 120 and len({g[0] - k for g, k in zip(got, D["pidx"])}) >= 5      # both answers, many advances
+
+
+@pytest.mark.parametrize("c", C_TABLE, ids=fc.FILTER_NAMES)
+def test_filter_table_literal_oracle_reference(c):
+    """which beams are kept: the table's literals, the oracle's two functions, the unmodified reference's two functions"""
+    key = "filter/" + c["name"]
+    for mode, want in ((0, c["kept0"]), (1, c["kept1"])):
+        pts, kept = fc.oracle_scan(mode, c)
+        assert list(kept) == want
+        ref = EDGES[key + ("/points" if mode == 0 else "/points_v")]
+        assert ref.shape == pts.shape == (2, len(want))
+        assert len(want) == 0 or np.abs(ref - pts).max() <= 1e-12 * max(1.0, np.abs(ref).max())
+    assert list(EDGES[key + "/velocity_v"][0]) == c["kept1"]
+
+
+def test_filter_table_sits_on_the_comparisons():
+    by = {c["name"]: c for c in C_TABLE}
+    assert by["range_at_range_min"]["ranges"][4] == fc.RMIN_C and by["range_at_upper_bound"]["ranges"][4] == fc.RMAXP_C - 0.02
+    assert by["range_below_upper_bound"]["ranges"][4] == np.nextafter(fc.RMAXP_C - 0.02, 0)
+    assert by["range_at_range_min"]["kept0"] != by["range_at_range_min"]["kept1"]                 # the one value the two modes part on
+    c = by["angle_at_lower_bound"]
+    assert fc.linspace_angle(c["angle_min"], c["angle_max"], 9, 3) == c["angle_range"][0]
+    c = by["angle_at_upper_bound"]
+    assert fc.linspace_angle(c["angle_min"], c["angle_max"], 9, 6) == c["angle_range"][1]
+    c = by["last_beam_at_upper_bound"]
+    assert c["angle_max"] == c["angle_range"][1] and 8 not in c["kept0"]
+
+
+def test_compaction_truncation_and_count_generators():
+    S = fc.compaction_scans()
+    assert {s["n"] for s in S} == {1, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1025} and max(s["n"] for s in S) <= fc.COMPACTION_STRIDE
+    seen = set()
+    for s in S:
+        assert s["down_sample"] == (int(s["mask"].sum()) + 1 if s["ds_kind"] == "kept+1" else s["ds_kind"])
+        seen.add((s["pattern"], s["ds_kind"]))
+        for mode in (0, 1):
+            _, idx = fc.oracle_scan(mode, s, n=s["n"])
+            assert list(idx) == list(np.flatnonzero(s["mask"])[::s["down_sample"]])                 # the oracle keeps exactly the mask
+    assert {p for p, _ in seen} == set(fc.COMPACTION_PATTERNS)
+    for p in ("all", "lane63", "thread0", "second", "random"):
+        assert {k for q, k in seen if q == p} >= {1, 2, 3, 7, "kept+1"}, (p, seen)
+    lane63 = [s for s in S if s["pattern"] == "lane63" and s["n"] == 513][0]
+    assert list(np.flatnonzero(lane63["mask"])) == list(range(63, 513, 64))
+    Tr = fc.truncation_scans()
+    assert len(Tr) == 8 and Tr[0]["down_sample"] == 3 and int(Tr[0]["mask"].sum()) > 30
+    assert fc.COUNT_USED == tuple(int(np.clip(n, 0, fc.COUNT_STRIDE)) for n in fc.COUNT_N_BEAMS)           # the clamp of the header
+    assert fc.COUNT_N_BEAMS[-1] == fc.COUNT_STRIDE and max(fc.COUNT_N_BEAMS[:-1]) > fc.COUNT_STRIDE and min(fc.COUNT_N_BEAMS) < 0
+    Cn = fc.count_scans()
+    assert len(Cn) == len(fc.COUNT_N_BEAMS)
+    for s, used in zip(Cn, fc.COUNT_USED):                  # the reference of every scene of the launch, as the device test asks for it
+        for mode in (0, 1):
+            pts, idx = fc.oracle_scan(mode, s, n=used)
+            assert pts.shape == (2, len(idx)) and (len(idx) > 0) == (used > 0)
+            assert list(idx) == [i for i in np.flatnonzero(s["mask"][:used]) if -2.5 < fc.linspace_angle(-3.0, 3.0, used, i) < 2.75][::s["down_sample"]]
+    for s in fc.truncation_scans():
+        for mode in (0, 1):
+            assert list(fc.oracle_scan(mode, s, n=s["n"])[1]) == list(np.flatnonzero(s["mask"])[::s["down_sample"]])
