@@ -567,6 +567,75 @@ int npa_cycle_act(int batch, int receding, int kinematics, int first_cycle, int 
 int npa_cycle_commit(int batch, int cycle, const double *state, const double *clearance, int32_t *collided,
                      double *log_states, double *log_clearance, void *stream);
 
+/* ---- training the adjust parameters inside the resident loop (csrc/lon.hip) ------------------------------------------
+ *
+ * The reference's LON examples (example/LON/LON_corridor.py) tune p_u, eta, d_max by driving a robot through a world: per
+ * cycle a loss on info["distance_tensor"], its gradient through the QP, an Adam step; the episode ends on arrive, stop or
+ * stuck.  These three calls are the host's part of that loop for B robots with one parameter row each, handle-free and
+ * stream-ordered like the cycle calls: one thread per robot, no workspace, no atomics, no device-side counter, nothing
+ * allocated, no host synchronisation.  Every arithmetic statement is one IEEE operation in the order given here (no
+ * contraction), so numpy restates them bit for bit.  One training cycle on one stream:
+ *     npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states
+ *     -> npa_forward_begin, K x { copy cur_s, cur_u; npa_forward_iter(k); copy the mu / lam / pts / count rows }, npa_forward_end
+ *     -> npa_cycle_act (override_row = the override buffer below) -> npa_world_step -> npa_cycle_commit
+ *     -> npa_lon_loss -> for k = K-1 .. first: npa_nrmp_backward(the copies of k, grad_s, grad_u, grad_d) -> npa_lon_chain(k)
+ *     -> npa_lon_adam
+ * Parameter-shaped arrays are rows of 8 like npa_set_adjust_batch's theta: q_s[0..2], p_u, eta, d_max, d_min, reserved;
+ * column 7 is never read or written here (npa_lon_chain reads the status that npa_nrmp_backward puts there).
+ *
+ * npa_lon_loss replaces LON_corridor.py:10-19 (cal_distance_loss), :62-82 (the stuck test, loss = 10 * distance_loss) and
+ *   :102 (the end of the episode); it runs behind npa_cycle_commit.  Inputs per robot: state [B][3] f64 (after the step),
+ *   last_xy [B][2] f64 (in / out: the position at the previous call; the caller initialises it to the start), opt_d [B][T],
+ *   min_distance [B] f32, stop [B] uint8 (npa_cycle_act's), arrived / collided [B] int32 (the latches), stuck_count and
+ *   ended [B] int32 (in / out, the caller zeroes them when an episode starts).
+ *   A robot with ended[b] != 0 at the call: active[b] = 0, loss 0, grad_d 0, stuck_count and ended unchanged.
+ *   Otherwise active[b] = 1 and: disp = sqrt(dx*dx + dy*dy) in f64; stuck_count += disp < stuck_threshold (cumulative over
+ *   the episode, as in the example); stuck = stuck_count > stuck_patience; S = ((0 + opt_d[b][0]) + opt_d[b][1]) + ... in f32;
+ *   min_distance[b] <= collision_threshold (f32): loss = loss_weight * (loss_offset - S), grad_d[b][t] = -loss_weight; else
+ *   stuck: loss = loss_weight * (loss_offset + S), grad_d[b][t] = +loss_weight; else loss 0, grad_d 0.  Then
+ *   ended[b] |= arrived | collided | stop | stuck.
+ *   For every robot: loss [B] f32; grad_s [B][3][T+1] and grad_u [B][2][T] are written as zeros (with grad_d [B][T] the
+ *   upstream gradients of the first npa_nrmp_backward); a robot whose ended flag is set after the call gets (0, 0) in its row
+ *   of override_row [B][2] f32 -- the buffer the NEXT npa_cycle_act takes as its override_row; the other rows keep what the
+ *   caller put there (NaN: the planner's action) --; last_xy = state[0:2]; row `cycle` of the logs (each nullable): log_loss
+ *   [cycles][B] f32, log_stuck [cycles][B] uint8 (the stuck test; for an ended robot, of its unchanged count), log_ended
+ *   [cycles][B] uint8 (ended after the call).
+ *
+ * npa_lon_chain is the step between two npa_nrmp_backward calls, run after the one that re-solved PAN iteration k.  For a robot
+ *   with iters[b] > k (it executed iteration k): tot[b][c] += (double) grad_theta[b][c], c = 0 .. 6 (tot [B][8] f64);
+ *   grad_s[b] <- grad_nom_s[b]; grad_u[b] <- 0; grad_d[b] <- 0; bad[b] += grad_theta[b][7] != 0 (the solver status).  Other
+ *   robots are untouched: their upstream gradients wait for an earlier iteration.
+ *
+ * npa_lon_adam replaces torch.optim.Adam.step and opt.zero_grad (LON_corridor.py:41, :94-95, :127), one thread per row.
+ *   For c = 0 .. 6: g32 = (float) tot[b][c]; gacc[b][c] = accumulate ? gacc[b][c] + g32 : g32 (the reference clears the
+ *   gradients once per episode, so a caller that follows it accumulates and zeroes gacc between episodes); tot[b][c] = 0.
+ *   Then, when active[b] != 0 and gacc[b][c] is finite for every c in column_mask (bit c = column c), for every c in the mask,
+ *   each line one rounded f32 operation per operator, left to right:
+ *       m = beta1 * m + one_minus_beta1 * g            v = beta2 * v + (one_minus_beta2 * g) * g
+ *       denom = sqrtf(v) / bc2_sqrt + eps               theta = theta - step_size * (m / denom)
+ *       theta = fminf(fmaxf(theta, lo[c]), hi[c])                 (sqrtf and / correctly rounded, as numpy's are)
+ *   with g = gacc[b][c]; m, v, theta [B][8] f32 (theta: the block npa_set_adjust_batch registered, rewritten in place).  An
+ *   active row with a non-finite masked entry is not stepped and skipped[b] += 1; a row that is not active is not stepped.
+ *   The scalars travel by value, computed by the host in double as torch computes them: one_minus_beta = 1 - beta,
+ *   step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), t = 1, 2, ... the step count; lo / hi: HOST arrays of 8 f32
+ *   (null: -inf / +inf), copied into the launch.
+ *
+ * NPA_E_ARG (before anything touches a device): a null required pointer, batch < 1, cycle < 0, k < 0, receding outside
+ *   [1, NPA_MAX_T], a column_mask with bits above 6. */
+int npa_lon_loss(int batch, int receding, int cycle, const double *state, double *last_xy, const float *opt_d,
+                 const float *min_distance, const uint8_t *stop, const int32_t *arrived, const int32_t *collided,
+                 float collision_threshold, double stuck_threshold, int stuck_patience, float loss_weight,
+                 float loss_offset, int32_t *stuck_count, int32_t *ended, int32_t *active, float *loss,
+                 float *grad_s, float *grad_u, float *grad_d, float *override_row, float *log_loss,
+                 uint8_t *log_stuck, uint8_t *log_ended, void *stream);
+int npa_lon_chain(int batch, int receding, int k, const int32_t *iters, const float *grad_theta,
+                  const float *grad_nom_s, double *tot, float *grad_s, float *grad_u, float *grad_d, int32_t *bad,
+                  void *stream);
+int npa_lon_adam(int batch, int column_mask, int accumulate, double *tot, float *gacc, float *m, float *v,
+                 float *theta, const int32_t *active, float beta1, float one_minus_beta1, float beta2,
+                 float one_minus_beta2, float step_size, float bc2_sqrt, float eps, const float *lo, const float *hi,
+                 int32_t *skipped, void *stream);
+
 /* ---- DUNE training labels (offline) ---------------------------------------------------------------
  * npa_dune_labels replaces DUNETrain.prob_solve / generate_data_set
  *   (neupan/blocks/dune_train.py:82-99, :109-140): for every point p the maximiser mu of

@@ -11,7 +11,8 @@ _LAZY = {"PAN": ("pan", "PAN"), "forward_interleaved": ("pan", "forward_interlea
          "scan_to_point_batch": ("frontend", "scan_to_point_batch"),
          "scan_to_point_velocity_batch": ("frontend", "scan_to_point_velocity_batch"),
          "DuneTrain": ("dune_train", "DuneTrain"), "neupan": ("planner", "neupan"),
-         "InputPipeline": ("ingest", "InputPipeline")}      # (dune_labels.dune_labels: import it from its module)
+         "InputPipeline": ("ingest", "InputPipeline"), "LonLoop": ("lon", "LonLoop"),
+         "train_closed_loop": ("lon", "train_closed_loop"), "lon_loss": ("lon", "lon_loss"), "lon_adam": ("lon", "lon_adam")}      # (dune_labels.dune_labels: import it from its module)
 
 
 def __getattr__(name):

@@ -86,6 +86,9 @@ SYMBOLS = {
     "npa_cycle_progress": (_I, [_I, _P, _P, _P, _P, _P, _I, C.c_double, _I, C.c_double, _I] + [_P] * 8 + [_P]),
     "npa_cycle_act": (_I, [_I, _I, _I, _I, _I, _P, _P, C.c_float] + [_P] * 12 + [_P]),
     "npa_cycle_commit": (_I, [_I, _I, _P, _P, _P, _P, _P, _P]),
+    "npa_lon_loss": (_I, [_I, _I, _I] + [_P] * 7 + [C.c_float, C.c_double, _I, C.c_float, C.c_float] + [_P] * 11 + [_P]),
+    "npa_lon_chain": (_I, [_I, _I, _I] + [_P] * 8 + [_P]),
+    "npa_lon_adam": (_I, [_I, _I, _I] + [_P] * 6 + [C.c_float] * 7 + [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
     "npa_dune_labels": (_I, [_I, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "npa_profile_enable": (_I, [_P, _I]),
     "npa_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

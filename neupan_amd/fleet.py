@@ -84,14 +84,17 @@ class FleetPlanner:
         self.nb.set_curves([cl[i] for cl, i in zip(self.curve_lists, self.curve_index)], self.intervals, point_index)
 
     # ------------------------------------------------------------------ one control cycle
-    def forward(self, states, points=None, velocities=None, n_points=None, certify=False):
+    def forward(self, states, points=None, velocities=None, n_points=None, certify=False, adjust=None):
         """states [B,3]; points [B,2,N] float32 (global frame) with optional n_points [B] / velocities [B,2,N].
         Returns (action [B,2] float32 device tensor, info dict).
         certify=True (with points): one more launch behind the plan measures opt_s against the cycle's WHOLE cloud, velocities
         included (PAN.plan_clearance, threshold = collision_threshold), and adds info["clearance"] (B,T+1), info["nearest"]
         (B,T+1), info["unsafe_step"] (B,): the first step closer than the threshold, -1 if none, and info["collision"] (B,):
         clearance[:, 0] <= 0, the polygon at the robot's current pose touches or contains a point (the reference declares the
-        key, neupan.py:86, and never sets it).  Neither the action nor `stop` depends on it."""
+        key, neupan.py:86, and never sets it).  Neither the action nor `stop` depends on it.
+        adjust: a (B, 7) or (B, 8) float32 device tensor of per-robot parameters, usually a `requires_grad` leaf: robot b is planned
+        with row b and the plan in `info` stays connected to it (PAN.forward_batch_grad(adjust=...)), so a loss on info["opt_d"]
+        fills `adjust.grad` with one row per robot -- the host-paced form of neupan_amd.lon.LonLoop."""
         B, dev = self.B, self.device
         st = np.asarray(states.cpu() if isinstance(states, torch.Tensor) else states, dtype=np.float64).reshape(B, -1)[:, :3]
         # 1. progress along the path, arrival (host bookkeeping only when a curve ends)
@@ -114,7 +117,10 @@ class FleetPlanner:
         # 2. nominal / reference states from the previous plan
         nom_s, nom_u, ref_s, ref_us = self.nb.generate_nom_ref_state(st, self.cur_vel, self.ref_speed)
         # 3. PAN
-        if any(p.requires_grad for p in self.pan.nrmp_layer.adjust_parameters):
+        if adjust is not None:
+            gs, gu, gd = self.pan.forward_batch_grad(nom_s, nom_u, ref_s, ref_us, points, velocities, n_points, adjust=adjust)
+            out = dict(self.pan.last_out, opt_s=gs, opt_u=gu, opt_d=None if self.pan.no_obs else gd)
+        elif any(p.requires_grad for p in self.pan.nrmp_layer.adjust_parameters):
             # LON use (example/LON/LON_corridor.py:94-127): the plan stays connected to the adjust parameters
             gs, gu, gd = self.pan.forward_batch_grad(nom_s, nom_u, ref_s, ref_us, points, velocities, n_points)
             out = dict(self.pan.last_out, opt_s=gs, opt_u=gu, opt_d=None if self.pan.no_obs else gd)

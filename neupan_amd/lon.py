@@ -1,0 +1,449 @@
+"""Training the NRMP adjust parameters in a closed loop -- the reference's example/LON/LON_corridor*.py for B robots with one
+parameter row each: a population of B tuners trained side by side.
+
+Per cycle the example plans, steps its simulator, computes a loss on info["distance_tensor"] (50 - sum d when the planner's
+min_distance is at or below the collision threshold, 50 + sum d when the robot is stuck, times 10), differentiates it through the
+QP and takes an Adam step; the episode ends on arrive, stop or stuck.  Here:
+
+* `LonLoop`            that cycle as a fixed launch sequence over buffers allocated once, with no host synchronisation:
+
+      npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states
+      -> npa_forward_begin, K x { copy cur_s, cur_u into snapshot k; npa_forward_iter(k); copy the mu / lam / pts / count rows
+         into snapshot k }, npa_forward_end
+      -> npa_cycle_act (override_row = the loop's override buffer) -> npa_world_step -> npa_cycle_commit
+      -> npa_lon_loss
+      -> for k = K-1 .. first: npa_nrmp_backward(snapshot k, gs, gu, gd) -> npa_lon_chain(k)
+      -> npa_lon_adam(t)
+
+* `train_closed_loop`  the same cycle paced by the host: FleetPlanner.forward(adjust=theta) -> the loss as torch operations ->
+                       backward() into theta.grad -> the Adam step; it is to `LonLoop` what `run_closed_loop` is to `ResidentLoop`.
+* `lon_loss`, `lon_adam`  thin wrappers of the two exports both loops share.
+
+The rules (csrc/lon.hip, include/neupan_amd.h) are stated as single IEEE operations in a fixed order, so the two loops give the
+same bits.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from math import inf, nan, pi, sqrt
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import NeupanAmdError, check
+from .frontend import _ptr, scan_to_point_batch, scan_to_point_velocity_batch
+from .world import ResidentLoop, robot_vertices
+
+COLUMNS = ("q_s0", "q_s1", "q_s2", "p_u", "eta", "d_max", "d_min")      # the columns of a parameter row (the eighth is reserved)
+
+
+def column_mask(train):
+    """Names ("q_s" = its three columns, "p_u", "eta", "d_max", "d_min", or a column's own name) or column indices -> bit mask"""
+    mask = 0
+    for name in train:
+        if isinstance(name, (int, np.integer)):
+            if not 0 <= int(name) <= 6:
+                raise ValueError(f"column {name} is outside 0 .. 6")
+            mask |= 1 << int(name)
+        elif name == "q_s":
+            mask |= 0b111
+        elif name in COLUMNS:
+            mask |= 1 << COLUMNS.index(name)
+        else:
+            raise ValueError(f"{name!r} is not an adjust parameter (q_s, {', '.join(COLUMNS)})")
+    return mask
+
+
+def adjust_block(theta0, B, device):
+    """(B, 7) or (B, 8) parameter rows -> an owned contiguous (B, 8) float32 block on `device`"""
+    t = torch.as_tensor(theta0).detach().to(device=device, dtype=torch.float32)
+    if t.dim() != 2 or t.shape[0] != B or t.shape[1] not in (7, 8):
+        raise ValueError(f"theta0 must be ({B}, 7) or ({B}, 8), not {list(t.shape)}")
+    block = torch.zeros((B, 8), dtype=torch.float32, device=device)
+    block[:, :t.shape[1]] = t
+    return block
+
+
+def adam_state(B, device):
+    """What an optimiser object carries from episode to episode: dict(m, v [B, 8] f32, t, skipped, bad [B] int32)"""
+    z = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=device)
+    return dict(m=z(torch.float32, B, 8), v=z(torch.float32, B, 8), t=0, skipped=z(torch.int32, B), bad=z(torch.int32, B))
+
+
+def _bounds(bounds):
+    """{name or column: (lo, hi)} -> two ctypes arrays of 8 floats (-inf / +inf where nothing is said)"""
+    lo, hi = [-inf] * 8, [inf] * 8
+    for name, (a, b) in (bounds or {}).items():
+        m = column_mask([name])
+        for c in range(7):
+            if (m >> c) & 1:
+                lo[c], hi[c] = (-inf if a is None else float(a)), (inf if b is None else float(b))
+    return (C.c_float * 8)(*lo), (C.c_float * 8)(*hi)
+
+
+def _adam_scalars(t, lr, betas, eps):
+    """the scalars of step t as torch.optim.Adam computes them (Python floats, i.e. double)"""
+    b1, b2 = float(betas[0]), float(betas[1])
+    return (b1, 1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), sqrt(1.0 - b2 ** t), float(eps))
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _want(t, dtype, shape, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or \
+            t.device.type != "cuda":
+        raise ValueError(f"{what} must be a contiguous {dtype} device tensor of shape {list(shape)}")
+    return t
+
+
+def lon_loss(state, last_xy, opt_d, min_distance, stop, arrived, collided, stuck_count, ended, collision_threshold,
+             stuck_threshold=0.01, stuck_patience=5, loss_weight=10.0, loss_offset=50.0, override=None):
+    """npa_lon_loss on the current stream.  state [B, 3] f64, last_xy [B, 2] f64, opt_d [B, T] or [B, 1, T] f32, min_distance [B]
+    f32, stop [B] uint8, arrived / collided / stuck_count / ended [B] int32, override [B, 2] f32 (default: NaN rows); last_xy,
+    stuck_count, ended and override are updated in place.  Returns dict(active [B] int32, loss [B] f32, stuck [B] uint8,
+    grad_s [B, 3, T+1], grad_u [B, 2, T], grad_d [B, T], override)."""
+    B = state.shape[0]
+    dev = state.device
+    d = opt_d.reshape(B, -1)
+    T = d.shape[1]
+    f32, f64, i32, u8 = torch.float32, torch.float64, torch.int32, torch.uint8
+    _want(state, f64, (B, 3), "state"); _want(last_xy, f64, (B, 2), "last_xy"); _want(d, f32, (B, T), "opt_d")
+    _want(min_distance, f32, (B,), "min_distance"); _want(stop, u8, (B,), "stop")
+    for t, what in ((arrived, "arrived"), (collided, "collided"), (stuck_count, "stuck_count"), (ended, "ended")):
+        _want(t, i32, (B,), what)
+    if override is None:
+        override = torch.full((B, 2), nan, dtype=f32, device=dev)
+    _want(override, f32, (B, 2), "override")
+    out = dict(active=torch.empty((B,), dtype=i32, device=dev), loss=torch.empty((B,), dtype=f32, device=dev),
+               stuck=torch.empty((1, B), dtype=u8, device=dev), grad_s=torch.empty((B, 3, T + 1), dtype=f32, device=dev),
+               grad_u=torch.empty((B, 2, T), dtype=f32, device=dev), grad_d=torch.empty((B, T), dtype=f32, device=dev),
+               override=override)
+    with torch.cuda.device(dev):
+        check(_lib.load().npa_lon_loss(B, T, 0, _ptr(state), _ptr(last_xy), _ptr(d), _ptr(min_distance), _ptr(stop), _ptr(arrived),
+                                       _ptr(collided), float(collision_threshold), float(stuck_threshold), int(stuck_patience),
+                                       float(loss_weight), float(loss_offset), _ptr(stuck_count), _ptr(ended), _ptr(out["active"]),
+                                       _ptr(out["loss"]), _ptr(out["grad_s"]), _ptr(out["grad_u"]), _ptr(out["grad_d"]),
+                                       _ptr(override), None, _ptr(out["stuck"]), None, _stream(dev)), "npa_lon_loss")
+    out["stuck"] = out["stuck"][0]
+    return out
+
+
+def lon_adam(theta, tot, gacc, m, v, active, skipped, t, mask, lr=5e-3, betas=(0.9, 0.999), eps=1e-8, accumulate=True,
+             bounds=None):
+    """npa_lon_adam on the current stream: step `t` (1, 2, ...) of Adam on the rows of theta [B, 8] f32 with the gradient rows
+    tot [B, 8] f64 (cleared behind the read), in place; gacc, m, v [B, 8] f32, active / skipped [B] int32; mask: a bit per
+    column (column_mask); bounds: {name: (lo, hi)}."""
+    B = theta.shape[0]
+    f32 = torch.float32
+    _want(theta, f32, (B, 8), "theta"); _want(tot, torch.float64, (B, 8), "tot")
+    for x, what in ((gacc, "gacc"), (m, "m"), (v, "v")):
+        _want(x, f32, (B, 8), what)
+    _want(active, torch.int32, (B,), "active"); _want(skipped, torch.int32, (B,), "skipped")
+    if int(t) < 1:
+        raise ValueError("the step count starts at 1")
+    lo, hi = _bounds(bounds)
+    with torch.cuda.device(theta.device):
+        check(_lib.load().npa_lon_adam(B, int(mask), 1 if accumulate else 0, _ptr(tot), _ptr(gacc), _ptr(m), _ptr(v), _ptr(theta),
+                                       _ptr(active), *_adam_scalars(int(t), lr, betas, eps), lo, hi, _ptr(skipped),
+                                       _stream(theta.device)), "npa_lon_adam")
+    return theta
+
+
+class LonLoop(ResidentLoop):
+    """`ResidentLoop` that trains: one parameter row per robot, one Adam step per robot and cycle, everything on the device (the
+    launch sequence: this module's header).  `fleet` as for ResidentLoop (fresh from `set_paths`); `theta0` (B, 7) or (B, 8): the
+    rows training starts from -- the loop owns a (B, 8) copy, installs it with `fleet.set_adjust` and the Adam kernel rewrites it
+    in place (`theta`).  train: the columns that are stepped; lr, betas, eps: torch.optim.Adam's; loss_weight, loss_offset,
+    stuck_threshold, stuck_patience: the example's 10, 50, 0.01, 5; accumulate: gradients add up over an episode, as they do in
+    the example, which clears them once per episode (False: every cycle steps on its own gradient); bounds: {name: (lo, hi)}
+    clamps a column after every step.  The remaining arguments are ResidentLoop's.
+    `t`, the step count of the bias correction, counts cycles since construction and is not reset, as an optimiser object's.
+    Attributes besides ResidentLoop's (device tensors, the same objects for the life of the loop): theta, m, v, gacc [B, 8] f32,
+    loss [B] f32, active, ended, stuck_count, skipped (steps refused for a non-finite gradient), bad (re-solves whose status
+    was not 0) [B] int32, override [B, 2] f32."""
+
+    def __init__(self, fleet, world, states, theta0, train=("p_u", "eta", "d_max"), lr=5e-3, betas=(0.9, 0.999), eps=1e-8,
+                 loss_weight=10.0, loss_offset=50.0, stuck_threshold=0.01, stuck_patience=5, accumulate=True, bounds=None,
+                 scan=None, point_velocities=False, peers=False, max_points=None):
+        if getattr(fleet, "B", 0) < 1:
+            raise ValueError("LonLoop: the fleet has no paths (set_paths first)")
+        pan = fleet.pan
+        if pan.no_obs:
+            raise NeupanAmdError("LonLoop: the planner has no obstacle stage (nrmp_max_num == 0 or dune_max_num == 0): there is no "
+                                 "opt_d, and opt_d is the loss's input")
+        self.mask = column_mask(train)
+        self._lo, self._hi = _bounds(bounds)
+        self.lr, self.betas, self.eps, self.accumulate = float(lr), (float(betas[0]), float(betas[1])), float(eps), bool(accumulate)
+        self._rule = (float(fleet.collision_threshold), float(stuck_threshold), int(stuck_patience), float(loss_weight),
+                      float(loss_offset))
+        theta = adjust_block(theta0, fleet.B, world.device)
+        if getattr(pan, "_untrained", False) or not pan._h.value:
+            raise NeupanAmdError("LonLoop: the planner has no kernel handle (no DUNE checkpoint yet)")
+        fleet.set_adjust(theta)
+        super().__init__(fleet, world, states, scan=scan, point_velocities=point_velocities, certify=False, peers=peers,
+                         max_points=max_points)
+        B, T, dev = self.B, self.T, self.device
+        K, M, E = pan.iter_num, max(pan.nrmp_max_num, 1), pan.E
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+        self.theta, self.t, self._first = theta, 0, True
+        self.m, self.v, self.gacc, self._tot = zeros((B, 8), f32), zeros((B, 8), f32), zeros((B, 8), f32), zeros((B, 8), f64)
+        self.active, self.ended, self.stuck_count = zeros((B,), i32), zeros((B,), i32), zeros((B,), i32)
+        self.skipped, self.bad, self.loss = zeros((B,), i32), zeros((B,), i32), zeros((B,), f32)
+        self.last_xy = self.states[:, :2].clone()
+        self.override = torch.full((B, 2), nan, dtype=f32, device=dev)
+        self._ended_mask = torch.zeros((B, 1), dtype=torch.bool, device=dev)
+        # ---- the backward pass: upstream gradients, one re-solve's outputs, the snapshots of the K iterations
+        self._gs, self._gu, self._gd = zeros((B, 3, T + 1), f32), zeros((B, 2, T), f32), zeros((B, T), f32)
+        self._gth, self._gns = zeros((B, 8), f32), zeros((B, 3, T + 1), f32)
+        self._bw_out = (zeros((B, 3, T + 1), f32), zeros((B, 2, T), f32), zeros((B, 1, T), f32))
+        self._kfirst = 0 if getattr(pan, "recurrent", True) else K - 1
+        self._snap = dict(cur_s=zeros((K, B, 3, T + 1), f32), cur_u=zeros((K, B, 2, T), f32), mu=zeros((K, B, T + 1, M, E), f32),
+                          lam=zeros((K, B, T + 1, M, 2), f32), pts=zeros((K, B, T + 1, M, 2), f32), count=zeros((K, B, T + 1), i32))
+        self._views = pan._workspace_views()                    # (offsets from npa_workspace_layout, over the held workspace)
+        for key, snap in self._snap.items():
+            assert tuple(self._views[key].shape) == tuple(snap.shape[1:]), key
+        self.K = K
+        # ---- what reset() restores
+        c, s = self._held[2], self._held[3]
+        self._saved = (self.states.clone(), c.clone(), s.clone(), self.cur_off.clone(), self.cur_len.clone())
+
+    # ------------------------------------------------------------------ one cycle
+    def _issue(self, row, logs, i):
+        """one cycle; row: this cycle's scripted actions [B, 2] (contiguous f32 device tensor) or None; logs: the addresses of
+        the nine logs or None; i: the cycle's row in them"""
+        lib, pan, dev = self._lib, self.fleet.pan, self.device
+        ws, state = pan._ws, pan._state
+        if ws is None or state is None or (ws.data_ptr(), state.data_ptr()) != self._held_ptrs:
+            raise NeupanAmdError("LonLoop: the planner's workspace was re-made since the loop was prepared (another batch size "
+                                 "planned on the same PAN): make the loop again")
+        if pan.scene_adjust is None or pan.scene_adjust.data_ptr() != self.theta.data_ptr():
+            raise NeupanAmdError("LonLoop: another adjust block was installed on the fleet since the loop was prepared")
+        B, T, K = self.B, self.T, self.K
+        stream = _stream(dev)
+        if row is not None:                              # a scripted row does not move a robot whose episode has ended
+            self.override.copy_(row)
+            torch.ne(self.ended.view(B, 1), 0, out=self._ended_mask)
+            self.override.masked_fill_(self._ended_mask, 0.0)
+        for name, fn, args in self._front:
+            rc = fn(*args, stream)
+            if rc:
+                check(rc, name)
+        check(lib.npa_forward_begin(*self._plan, stream, 0), "npa_forward_begin")
+        snap, vw, h = self._snap, self._views, pan._h
+        try:
+            for k in range(K):
+                if k >= self._kfirst:
+                    snap["cur_s"][k].copy_(vw["cur_s"]); snap["cur_u"][k].copy_(vw["cur_u"])
+                rc = lib.npa_forward_iter(h, k)
+                if rc:
+                    check(rc, "npa_forward_iter")
+                if k >= self._kfirst:
+                    for key in ("mu", "lam", "pts", "count"):
+                        snap[key][k].copy_(vw[key])
+        except BaseException:
+            lib.npa_forward_end(h)
+            raise
+        check(lib.npa_forward_end(h), "npa_forward_end")
+        la, ls, lc, ln, lh, lr, ll, lk, le = logs if logs is not None else (None,) * 9
+        rc = lib.npa_cycle_act(B, T, self._kin, 1 if self._first else 0, i, *self._act, _ptr(self.override), *self._act_out,
+                               la, ls, lc, ln, stream)
+        if rc:
+            check(rc, "npa_cycle_act")
+        rc = lib.npa_world_step(*self._step, stream)
+        if rc:
+            check(rc, "npa_world_step")
+        rc = lib.npa_cycle_commit(B, i, *self._commit, lh, lr, stream)
+        if rc:
+            check(rc, "npa_cycle_commit")
+        if row is not None:
+            self.override.fill_(nan)
+        out = self.out
+        rc = lib.npa_lon_loss(B, T, i, _ptr(self.states), _ptr(self.last_xy), _ptr(out["opt_d"]), _ptr(out["min_distance"]),
+                              _ptr(self.stop), _ptr(self.arrived), _ptr(self.collided), *self._rule, _ptr(self.stuck_count),
+                              _ptr(self.ended), _ptr(self.active), _ptr(self.loss), _ptr(self._gs), _ptr(self._gu), _ptr(self._gd),
+                              _ptr(self.override), ll, lk, le, stream)
+        if rc:
+            check(rc, "npa_lon_loss")
+        ref_s, ref_us = self.nominal[2], self.nominal[3]
+        bs, bu, bd = self._bw_out
+        for k in range(K - 1, self._kfirst - 1, -1):
+            rc = lib.npa_nrmp_backward(h, B, _ptr(snap["cur_s"][k]), _ptr(snap["cur_u"][k]), _ptr(ref_s), _ptr(ref_us),
+                                       _ptr(snap["mu"][k]), _ptr(snap["lam"][k]), _ptr(snap["pts"][k]), _ptr(snap["count"][k]),
+                                       _ptr(bs), _ptr(bu), _ptr(bd), _ptr(self._gs), _ptr(self._gu), _ptr(self._gd),
+                                       _ptr(self._gth), _ptr(self._gns), None, stream)
+            if rc:
+                check(rc, "npa_nrmp_backward")
+            rc = lib.npa_lon_chain(B, T, k, _ptr(out["iters"]), _ptr(self._gth), _ptr(self._gns), _ptr(self._tot), _ptr(self._gs),
+                                   _ptr(self._gu), _ptr(self._gd), _ptr(self.bad), stream)
+            if rc:
+                check(rc, "npa_lon_chain")
+        self.t += 1
+        rc = lib.npa_lon_adam(B, self.mask, 1 if self.accumulate else 0, _ptr(self._tot), _ptr(self.gacc), _ptr(self.m),
+                              _ptr(self.v), _ptr(self.theta), _ptr(self.active), *_adam_scalars(self.t, self.lr, self.betas, self.eps),
+                              self._lo, self._hi, _ptr(self.skipped), stream)
+        if rc:
+            check(rc, "npa_lon_adam")
+        pan._last, pan.last_out = self._pan_last, self.out
+        self._first = False
+        self.cycles_done += 1
+        if (self.cycles_done & 63) == 0:             # (a host read of one pinned word: no synchronisation)
+            pan.check_audit()
+
+    def _row(self, t):
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.states.device
+                and tuple(t.shape) == (self.B, 2) and t.is_contiguous()):
+            t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32).reshape(self.B, 2).contiguous()
+        return t
+
+    def cycle(self, actions_row=None):
+        """One training cycle on the current stream; actions_row as for ResidentLoop.cycle (rows of robots whose episode has ended
+        count as zeros).  Returns `action`."""
+        self._on_device(self._row(actions_row), None, 0)
+        return self.action
+
+    def run(self, cycles, actions=None):
+        return self.episode(cycles, actions)
+
+    def episode(self, cycles, actions=None):
+        """`cycles` training cycles from where the loop stands (`reset` starts the robots over); returns run_closed_loop's dict
+        plus loss [cycles, B] f32, stuck and ended [cycles, B] bool (after each cycle) and theta [cycles, B, 8] f32 (after each
+        cycle's step).  The logs are allocated here, once; nothing is read back."""
+        B, T, dev = self.B, self.T, self.device
+        cycles = int(cycles)
+        f32, f64 = torch.float32, torch.float64
+        hist = torch.empty((cycles + 1, B, 3), dtype=f64, device=dev)
+        acts = torch.zeros((cycles, B, 2), dtype=f32, device=dev)
+        stops = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
+        clrs = torch.full((cycles, B), float("inf"), dtype=f64, device=dev)
+        ctrl = torch.zeros((cycles, B, 2, T), dtype=f32, device=dev)
+        npt = torch.zeros((cycles, B), dtype=torch.int32, device=dev)
+        loss = torch.zeros((cycles, B), dtype=f32, device=dev)
+        stuck = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
+        ended = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
+        thetas = torch.zeros((cycles, B, 8), dtype=f32, device=dev)
+        hist[0].copy_(self.states)
+        override = None
+        if actions is not None:
+            override = torch.as_tensor(actions).to(device=dev, dtype=f32).contiguous()
+            if tuple(override.shape) != (cycles, B, 2):
+                raise ValueError(f"actions must be [{cycles}, {B}, 2], not {list(override.shape)}")
+        logs = tuple(_ptr(t) for t in (acts, stops, ctrl, npt, hist, clrs, loss, stuck, ended)) if cycles > 0 else None
+        for i in range(cycles):
+            self._on_device(override[i] if override is not None else None, logs, i)
+            thetas[i].copy_(self.theta)
+        return dict(states=hist, actions=acts, arrive=self.arrived != 0, stop=stops, collided=self.collided != 0, clearance=clrs,
+                    controls=ctrl, n_points=npt, loss=loss, stuck=stuck, ended=ended, theta=thetas)
+
+    def reset(self):
+        """Start every robot over -- poses, path state, latches, warm start, stuck counters, the accumulated gradients, the
+        planner's state record, the world -- without touching theta, m, v or t.  copy_ / zero_ / fill_ only."""
+        st0, c0, s0, off0, len0 = self._saved
+        self.states.copy_(st0)
+        self.last_xy.copy_(st0[:, :2])
+        self._held[2].copy_(c0); self._held[3].copy_(s0)
+        self.cur_off.copy_(off0); self.cur_len.copy_(len0)
+        for t in (self.curve_index, self.point_index, self.arrived, self.collided, self._curve_arrived, self.cur_vel,
+                  self.stuck_count, self.ended, self.gacc, self._tot, self.fleet.pan._state):
+            t.zero_()
+        self.override.fill_(nan)
+        self._first = True
+
+
+def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train=("p_u", "eta", "d_max"), lr=5e-3,
+                      betas=(0.9, 0.999), eps=1e-8, loss_weight=10.0, loss_offset=50.0, stuck_threshold=0.01, stuck_patience=5,
+                      accumulate=True, bounds=None, scan=None, point_velocities=False, peers=False, max_points=None, actions=None):
+    """One episode of `LonLoop`'s cycle paced by the host, for a fleet fresh from `set_paths` in a fresh `world`:
+
+        scan -> scan_to_point[_velocity]_batch -> fleet.forward(adjust=theta) -> LidarWorld.step -> the loss (torch operations
+        on info["opt_d"]; the bookkeeping by lon_loss) -> backward() into theta.grad -> lon_adam
+
+    `theta`: the (B, 8) float32 device block (`adjust_block`), stepped in place; `opt_state`: what `adam_state` made (m, v, t,
+    skipped, bad), carried from episode to episode and updated in place (default: a fresh one).  The other arguments are
+    LonLoop's and run_closed_loop's.  The host reads the device several times per cycle (fleet.forward's bookkeeping, the
+    gradient chain's flags).  Returns the dict LonLoop.episode returns."""
+    sp = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0)
+    sp.update(scan or {})
+    dev = world.device
+    if fleet.pan.no_obs:
+        raise NeupanAmdError("train_closed_loop: the planner has no obstacle stage: there is no opt_d, and opt_d is the loss's input")
+    V = robot_vertices(fleet.robot)
+    kin, L, dt = fleet.robot.kinematics, getattr(fleet.robot, "L", 0.0) or 0.0, fleet.dt
+    st = world._states(states).clone()
+    B, T = st.shape[0], fleet.T
+    f32, f64, i32 = torch.float32, torch.float64, torch.int32
+    _want(theta, f32, (B, 8), "theta")
+    opt = adam_state(B, dev) if opt_state is None else opt_state
+    mask = column_mask(train)
+    w, off, thr = float(loss_weight), float(loss_offset), float(fleet.collision_threshold)
+    if peers:
+        world.set_peers(st, V)
+    hist = torch.empty((cycles + 1, B, 3), dtype=f64, device=dev)
+    acts = torch.zeros((cycles, B, 2), dtype=f32, device=dev)
+    stops = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
+    clrs = torch.full((cycles, B), float("inf"), dtype=f64, device=dev)
+    ctrl = torch.zeros((cycles, B, 2, T), dtype=f32, device=dev)
+    npt = torch.zeros((cycles, B), dtype=i32, device=dev)
+    losses = torch.zeros((cycles, B), dtype=f32, device=dev)
+    stucks = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
+    endeds = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
+    thetas = torch.zeros((cycles, B, 8), dtype=f32, device=dev)
+    collided = torch.zeros((B,), dtype=torch.bool, device=dev)
+    arrive = torch.zeros((B,), dtype=torch.bool, device=dev)
+    ended, stuck_count = torch.zeros((B,), dtype=i32, device=dev), torch.zeros((B,), dtype=i32, device=dev)
+    gacc = torch.zeros((B, 8), dtype=f32, device=dev)
+    last_xy = st[:, :2].clone()
+    hist[0] = st
+    scripted = None if actions is None else torch.as_tensor(actions).to(device=dev, dtype=f32)
+    extra = {k: sp[k] for k in ("angle_range", "down_sample") if k in sp}
+    offset = sp.get("scan_offset", (0.0, 0.0, 0.0))
+    zero = torch.zeros((B,), dtype=f32, device=dev)
+    for cyc in range(cycles):
+        st_h = st.cpu().numpy()
+        ranges, bvel, _ = world.scan(st, sp["n_beams"], sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"], offset)
+        if point_velocities:
+            pts, pvel, npts = scan_to_point_velocity_batch(st_h, ranges, sp["angle_min"], sp["angle_max"], sp["range_min"],
+                                                           sp["range_max"], velocities=bvel, scan_offset=offset,
+                                                           max_points=max_points, device=dev, **extra)
+        else:
+            pts, npts = scan_to_point_batch(st_h, ranges, sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"],
+                                            scan_offset=offset, max_points=max_points, device=dev, **extra)
+            pvel = None
+        leaf = theta.detach().clone().requires_grad_(True)
+        act, info = fleet.forward(st_h, pts, pvel, npts, adjust=leaf)
+        act = act.detach()
+        # the override: the scripted row (NaN = the planner's action); a robot whose episode has ended stands still
+        ov = torch.full((B, 2), nan, dtype=f32, device=dev) if scripted is None else scripted[cyc]
+        ov = torch.where(ended[:, None] != 0, torch.zeros_like(ov), ov)
+        act = torch.where(torch.isnan(ov), act, ov)
+        arrive = info["arrive"]
+        frozen = (arrive | collided).to(i32)
+        act = torch.where(frozen[:, None] != 0, torch.zeros_like(act), act)
+        st, clr = world.step(st, act, dt, kin, L, frozen=frozen, robot_vertices=V, peers=peers)
+        collided = collided | (clr <= 0)
+        acts[cyc], stops[cyc], clrs[cyc], hist[cyc + 1] = act, info["stop"], clr, st
+        ctrl[cyc], npt[cyc] = info["opt_u"].detach(), npts
+        # the loss: the bookkeeping by the kernel both loops share, the differentiable part as torch operations
+        md = info["min_distance"]
+        book = lon_loss(st, last_xy, info["opt_d"].detach().contiguous(), md, info["stop"].to(torch.uint8), arrive.to(i32),
+                        collided.to(i32), stuck_count, ended, thr, stuck_threshold, stuck_patience, w, off)
+        d = info["opt_d"][:, 0, :]
+        S = torch.zeros((B,), dtype=f32, device=dev)
+        for t in range(T):
+            S = S + d[:, t]
+        loss = torch.where(md <= thr, w * (off - S), torch.where(book["stuck"] != 0, w * (off + S), zero))
+        loss = torch.where(book["active"] != 0, loss, zero)
+        loss.sum().backward()
+        losses[cyc], stucks[cyc], endeds[cyc] = loss.detach(), book["stuck"] != 0, ended != 0
+        opt["bad"] += fleet.pan.last_backward_bad
+        opt["t"] += 1
+        lon_adam(theta, leaf.grad.double().contiguous(), gacc, opt["m"], opt["v"], book["active"], opt["skipped"], opt["t"], mask,
+                 lr=lr, betas=betas, eps=eps, accumulate=accumulate, bounds=bounds)
+        thetas[cyc] = theta
+    return dict(states=hist, actions=acts, arrive=arrive, stop=stops, collided=collided, clearance=clrs, controls=ctrl,
+                n_points=npt, loss=losses, stuck=stucks, ended=endeds, theta=thetas)

@@ -903,18 +903,23 @@ def _grad_backward_rows(ctx, gs, gu, gd):
     gu = torch.zeros((B, 2, T), device=dev) if gu is None else gu.contiguous()
     gd = None if (gd is None or ctx.no_obs) else gd.contiguous()
     tot = torch.zeros((B, 7), dtype=torch.float64, device=dev)
+    bad = torch.zeros((B,), dtype=torch.int32, device=dev)
+    pan.last_backward_bad = bad                    # (B,) int32: re-solves of this pass whose solver status was not 0
     for k, snap_s, snap_u, stage in reversed(ctx.snaps):
         ran = ctx.iters > k                        # scenes whose stop test ended the loop earlier skip this solve
         if not bool(ran.any()):
             continue
         r = pan.nrmp_backward(snap_s, snap_u, ref_s, ref_us, stage, gs, gu, gd)
         tot += torch.where(ran[:, None], r["grad"][:, :7].double(), torch.zeros_like(tot))
+        bad += (ran & (r["grad"][:, 7] != 0)).to(torch.int32)
         m = ran[:, None, None]
         gs = torch.where(m, r["grad_nom_s"], gs)
         gu = torch.where(m, torch.zeros_like(gu), gu)
         if gd is not None:
             gd = torch.where(m, torch.zeros_like(gd), gd)
-        if not bool((gs != 0).any()):
+        # (nothing left upstream for any scene: the remaining solves would add exact zeros.  gu and gd count too: a scene that
+        # has not run yet -- its loop ended before iteration k -- still holds the loss's own gradient in them)
+        if not (bool((gs != 0).any()) or bool((gu != 0).any()) or (gd is not None and bool((gd != 0).any()))):
             break
     return tot
 
