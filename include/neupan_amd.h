@@ -515,6 +515,82 @@ int npa_world_step(int batch, int n_worlds, int c_stride, int s_stride, double *
                    const int32_t *frozen, double dt, int kinematics, double wheelbase, const double *bounds,
                    int edge_num, const double *vertices, int peer_base, double *clearance, void *stream);
 
+/* ---- reactive obstacles: agents of the lidar world that choose their own velocity (csrc/behave.hip) --------------------
+ *
+ * The method is the sampled penalty of J. van den Berg, M. Lin, D. Manocha, "Reciprocal Velocity Obstacles for Real-Time
+ * Multi-Agent Navigation", ICRA 2008: every agent takes, of a table of candidate velocities v', the one with the lowest
+ * w / tc(v') + |v_pref - v'|, tc the time to the first collision if every neighbour kept its share of the avoidance.  This
+ * comment is the specification (tests/behave_ref.py restates it in numpy).  Handle-free, stream-ordered: no workspace, no
+ * atomics, no host synchronisation; float64 in the operation order written here, no FMA contraction.
+ *
+ * An AGENT is a primitive, or a run of primitives, of a world: a circle agent owns one circle, a polygon agent `count`
+ * consecutive segments.  Two DEVICE tables per world, with a row stride and counts like the primitives':
+ *   agents    [W][a_stride][NPA_AGENT_DOUBLES] f64   0 gx  1 gy (the goal)   2 vx  3 vy (the velocity chosen by the last call)
+ *                                                    4 ox  5 oy: centre - anchor, the anchor being the circle's centre or end a
+ *                                                    of the first segment (constant under translation: the centre is never
+ *                                                    stored)   6 R (bounding radius about the centre)   7 v_max
+ *                                                    8 goal_threshold   9 the index of the candidate chosen by the last call
+ *   agent_idx [W][a_stride][NPA_AGENT_INTS] int32    0 first primitive (the world's numbering: circles, then segments)
+ *                                                    1 count (1 for a circle)   2 wander (0 / 1)   3 draws (uint32: wander
+ *                                                    goals drawn so far)
+ *   n_agents  [W] int32 (clamped to a_stride).  A row whose primitives do not exist (first < 0, count < 1, a circle with
+ *   count != 1, a run beyond n_segments) is no agent: it is neither moved nor anybody's neighbour.  Runs must not overlap.
+ * npa_behave_params (HOST): weight (the w of the penalty, > 0), horizon (seconds, > 0), robot_share (in (0, 1]),
+ *   range_low / range_high (the box wander goals are drawn from), seed, world_base (added to the world's index in the
+ *   generator, so that a world computes the same whichever batch it is in).
+ *
+ * npa_world_behave (two launches).  Per agent A: centre p = anchor + (ox, oy); v_A = the velocity columns of its first
+ * primitive (the velocities of the cycle before: launch 1 writes agent rows only).
+ *   1. d = g - p, L = sqrt(dx dx + dy dy); arrived: L <= goal_threshold.  Arrived with wander: a new goal is drawn, draws += 1,
+ *      d and L are recomputed (no second arrival test).  Arrived without wander, or L == 0: v_pref = 0 (goal and draws
+ *      untouched).  Otherwise s = min(v_max, L / dt), v_pref = ((dx / L) s, (dy / L) s).
+ *      The generator: mix(z) = { z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27)
+ *      0x94D049BB133111EB; z ^ z >> 31 } on uint64; z = mix(mix(mix(mix(seed + world_base + w) + first) + draw) + coordinate),
+ *      coordinate 0 for x and 1 for y, draw = `draws` before the increment; u = (z >> 11) 2^-53, g = lo + (hi - lo) u.  The
+ *      agent is named by its first primitive, not by its row.
+ *   2. candidates: 0 = (0, 0); 1 = v_pref; 2 = v_A, times v_max / |v_A| when |v_A| > v_max; 3 + j n_dir + k =
+ *      (s_j dirs[k].x, s_j dirs[k].y), s_j = (v_max (j + 1)) / n_speed, j < n_speed, k < n_dir.  dirs [n_dir][2] f64 DEVICE: unit
+ *      directions tabulated by the caller.  3 + n_speed n_dir <= npa_behave_max_candidates().
+ *   3. neighbours, each with the share alpha of the avoidance A takes: apex = (1 - alpha) v_A + alpha v_B, relative velocity
+ *      u = (v' - apex) (1 / alpha).
+ *        another agent of the world      alpha = 1/2          disc of radius R_A + R_B at its centre
+ *        a circle no agent owns          alpha = 1            disc of radius R_A + r
+ *        a segment no agent owns, index below seg_limit (seg_limit < 0: all)
+ *                                        alpha = 1            the capsule: discs of radius R_A at both ends and the segment
+ *                                                             shifted by +- R_A n, n = (ey, -ex) / |e|, e = b - a
+ *        a robot                         alpha = robot_share  disc of radius R_A + robot_radius at state[b]; v_B = (state -
+ *                                                             prev_state) / dt, 0 when prev_state is null
+ *      An agent of world w sees robot w when n_worlds == batch and all `batch` robots when n_worlds == 1.
+ *   4. tc: the ray p + t u against each shape, in npa_world_scan's forms.  Disc, c = centre - p, c2 = |c|^2 - rho^2,
+ *      b = c . u: c2 <= 0 (touching): tc = 0 when b > 0, else no collision; otherwise a hit when b > 0 and disc = b^2 - |u|^2 c2
+ *      >= 0, tc = c2 / (b + sqrt(disc)).  Segment: the sign-corrected cross-multiplied validity test, then one division.
+ *      tc > horizon: no collision.  tc_min = the minimum over the neighbours, +inf without one.
+ *   5. cost = weight / tc_min + sqrt((v_pref.x - v'.x)^2 + (v_pref.y - v'.y)^2) (+inf for tc_min = 0); the lowest cost wins,
+ *      ties to the lowest index.  Launch 1 writes columns 0 - 3 and 9 of the agent's row and `draws`; launch 2 copies the
+ *      chosen velocity into the velocity columns of every primitive the agent owns and touches nothing else.
+ *      npa_world_step then translates them as any moving primitive.
+ *   Neighbours are culled against horizon (v_max + |apex|) / alpha + rho and cast in chunks of npa_behave_list_capacity();
+ *   the result does not depend on the chunking, on the order of the agent rows or on the batch a world is in.
+ * NPA_E_ARG (before anything touches a device): a null required pointer (prev_state may be null; dirs when there is no
+ *   grid), batch <= 0, a_stride <= 0, n_worlds not in {1, batch}, dt <= 0, weight <= 0, horizon <= 0, robot_share outside
+ *   (0, 1], range_low above range_high, robot_radius < 0, more candidates than the cap, strides that do not fit (no
+ *   primitives at all, seg_limit beyond s_stride, more rows than a launch addresses). */
+#define NPA_AGENT_DOUBLES 10
+#define NPA_AGENT_INTS 4
+typedef struct npa_behave_params {
+  double weight, horizon, robot_share;
+  double range_low[2], range_high[2];
+  uint64_t seed;
+  int32_t world_base, reserved;
+} npa_behave_params;
+int npa_behave_list_capacity(void);
+int npa_behave_max_candidates(void);
+int npa_world_behave(int batch, int n_worlds, int c_stride, int s_stride, double *circles, double *segments,
+                     const int32_t *n_circles, const int32_t *n_segments, int a_stride, double *agents,
+                     int32_t *agent_idx, const int32_t *n_agents, const npa_behave_params *params,
+                     const double *state, const double *prev_state, double robot_radius, int seg_limit,
+                     int n_dir, const double *dirs, int n_speed, double dt, void *stream);
+
 /* ---- the bookkeeping of a device-resident closed loop (csrc/cycle.hip) -----------------------------------------------
  *
  * What the host does between the kernels of a control cycle, as three calls: handle-free, stream-ordered, one thread per

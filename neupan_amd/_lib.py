@@ -40,6 +40,12 @@ class NpaForwardCall(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class NpaBehaveParams(C.Structure):
+    """npa_behave_params (include/neupan_amd.h): the behaviour parameters of a world's agents, npa_world_behave."""
+    _fields_ = [("weight", C.c_double), ("horizon", C.c_double), ("robot_share", C.c_double), ("range_low", C.c_double * 2),
+                ("range_high", C.c_double * 2), ("seed", C.c_uint64), ("world_base", C.c_int32), ("reserved", C.c_int32)]
+
+
 class NpaDuneWeights(C.Structure):
     _fields_ = [("lin_w", C.c_void_p * 6), ("lin_b", C.c_void_p * 6), ("ln_w", C.c_void_p * 3), ("ln_b", C.c_void_p * 3)]
 
@@ -83,6 +89,10 @@ SYMBOLS = {
     "npa_world_scan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "npa_world_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_double, _I, C.c_double, C.POINTER(C.c_double), _I,
                             C.POINTER(C.c_double), _I, _P, _P]),
+    "npa_behave_list_capacity": (_I, []),
+    "npa_behave_max_candidates": (_I, []),
+    "npa_world_behave": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, C.POINTER(NpaBehaveParams), _P, _P, C.c_double, _I,
+                              _I, _P, _I, C.c_double, _P]),
     "npa_cycle_progress": (_I, [_I, _P, _P, _P, _P, _P, _I, C.c_double, _I, C.c_double, _I] + [_P] * 8 + [_P]),
     "npa_cycle_act": (_I, [_I, _I, _I, _I, _I, _P, _P, C.c_float] + [_P] * 12 + [_P]),
     "npa_cycle_commit": (_I, [_I, _I, _P, _P, _P, _P, _P, _P]),

@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libneupan_amd.so")
 # launch, the first form of the geometric selection) and their knobs.
 EXPERIMENTS = os.environ.get("NPA_EXPERIMENTS", "0") not in ("", "0")
 SOURCES = ["dune.hip", "nrmp_qp.hip", "frontend.hip", "dune_labels.hip", "c_api.hip", "create.hip", "pack_image.hip", "serve_group.hip",
-           "ingest.hip", "clearance.hip", "world.hip", "cycle.hip", "lon.hip"] + \
+           "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip"] + \
           (["aset_reduce.hip"] if EXPERIMENTS else [])
 # -ffp-contract=fast-honor-pragmas is hipcc's default for device code, stated here so that it is the BUILD's property, not the
 # compiler's: the bit-exact legs (A / B / C, fa against the reference's tensors) are written with __f*_rn intrinsics where the
@@ -82,7 +82,8 @@ def build(force=False, verbose=True):
     for cmd, pr in procs:
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB]
+    # (linked stripped: the static symbol table is a fiftieth of the file and nothing reads it -- the exports are .dynsym's)
+    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--strip-all", *objs, "-o", LIB]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

@@ -10,7 +10,8 @@ QP and takes an Adam step; the episode ends on arrive, stop or stuck.  Here:
       npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states
       -> npa_forward_begin, K x { copy cur_s, cur_u into snapshot k; npa_forward_iter(k); copy the mu / lam / pts / count rows
          into snapshot k }, npa_forward_end
-      -> npa_cycle_act (override_row = the loop's override buffer) -> npa_world_step -> npa_cycle_commit
+      -> npa_cycle_act (override_row = the loop's override buffer) [-> npa_world_behave, when the world has agents]
+      -> npa_world_step -> npa_cycle_commit
       -> npa_lon_loss
       -> for k = K-1 .. first: npa_nrmp_backward(snapshot k, gs, gu, gd) -> npa_lon_chain(k)
       -> npa_lon_adam(t)
@@ -33,7 +34,7 @@ import torch
 from . import _lib
 from ._lib import NeupanAmdError, check
 from .frontend import _ptr, scan_to_point_batch, scan_to_point_velocity_batch
-from .world import ResidentLoop, robot_vertices
+from .world import ResidentLoop, robot_radius, robot_vertices
 
 COLUMNS = ("q_s0", "q_s1", "q_s2", "p_u", "eta", "d_max", "d_min")      # the columns of a parameter row (the eighth is reserved)
 
@@ -210,6 +211,10 @@ class LonLoop(ResidentLoop):
         # ---- what reset() restores
         c, s = self._held[2], self._held[3]
         self._saved = (self.states.clone(), c.clone(), s.clone(), self.cur_off.clone(), self.cur_len.clone())
+        self._saved_agents = None                                # (the agent table: goals, chosen velocities, draw counters)
+        if self._behave is not None:
+            ag, agi = world._upload_agents()[:2]
+            self._saved_agents = (ag, agi, ag.clone(), agi.clone())
 
     # ------------------------------------------------------------------ one cycle
     def _issue(self, row, logs, i):
@@ -253,6 +258,8 @@ class LonLoop(ResidentLoop):
                                la, ls, lc, ln, stream)
         if rc:
             check(rc, "npa_cycle_act")
+        if self._behave is not None:
+            self._issue_behave(self._first, stream)
         rc = lib.npa_world_step(*self._step, stream)
         if rc:
             check(rc, "npa_world_step")
@@ -348,6 +355,9 @@ class LonLoop(ResidentLoop):
         self.last_xy.copy_(st0[:, :2])
         self._held[2].copy_(c0); self._held[3].copy_(s0)
         self.cur_off.copy_(off0); self.cur_len.copy_(len0)
+        if self._saved_agents is not None:
+            ag, agi, ag0, agi0 = self._saved_agents
+            ag.copy_(ag0); agi.copy_(agi0)
         for t in (self.curve_index, self.point_index, self.arrived, self.collided, self._curve_arrived, self.cur_vel,
                   self.stuck_count, self.ended, self.gacc, self._tot, self.fleet.pan._state):
             t.zero_()
@@ -403,6 +413,8 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
     extra = {k: sp[k] for k in ("angle_range", "down_sample") if k in sp}
     offset = sp.get("scan_offset", (0.0, 0.0, 0.0))
     zero = torch.zeros((B,), dtype=f32, device=dev)
+    agents = world.has_agents
+    prev, rad = (torch.empty_like(st), robot_radius(fleet.robot)) if agents else (None, 0.0)
     for cyc in range(cycles):
         st_h = st.cpu().numpy()
         ranges, bvel, _ = world.scan(st, sp["n_beams"], sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"], offset)
@@ -424,6 +436,9 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
         arrive = info["arrive"]
         frozen = (arrive | collided).to(i32)
         act = torch.where(frozen[:, None] != 0, torch.zeros_like(act), act)
+        if agents:
+            world.behave(st, prev if cyc > 0 else None, dt, rad)
+            prev.copy_(st)
         st, clr = world.step(st, act, dt, kin, L, frozen=frozen, robot_vertices=V, peers=peers)
         collided = collided | (clr <= 0)
         acts[cyc], stops[cyc], clrs[cyc], hist[cyc + 1] = act, info["stop"], clr, st

@@ -1,16 +1,22 @@
 """A lidar world on the device and the closed loop around `FleetPlanner` -- the part of the reference's driver that its
 simulator plays (example/run_exp.py: env.get_lidar_scan() -> scan_to_point -> neupan_planner(...) -> env.step(action)).
 
-* `LidarWorld`        circles and segments (polygons and rectangles are their edges), static or moving at constant velocity;
-                      `scan` ray-casts B robots' lidars (npa_world_scan), `step` advances robots and world and measures every
-                      robot's exact clearance to the world (npa_world_step).  `from_yaml` reads the `obstacle:` list of an
-                      IR-SIM environment file.
+* `LidarWorld`        circles and segments (polygons and rectangles are their edges), static, moving at constant velocity, or
+                      AGENTS that choose their velocity every cycle (`add_agents`, `behave`: npa_world_behave, the sampled
+                      reciprocal-velocity-obstacle penalty of van den Berg, Lin, Manocha, ICRA 2008); `scan` ray-casts B robots'
+                      lidars (npa_world_scan), `step` advances robots and world and measures every robot's exact clearance to
+                      the world (npa_world_step).  `from_yaml` reads the `obstacle:` list of an IR-SIM environment file; with
+                      behaviours=True its `rvo` groups become agents.
 * `run_closed_loop`   scan -> scan_to_point[_velocity]_batch -> FleetPlanner.forward -> step, for B robots and a number of cycles.
 * `ResidentLoop`      the same cycle as a fixed sequence of launches over buffers that never move: the path bookkeeping, the action
                       and the latches are kernels too (csrc/cycle.hip), so the host neither reads the device nor allocates.
 
 There is no CPU fallback: scan and step are the HIP kernels of csrc/world.hip behind the C ABI (include/neupan_amd.h).
-What IR-SIM does and this does not: sensor noise, obstacle behaviours (rvo, ...), rendering.
+The loops call `behave` between the action and the step when the world has agents; a world without agents issues exactly the
+launches it issued before there were agents.
+What IR-SIM does and this does not: sensor noise, obstacle behaviours other than rvo, obstacle kinematics and heading (every
+agent is a holonomic disc or a translating polygon), rendering.  IR-SIM's rvo implementation was not available to compare with:
+the behaviour is the one include/neupan_amd.h specifies from the paper.
 """
 from __future__ import annotations
 
@@ -22,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import KIN, NeupanAmdError, check
+from ._lib import KIN, NeupanAmdError, NpaBehaveParams, check
 from .frontend import _SCAN_DTYPE, _bcast, _ptr, _stream, scan_to_point_batch, scan_to_point_velocity_batch
 
 _PARAM_DOUBLES = _SCAN_DTYPE.itemsize // 8         # npa_scan_params as a row of float64 words (13; the last holds two int32)
@@ -32,6 +38,47 @@ assert _SCAN_DTYPE.itemsize % 8 == 0
 def list_capacity():
     """primitives of one cull / cast chunk of npa_world_scan (the capacity of its LDS list)"""
     return int(_lib.load().npa_world_list_capacity())
+
+
+def behave_list_capacity():
+    """neighbours of one cull / cast chunk of npa_world_behave (the capacity of its LDS list)"""
+    return int(_lib.load().npa_behave_list_capacity())
+
+
+def behave_max_candidates():
+    """the most candidate velocities (3 + n_speed * n_dir) npa_world_behave takes"""
+    return int(_lib.load().npa_behave_max_candidates())
+
+
+AGENT_DOUBLES, AGENT_INTS = 10, 4              # NPA_AGENT_DOUBLES, NPA_AGENT_INTS (include/neupan_amd.h)
+_M64 = (1 << 64) - 1
+BEHAVIOUR = dict(weight=1.0, horizon=5.0, robot_share=0.5, range_low=(0.0, 0.0), range_high=(10.0, 10.0), seed=0, world_base=0,
+                 n_dir=20, n_speed=3)
+
+
+def _mix(z):
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def wander_goal(seed, world, agent, draw, range_low, range_high):
+    """draw number `draw` of the wander goal of the agent whose first primitive is `agent`, in world `world` (world_base
+    included): the counter-based generator of npa_world_behave (include/neupan_amd.h), integer operations only"""
+    out = []
+    for coord in (0, 1):
+        z = _mix((int(seed) + int(world)) & _M64)
+        for k in (agent, draw, coord):
+            z = _mix((z + int(k)) & _M64)
+        u = float(z >> 11) * 2.0 ** -53
+        out.append(float(range_low[coord]) + (float(range_high[coord]) - float(range_low[coord])) * u)
+    return out
+
+
+def direction_table(n_dir):
+    """[n_dir, 2] unit directions at the angles 2 pi k / n_dir (the table npa_world_behave reads)"""
+    return np.array([[cos(2.0 * pi * k / n_dir), sin(2.0 * pi * k / n_dir)] for k in range(int(n_dir))], dtype=np.float64).reshape(-1, 2)
 
 
 def polygon_segments(vertices, velocity=(0.0, 0.0)):
@@ -81,6 +128,11 @@ class LidarWorld:
         self.device = torch.device(device)
         self._dev = None                       # (circles, segments, n_circles, n_segments) device tensors, made on first use
         self.peer_base, self._peer_shape, self.skip, self._vertices = -1, None, None, None
+        # agents (include/neupan_amd.h: the tables of npa_world_behave); none until add_agents
+        self._ag, self._agi = np.zeros((W, 0, AGENT_DOUBLES)), np.zeros((W, 0, AGENT_INTS), dtype=np.int32)
+        self._na = np.zeros(W, dtype=np.int32)
+        self._adev, self._held_by_loop = None, False
+        self.behaviour = dict(BEHAVIOUR)
 
     # ------------------------------------------------------------------ building
     def add_polygon(self, vertices, velocity=(0.0, 0.0)):
@@ -99,6 +151,125 @@ class LidarWorld:
         self._s = s
         return first
 
+    def add_agents(self, first, count=1, v_max=1.0, goal_threshold=0.1, wander=False, goals=None, **behaviour):
+        """Make primitives of every world agents: they choose their velocity in every `behave` call (npa_world_behave).
+        first [n] or [W, n]: the first primitive of each agent in the world's numbering (circles 0 .. C-1, then segments);
+        count (scalar or [n]): 1 for a circle, E for a polygon of E consecutive segments; v_max, goal_threshold, wander: scalars
+        or [n]; goals [n, 2] or [W, n, 2], default: draw 0 of the wander generator from the behaviour's box (the draw counter
+        then starts at 1).  A polygon's centre is the mean of its vertices, its radius their largest distance from it.
+        **behaviour updates `self.behaviour`: weight, horizon, robot_share, range_low, range_high, seed, world_base, n_dir,
+        n_speed.  Returns the row of the first new agent."""
+        if self._held_by_loop:
+            raise RuntimeError("add_agents while a loop holds the world's device arrays")
+        unknown = set(behaviour) - set(BEHAVIOUR)
+        if unknown:
+            raise TypeError(f"unknown behaviour parameters {sorted(unknown)}")
+        self._download()
+        self.behaviour.update(behaviour)
+        bh = self.behaviour
+        W = self.W
+        first = np.asarray(first, dtype=np.int64)
+        first = np.broadcast_to(first.reshape((1, -1)) if first.ndim <= 1 else first, (W, first.shape[-1] if first.ndim else 1))
+        n = first.shape[1]
+        col = lambda x, dt: np.broadcast_to(np.asarray(x, dtype=dt), (n,))
+        count, vm, thr, wd = col(count, np.int64), col(v_max, np.float64), col(goal_threshold, np.float64), col(wander, bool)
+        if goals is not None:
+            goals = np.broadcast_to(np.asarray(goals, dtype=np.float64), (W, n, 2))
+        base = int(self._na.max()) if W else 0
+        ag = np.zeros((W, base + n, AGENT_DOUBLES))
+        agi = np.zeros((W, base + n, AGENT_INTS), dtype=np.int32)
+        for w in range(W):
+            k0 = int(self._na[w])
+            ag[w, :k0], agi[w, :k0] = self._ag[w, :k0], self._agi[w, :k0]
+            nC, nS = int(self._nc[w]), int(self._ns[w])
+            taken = np.zeros(nC + nS, dtype=bool)
+            for f, c in agi[w, :k0, :2]:
+                taken[f:f + c] = True
+            for k in range(n):
+                f, c = int(first[w, k]), int(count[k])
+                if f < 0 or c < 1 or (f < nC and c != 1) or f + c > nC + nS:
+                    raise ValueError(f"agent {k} of world {w}: primitives {f} .. {f + c - 1} do not exist ({nC} circles, {nS} segments)")
+                if self.peer_base >= 0 and f + c > nC + self.peer_base:
+                    raise ValueError("an agent cannot own the peer tail")
+                if taken[f:f + c].any():
+                    raise ValueError(f"agent {k} of world {w}: primitive already owned by an agent")
+                taken[f:f + c] = True
+                if f < nC:
+                    off, R = (0.0, 0.0), float(self._c[w, f, 2])
+                else:
+                    Vx = self._s[w, f - nC:f - nC + c, 0:2]
+                    ctr = Vx.mean(axis=0)
+                    off, R = tuple(ctr - Vx[0]), float(np.sqrt(((Vx - ctr) ** 2).sum(axis=1)).max())
+                if goals is None:
+                    g, draws = wander_goal(bh["seed"], int(bh["world_base"]) + w, f, 0, bh["range_low"], bh["range_high"]), 1
+                else:
+                    g, draws = goals[w, k], 0
+                ag[w, k0 + k] = [g[0], g[1], 0.0, 0.0, off[0], off[1], R, vm[k], thr[k], 0.0]
+                agi[w, k0 + k] = [f, c, int(wd[k]), draws]
+            self._na[w] = k0 + n
+        self._ag, self._agi = ag, agi
+        return base
+
+    @property
+    def agents(self):
+        """dict(rows [W, a_stride, 10] f64, idx [W, a_stride, 4] int32, n [W] int32): the agent tables of include/neupan_amd.h
+        (device tensors once a launch has run, else the host arrays)"""
+        if self._adev is not None:
+            return dict(rows=self._adev[0], idx=self._adev[1], n=self._na)
+        return dict(rows=self._ag, idx=self._agi, n=self._na)
+
+    @property
+    def has_agents(self):
+        return bool(self._na.any())
+
+    def _upload_agents(self):
+        """(rows, idx, n, dirs) device tensors"""
+        if self._adev is None:
+            dev = self.device
+            self._adev = (torch.from_numpy(self._ag).to(dev), torch.from_numpy(self._agi).to(dev), torch.from_numpy(self._na).to(dev),
+                          torch.from_numpy(direction_table(self.behaviour["n_dir"])).to(dev))
+        return self._adev
+
+    def _behave_params(self):
+        bh = self.behaviour
+        n_cand = 3 + int(bh["n_dir"]) * int(bh["n_speed"])
+        if n_cand > behave_max_candidates():
+            raise ValueError(f"{n_cand} candidate velocities, npa_world_behave takes {behave_max_candidates()}")
+        return NpaBehaveParams(float(bh["weight"]), float(bh["horizon"]), float(bh["robot_share"]),
+                               (C.c_double * 2)(*[float(x) for x in bh["range_low"][:2]]),
+                               (C.c_double * 2)(*[float(x) for x in bh["range_high"][:2]]), int(bh["seed"]) & _M64,
+                               int(bh["world_base"]), 0)
+
+    def _behave_args(self, B, st, robot_radius, dt):
+        """the arguments of npa_world_behave up to prev_state, and those behind it up to the stream (held: `self._bpar`)"""
+        c, s, nc, ns = self._upload()
+        ag, agi, na, dirs = self._upload_agents()
+        self._bpar = self._behave_params()
+        bh = self.behaviour
+        return ((B, self.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), ag.shape[1], _ptr(ag), _ptr(agi), _ptr(na),
+                 C.byref(self._bpar), _ptr(st)),
+                (float(robot_radius), self.peer_base if self.peer_base >= 0 else -1, int(bh["n_dir"]), _ptr(dirs), int(bh["n_speed"]),
+                 float(dt)))
+
+    def behave(self, states, prev_states, dt, robot_radius):
+        """Every agent chooses its velocity for the coming step (npa_world_behave: two launches, no host synchronisation).
+        states [B, 3]: the robots' poses; prev_states: their poses one cycle earlier, or None (the robots count as standing);
+        robot_radius: the radius of the disc a robot is to the agents.  With a peer tail the robots' edges are nobody's
+        neighbour (seg_limit = peer_base).  A world without agents: nothing is launched."""
+        if not self.has_agents:
+            return
+        dev = self.device
+        st = self._states(states)
+        pv = None if prev_states is None else self._states(prev_states)
+        B = st.shape[0]
+        if self.W not in (1, B):
+            raise ValueError(f"{self.W} worlds for {B} robots")
+        if pv is not None and pv.shape[0] != B:
+            raise ValueError(f"{pv.shape[0]} earlier poses for {B} robots")
+        head, tail = self._behave_args(B, st, robot_radius, dt)
+        with torch.cuda.device(dev):
+            check(_lib.load().npa_world_behave(*head, _ptr(pv), *tail, _stream(dev)), "npa_world_behave")
+
     def _upload(self):
         if self._dev is None:
             dev = self.device
@@ -110,6 +281,9 @@ class LidarWorld:
         if self._dev is not None:
             self._c, self._s = self._dev[0].cpu().numpy().copy(), self._dev[1].cpu().numpy().copy()
             self._dev = None
+        if self._adev is not None:
+            self._ag, self._agi = self._adev[0].cpu().numpy().copy(), self._adev[1].cpu().numpy().copy()
+            self._adev = None
 
     @property
     def circles(self):
@@ -130,16 +304,24 @@ class LidarWorld:
 
     # ------------------------------------------------------------------ yaml
     @classmethod
-    def from_yaml(cls, env_yaml, seed=0, **kw):
+    def from_yaml(cls, env_yaml, seed=0, behaviours=False, behaviour=None, **kw):
         """The `obstacle:` list of an IR-SIM environment file: shapes circle, rectangle (length along x, width along y, centred
         on the state) and polygon (vertices in the obstacle's frame); distributions manual (the `state` list; a short list
         repeats its last entry, as the shape list does) and random (uniform between range_low and range_high,
-        numpy.random.default_rng(seed)).  Behaviours (rvo, ...) are not simulated: such obstacles stand still."""
+        numpy.random.default_rng(seed)).  Behaviours (rvo, ...) are not simulated by default: such obstacles stand still.
+        behaviours=True: every obstacle of a group with `behavior: {name: 'rvo', ...}` becomes an agent (`add_agents`) with
+        v_max = min(vxmax, vymax) (a `diff` group: capped by vel_max[0]), the group's goal_threshold and wander flag; the wander
+        box is the behaviour's range_low / range_high, `seed` also seeds the wander generator, and the first goals are its
+        draw 0.  Obstacle kinematics and heading are not simulated: every agent is a holonomic disc or a translating polygon.
+        `behaviour`: further parameters for `add_agents` (weight, horizon, robot_share, n_dir, n_speed, ...).  Other behaviour
+        names still warn and stand still."""
         import yaml
         with open(env_yaml) as f:
             doc = yaml.safe_load(f)
         rng = np.random.default_rng(seed)
         circles, segments = [], []
+        made = []                                  # per agent: ("c" | "s", row, count, v_max, goal_threshold, wander)
+        box = None
         for group in doc.get("obstacle") or []:
             number = int(group.get("number", 1))
             shapes = group.get("shape") or []
@@ -158,13 +340,25 @@ class LidarWorld:
                 states = [rng.uniform(lo, hi) for _ in range(number)]
             else:
                 raise ValueError(f"obstacle distribution {dist['name']!r} is not supported (manual, random)")
-            if group.get("behavior"):
+            beh = group.get("behavior")
+            beh = beh[0] if isinstance(beh, (list, tuple)) and beh else beh
+            rvo = bool(behaviours) and isinstance(beh, dict) and beh.get("name") == "rvo"
+            if rvo:
+                vm = min(float(beh.get("vxmax", 1.5)), float(beh.get("vymax", 1.5)))
+                if (group.get("kinematics") or {}).get("name") == "diff" and group.get("vel_max") is not None:
+                    vm = min(vm, float(np.asarray(group["vel_max"], dtype=np.float64).reshape(-1)[0]))
+                thr, wd = float(group.get("goal_threshold", 0.1)), bool(beh.get("wander", False))
+                if box is None and beh.get("range_low") is not None and beh.get("range_high") is not None:
+                    box = ([float(x) for x in beh["range_low"][:2]], [float(x) for x in beh["range_high"][:2]])
+            elif group.get("behavior"):
                 warnings.warn("LidarWorld.from_yaml: obstacle behaviours (rvo, ...) are not simulated; these obstacles get "
                               "zero velocity", stacklevel=2)
             for k, (x, y, th) in enumerate(states):
                 shp = shapes[min(k, len(shapes) - 1)]
                 name = shp.get("name")
                 if name == "circle":
+                    if rvo:
+                        made.append(("c", len(circles), 1, vm, thr, wd))
                     circles.append([x, y, float(shp["radius"]), 0.0, 0.0, 0.0])
                     continue
                 if name == "rectangle":
@@ -176,8 +370,18 @@ class LidarWorld:
                     raise ValueError(f"obstacle shape {name!r} is not supported (circle, rectangle, polygon)")
                 c, s = cos(th), sin(th)
                 Vw = np.stack([c * V[:, 0] - s * V[:, 1] + x, s * V[:, 0] + c * V[:, 1] + y], axis=1)
+                if rvo:
+                    made.append(("s", len(segments), len(Vw), vm, thr, wd))
                 segments.extend(polygon_segments(Vw))
-        return cls(np.array(circles).reshape(-1, 6), np.array(segments).reshape(-1, 6), **kw)
+        world = cls(np.array(circles).reshape(-1, 6), np.array(segments).reshape(-1, 6), **kw)
+        if made:
+            bh = dict(seed=seed)
+            if box is not None:
+                bh["range_low"], bh["range_high"] = box
+            bh.update(behaviour or {})
+            world.add_agents([row + (len(circles) if kind == "s" else 0) for kind, row, *_ in made], [m[2] for m in made],
+                             [m[3] for m in made], [m[4] for m in made], [m[5] for m in made], **bh)
+        return world
 
     # ------------------------------------------------------------------ scan
     def _states(self, states):
@@ -322,6 +526,12 @@ def robot_vertices(robot):
     return np.array([np.linalg.solve(np.stack([G[e - 1], G[e]]), np.array([h[e - 1], h[e]])) for e in range(E)])
 
 
+def robot_radius(robot):
+    """the radius of the disc a Robot is to the world's agents: the circumradius of its polygon about the robot's origin"""
+    V = robot_vertices(robot)
+    return float(np.sqrt((V * V).sum(axis=1)).max())
+
+
 def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=False, certify=False, peers=False,
                     max_points=None, actions=None):
     """example/run_exp.py's loop for the B robots of `fleet` (a FleetPlanner whose paths are set) in `world`:
@@ -361,6 +571,8 @@ def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=Fa
     override = None if actions is None else torch.as_tensor(actions).to(device=dev, dtype=torch.float32)
     extra = {k: sp[k] for k in ("angle_range", "down_sample") if k in sp}
     offset = sp.get("scan_offset", (0.0, 0.0, 0.0))
+    agents = world.has_agents
+    prev, rad = (torch.empty_like(st), robot_radius(fleet.robot)) if agents else (None, 0.0)
     for cyc in range(cycles):
         st_h = st.cpu().numpy()                                 # (the cycle's one read of the poses: forward needs them on the host)
         ranges, bvel, _ = world.scan(st, sp["n_beams"], sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"], offset)
@@ -379,6 +591,9 @@ def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=Fa
         arrive = info["arrive"]
         frozen = (arrive | collided).to(torch.int32)
         act = torch.where(frozen[:, None] != 0, torch.zeros_like(act), act)
+        if agents:                                              # the agents choose: the robots count as standing in the first cycle
+            world.behave(st, prev if cyc > 0 else None, dt, rad)
+            prev.copy_(st)
         st, clr = world.step(st, act, dt, kin, L, frozen=frozen, robot_vertices=V, peers=peers)
         collided = collided | (clr <= 0)
         acts[cyc], stops[cyc], clrs[cyc], hist[cyc + 1] = act, info["stop"], clr, st
@@ -421,14 +636,16 @@ class ResidentLoop:
 
         npa_cycle_progress (path progress, curve switch, arrival latch, poses -> both scan parameter blocks)
         -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states -> npa_forward_batch_flags
-        [-> npa_plan_clearance] -> npa_cycle_act (warm start, stop, action, override, freeze) -> npa_world_step
-        -> npa_cycle_commit (collision latch, log rows)
+        [-> npa_plan_clearance] -> npa_cycle_act (warm start, stop, action, override, freeze)
+        [-> npa_world_behave, when the world has agents] -> npa_world_step -> npa_cycle_commit (collision latch, log rows)
 
     The arguments are `run_closed_loop`'s.  `fleet` must be fresh from `set_paths` (its host bookkeeping -- curve_index, arrived,
     cur_vel -- is not used again: this object owns the device copy, and `fleet.forward` must not be mixed in until the next
     `set_paths`); its adjust parameters must not require gradients (that path is `fleet.forward`'s).  A per-scene block from
     `fleet.set_adjust` is read by the kernels at run time: rewrite it in place between cycles.  `world` must not be rebuilt
-    (add_polygon) while the loop lives: its device arrays are held by address.
+    (add_polygon; add_agents refuses) while the loop lives: its device arrays are held by address.  With agents in the world,
+    `prev_states` [B, 3] holds the poses one cycle earlier (made once, filled by a copy_ in front of npa_world_step; the first
+    cycle passes null: the robots count as standing).
     No priming forward runs here: the first cycle plans from the state a fresh FleetPlanner plans its first cycle from (the
     planner's state record as it is, cur_vel zeros, min_distance as the kernels persist it).
     Columns of the cloud at or beyond n_points[b] keep what an earlier cycle left; the selection and the clearance kernel bound
@@ -578,6 +795,13 @@ class ResidentLoop:
                       _ptr(self.frozen), float(fleet.dt), KIN[kin], float(L), world.bounds, len(V),
                       V.ctypes.data_as(C.POINTER(C.c_double)), world.peer_base if peers else -1, _ptr(self.clearance))
         self._commit = (_ptr(st), _ptr(self.clearance), _ptr(self.collided))
+        # ---- the agents' choice, between act and step (a world without agents: no launch, no buffer)
+        self._behave, self.prev_states = None, None
+        if world.has_agents:
+            self.prev_states = torch.empty_like(st)
+            self._behave = world._behave_args(B, st, robot_radius(fleet.robot), float(fleet.dt))
+            self._prev_ptr = _ptr(self.prev_states)
+            world._held_by_loop = True
         fleet.cur_vel = self.cur_vel                 # (the fleet has planned from here on: a second loop needs set_paths)
 
     # ------------------------------------------------------------------ one cycle
@@ -606,6 +830,8 @@ class ResidentLoop:
                                *self._act_out, la, ls, lc, ln, stream)
         if rc:
             check(rc, "npa_cycle_act")
+        if self._behave is not None:
+            self._issue_behave(self.cycles_done == 0, stream)
         rc = lib.npa_world_step(*self._step, stream)
         if rc:
             check(rc, "npa_world_step")
@@ -616,6 +842,14 @@ class ResidentLoop:
         self.cycles_done += 1
         if (self.cycles_done & 63) == 0:             # (a host read of one pinned word: no synchronisation)
             pan.check_audit()
+
+    def _issue_behave(self, first, stream):
+        """npa_world_behave (first: the robots count as standing), then the poses kept for the next cycle's call"""
+        head, tail = self._behave
+        rc = self._lib.npa_world_behave(*head, None if first else self._prev_ptr, *tail, stream)
+        if rc:
+            check(rc, "npa_world_behave")
+        self.prev_states.copy_(self.states)
 
     def _on_device(self, override, logs, row):
         if torch.cuda.current_device() != self._idx:   # the launches must see the device of the handle

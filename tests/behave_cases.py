@@ -1,0 +1,225 @@
+"""The tables of tests/test_behave.py (the restatement, on the CPU) and tests/test_behave_gpu.py (npa_world_behave).
+
+DECIDED: cases on dyadic inputs, on which every intermediate is exact (or a single correctly rounded operation), with the
+expected result written out as literals.  A case is a dict:
+    worlds   list of dict(circles (C, 6), segments (S, 6), rows (A, 10), idx (A, 4))
+    par      dict(weight, horizon, robot_share, range_low, range_high, seed)
+    robots (B, 3), prev (B, 3) or None, radius, seg_limit, dt, n_speed, dirs
+    expect   per world, per agent: (chosen index, (vx, vy), (gx, gy), draws)
+The candidate table of the decided cases: 4 exact directions, 2 speeds -> 0 zero, 1 v_pref, 2 v_A, 3 - 6 half speed E N W S,
+7 - 10 full speed E N W S.
+"""
+import numpy as np
+
+DIRS4 = np.array([[1.0, 0.0], [0.0, 1.0], [-1.0, 0.0], [0.0, -1.0]])
+FAR = (1024.0, 1024.0, 0.0)                                     # a robot nobody meets within any horizon used here
+
+
+def circle(x, y, r, vx=0.0, vy=0.0):
+    return [x, y, r, vx, vy, 0.0]
+
+
+def seg(ax, ay, bx, by, vx=0.0, vy=0.0):
+    return [ax, ay, bx, by, vx, vy]
+
+
+def agent_row(gx, gy, R=0.5, v_max=1.0, thr=0.25, ox=0.0, oy=0.0, vx=0.0, vy=0.0):
+    return [gx, gy, vx, vy, ox, oy, R, v_max, thr, -1.0]
+
+
+def world(circles=(), segments=(), rows=(), idx=()):
+    return dict(circles=np.array(circles, dtype=np.float64).reshape(-1, 6), segments=np.array(segments, dtype=np.float64).reshape(-1, 6),
+                rows=np.array(rows, dtype=np.float64).reshape(-1, 10), idx=np.array(idx, dtype=np.int32).reshape(-1, 4))
+
+
+def case(name, worlds, expect, robots=(FAR,), prev=None, radius=0.5, seg_limit=-1, weight=1.0, horizon=8.0, share=1.0, seed=11,
+         lo=(-8.0, -8.0), hi=(8.0, 8.0), dt=0.5, n_speed=2, dirs=DIRS4):
+    return dict(name=name, worlds=worlds, expect=expect, robots=np.array(robots, dtype=np.float64).reshape(-1, 3),
+                prev=None if prev is None else np.array(prev, dtype=np.float64).reshape(-1, 3), radius=radius, seg_limit=seg_limit,
+                par=dict(weight=weight, horizon=horizon, robot_share=share, range_low=lo, range_high=hi, seed=seed), dt=dt,
+                n_speed=n_speed, dirs=np.asarray(dirs, dtype=np.float64).reshape(-1, 2))
+
+
+def _one(goal=(4.0, 0.0), circles=(), segments=(), wander=0, draws=7, **kw):
+    """the agent: circle 0 at the origin, r = R = 0.5, v_max 1, goal_threshold 1/4, at rest"""
+    return world([circle(0.0, 0.0, kw.get("R", 0.5))] + list(circles), segments, [agent_row(*goal, **kw)], [[0, 1, wander, draws]])
+
+
+ABOVE = float(np.nextafter(0.25, 1.0))
+BELOW = lambda x: float(np.nextafter(x, 0.0))
+
+DECIDED = [
+    # a lone agent takes its preferred velocity (candidate 7 = (1, 0) costs the same: the tie goes to the lower index)
+    case("lone", [_one()], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]]),
+    # at its goal without wander: index 0, goal and counter untouched
+    case("at_goal", [_one(goal=(0.0, 0.0))], [[(0, (0.0, 0.0), (0.0, 0.0), 7)]]),
+    # at its goal with wander: draw 5 of (seed 11, world 0, agent 0) in the box (-8, 8)^2, counter + 1; then towards it
+    case("at_goal_wander", [_one(goal=(0.125, 0.0), wander=1, draws=5)],
+         [[(1, (-0.849322495078739, 0.5278743215512811), (-7.218176121674855, 4.486269756358599), 6)]]),
+    # L exactly at the threshold is arrived; the next double above it is not (s = min(1, L / dt), dx / L = 1)
+    case("threshold_at", [_one(goal=(0.25, 0.0))], [[(0, (0.0, 0.0), (0.25, 0.0), 7)]]),
+    case("threshold_above", [_one(goal=(ABOVE, 0.0))], [[(1, (ABOVE / 0.5, 0.0), (ABOVE, 0.0), 7)]]),
+    # L < v_max dt: the speed is L / dt, the agent arrives exactly
+    case("no_overshoot", [_one(goal=(0.375, 0.0))], [[(1, (0.75, 0.0), (0.375, 0.0), 7)]]),
+    # a touching circle (c2 == 0, then c2 < 0) ahead: v_pref and every candidate with a component towards it cost +inf, the ones
+    # away from it and the ones along the tangent stay; index 0 (cost |v_pref| = 1) wins over 4 and 6 (sqrt(1.25))
+    case("touching_c2_zero", [_one(circles=[circle(1.0, 0.0, 0.5)])], [[(0, (0.0, 0.0), (4.0, 0.0), 7)]]),
+    case("touching_c2_negative", [_one(circles=[circle(0.75, 0.0, 0.5)])], [[(0, (0.0, 0.0), (4.0, 0.0), 7)]]),
+    # the same, the goal away from the circle: candidate 1 = (-1, 0) has b < 0 and is free
+    case("touching_away", [_one(goal=(-4.0, 0.0), circles=[circle(1.0, 0.0, 0.5)])], [[(1, (-1.0, 0.0), (-4.0, 0.0), 7)]]),
+    # a tangent pass (c = (2, 1), rho = 1, u = (1, 0): disc = 4 - 4 = 0) is a hit at tc = 2: weight 4 makes (1, 0) cost 2, (1/2, 0)
+    # (tc = 4) 1.5, standing 1 -> index 0.  Were it no hit, index 1 would cost 0
+    case("tangent", [_one(circles=[circle(2.0, 1.0, 0.5)])], [[(0, (0.0, 0.0), (4.0, 0.0), 7)]], weight=4.0),
+    # head on, c = (3, 0), rho = 1: tc = 8 / (3 + 1) = 2 at speed 1 and 8 / (1.5 + 0.5) = 4 at speed 1/2.  horizon == tc counts: (1, 0)
+    # costs 4 / 2, (1/2, 0) is beyond the horizon and costs 1/2 -> 3; with the horizon one double below tc (1, 0) is free -> 1
+    case("horizon_at", [_one(circles=[circle(3.0, 0.0, 0.5)])], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], weight=4.0, horizon=2.0),
+    case("horizon_below", [_one(circles=[circle(3.0, 0.0, 0.5)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], weight=4.0, horizon=BELOW(2.0)),
+    # a wall x = 2 approached at right angles: tc = (gap - R) / speed = 1.5 exactly (pinned by the horizon, as above)
+    case("wall_at", [_one(segments=[seg(2.0, -4.0, 2.0, 4.0)])], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], weight=3.0, horizon=1.5),
+    case("wall_below", [_one(segments=[seg(2.0, -4.0, 2.0, 4.0)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], weight=3.0, horizon=BELOW(1.5)),
+    # a candidate parallel to the wall y = 1 does not hit (and misses the end discs)
+    case("wall_parallel", [_one(segments=[seg(-4.0, 1.0, 4.0, 1.0)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], weight=4.0),
+    # a pass beyond the wall's end hits the end disc: R = 5/8, end (3, 3/8): c2 = 8.75, disc = 1/4, tc = 8.75 / 3.5 = 2.5; the
+    # shifted segments span y in [3/8, 4] and are missed.  horizon 2.5: (1, 0) costs 5 / 2.5, (1/2, 0) is beyond it -> 3
+    case("wall_end_disc", [_one(segments=[seg(3.0, 0.375, 3.0, 4.0)], R=0.625)], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], weight=5.0,
+         horizon=2.5),
+    case("wall_end_disc_below", [_one(segments=[seg(3.0, 0.375, 3.0, 4.0)], R=0.625)], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], weight=5.0,
+         horizon=BELOW(2.5)),
+    # the same disc at (3, 0) as a plain circle (alpha 1: tc = 2 > horizon 1 -> free, index 1) and as an agent at rest (alpha 1/2:
+    # u = 2 v', tc = 1 counts, cost 1; (1/2, 0) has tc 2, free, cost 1/2 -> index 3); the other agent stands at its goal
+    case("plain_circle", [_one(circles=[circle(3.0, 0.0, 0.5)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], horizon=1.0),
+    case("agent_circle", [world([circle(0.0, 0.0, 0.5), circle(3.0, 0.0, 0.5)], (), [agent_row(4.0, 0.0), agent_row(3.0, 0.0)],
+                                [[0, 1, 0, 7], [1, 1, 0, 9]])],
+         [[(3, (0.5, 0.0), (4.0, 0.0), 7), (0, (0.0, 0.0), (3.0, 0.0), 9)]], horizon=1.0),
+    # a robot at (3, 0), rho = 1/2 + 1/2: robot_share 1 is the plain circle, 1/2 the agent
+    case("robot_share_1", [_one()], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], robots=[(3.0, 0.0, 0.0)], horizon=1.0, share=1.0),
+    case("robot_share_half", [_one()], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], robots=[(3.0, 0.0, 0.0)], horizon=1.0, share=0.5),
+    # the robot's velocity (state - prev_state) / dt = (-1, 0): u = (2, 0), tc = 1 counts -> 3; a null prev_state: at rest -> 1
+    case("robot_moving", [_one()], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], robots=[(3.0, 0.0, 0.0)], prev=[(3.5, 0.0, 0.0)], horizon=1.0),
+    # n_worlds == batch: world w sees robot w only (robot 0 is in the way, robot 1 far off)
+    case("robots_own", [_one(), _one()], [[(3, (0.5, 0.0), (4.0, 0.0), 7)], [(1, (1.0, 0.0), (4.0, 0.0), 7)]],
+         robots=[(3.0, 0.0, 0.0), FAR], weight=4.0, horizon=2.0),
+    # n_worlds == 1: the agent sees all robots, whichever row the one in the way has
+    case("robots_all_first", [_one()], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], robots=[(3.0, 0.0, 0.0), FAR], weight=4.0, horizon=2.0),
+    case("robots_all_last", [_one()], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], robots=[FAR, FAR, (3.0, 0.0, 0.0)], weight=4.0, horizon=2.0),
+    # seg_limit hides the tail: the wall is segment 1
+    case("seg_limit_hides", [_one(segments=[seg(64.0, 64.0, 65.0, 64.0), seg(2.0, -4.0, 2.0, 4.0)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]],
+         weight=3.0, horizon=1.5, seg_limit=1),
+    case("seg_limit_open", [_one(segments=[seg(64.0, 64.0, 65.0, 64.0), seg(2.0, -4.0, 2.0, 4.0)])], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]],
+         weight=3.0, horizon=1.5, seg_limit=-1),
+    # a polygon agent (the unit square about the origin: segments 1 - 4 of 0 - 5, behind one circle): all four rows get the
+    # velocity, nothing else changes, and it does not see its own edges (it would be inside its own capsules)
+    case("polygon_agent", [world([circle(64.0, 64.0, 0.5)],
+                                 [seg(80.0, 80.0, 81.0, 80.0), seg(-0.5, -0.5, 0.5, -0.5), seg(0.5, -0.5, 0.5, 0.5), seg(0.5, 0.5, -0.5, 0.5),
+                                  seg(-0.5, 0.5, -0.5, -0.5), seg(90.0, 90.0, 91.0, 90.0)],
+                                 [agent_row(4.0, 0.0, R=0.7071067811865476, ox=0.5, oy=0.5)], [[2, 4, 0, 7]])],
+         [[(1, (1.0, 0.0), (4.0, 0.0), 7)]]),
+    # every candidate infinite (a touching circle that closes in at speed 2: c . (v' - apex) > 0 for every |v'| <= 1): index 0
+    case("all_infinite", [_one(circles=[circle(1.0, 0.0, 0.5, -2.0, 0.0)])], [[(0, (0.0, 0.0), (4.0, 0.0), 7)]]),
+]
+
+
+# ---------------------------------------------------------------------------------------------------------------- random worlds
+def directions(n_dir):
+    from math import cos, pi, sin
+    return np.array([[cos(2.0 * pi * k / n_dir), sin(2.0 * pi * k / n_dir)] for k in range(n_dir)], dtype=np.float64).reshape(-1, 2)
+
+
+def random_world(rng, n_agents, n_free_circles, n_free_segments, n_polygon_agents=0, box=6.0, wander=True):
+    """n_agents agents (the first n_polygon_agents of them squares of 4 segments, the rest circles) among free circles and
+    segments, all inside (-box, box)^2 with velocities below 1; agent rows in random order"""
+    n_poly = min(n_polygon_agents, n_agents)
+    n_circ_agents = n_agents - n_poly
+    nC = n_circ_agents + n_free_circles
+    C = np.zeros((nC, 6))
+    C[:, 0:2] = rng.uniform(-box, box, (nC, 2))
+    C[:, 2] = rng.uniform(0.2, 0.8, nC)
+    C[:, 3:5] = rng.uniform(-0.7, 0.7, (nC, 2))
+    S = []
+    for _ in range(n_free_segments):
+        a = rng.uniform(-box, box, 2)
+        b = a + rng.uniform(-4, 4, 2)
+        S.append(seg(a[0], a[1], b[0], b[1], *(rng.uniform(-0.5, 0.5, 2) if rng.random() < 0.3 else (0.0, 0.0))))
+    circle_ids = rng.permutation(nC)[:n_circ_agents]
+    rows, idx = [], []
+    for f in circle_ids:
+        g = rng.uniform(-box, box, 2)
+        rows.append(agent_row(g[0], g[1], R=C[f, 2], v_max=rng.uniform(0.5, 1.5), thr=0.3))
+        idx.append([int(f), 1, int(wander), int(rng.integers(0, 5))])
+    for _ in range(n_poly):
+        c, h = rng.uniform(-box, box, 2), rng.uniform(0.3, 0.7)
+        v = rng.uniform(-0.5, 0.5, 2)
+        V = np.array([[-h, -h], [h, -h], [h, h], [-h, h]]) + c
+        first = nC + len(S)
+        for e in range(4):
+            S.append(seg(*V[e], *V[(e + 1) % 4], *v))
+        ctr = V.mean(axis=0)
+        g = rng.uniform(-box, box, 2)
+        rows.append(agent_row(g[0], g[1], R=float(np.sqrt(((V - ctr) ** 2).sum(axis=1)).max()), v_max=rng.uniform(0.5, 1.5), thr=0.3,
+                              ox=ctr[0] - V[0, 0], oy=ctr[1] - V[0, 1]))
+        idx.append([first, 4, int(wander), int(rng.integers(0, 5))])
+    order = rng.permutation(len(rows))
+    w = world(C, S, [rows[k] for k in order], [idx[k] for k in order])
+    for k in rng.permutation(len(rows))[:max(1, len(rows) // 4)] if len(rows) else []:      # some start at their goal: they redraw
+        f = int(w["idx"][k, 0])
+        anc = w["circles"][f, 0:2] if f < nC else w["segments"][f - nC, 0:2]
+        w["rows"][k, 0:2] = anc + w["rows"][k, 4:6]
+    return w
+
+
+PAR = dict(weight=2.0, horizon=6.0, robot_share=0.5, range_low=(-6.0, -6.0), range_high=(6.0, 6.0), seed=2008)
+
+# (name, n_worlds, agents per world, free circles, free segments, polygon agents, robots (n_worlds == 1), n_dir, n_speed, rng seed)
+# candidates 3 + n_dir n_speed: 3 (no grid), 63, 64 (not a product: 61 + 3 -> 61 x 1), 65 (31 x 2), 131 (32 x 4); neighbours: none,
+# one, the list capacity (64) and one more, mixed kinds; 65 agents: more than one chunk of agent neighbours and a ragged tail
+RANDOM = [
+    ("w1_a1_none", 1, 1, 0, 0, 0, 0, 0, 0, 1),
+    ("w1_a1_one", 1, 1, 1, 0, 0, 0, 20, 3, 2),
+    ("w1_a2_cap", 1, 2, 62, 0, 0, 1, 61, 1, 3),               # 62 circles + 1 agent + 1 robot = 64 discs: the capacity
+    ("w1_a2_cap1", 1, 2, 63, 0, 0, 1, 31, 2, 4),              # one more
+    ("w1_a5_mixed", 1, 5, 7, 9, 2, 3, 32, 4, 5),
+    ("w3_a5_mixed", 3, 5, 6, 70, 1, 0, 20, 3, 6),             # 70 + 4 segments: a second chunk of capsules
+    ("w3_a2", 3, 2, 3, 2, 0, 0, 31, 2, 7),
+    ("w1_a65", 1, 65, 5, 6, 3, 2, 20, 3, 8),
+    ("w3_a65", 3, 65, 0, 3, 0, 0, 61, 1, 9),
+]
+
+
+def random_case(spec):
+    name, W, nA, nc, ns, npoly, nrob, n_dir, n_speed, seed = spec
+    rng = np.random.default_rng(seed)
+    worlds = [random_world(rng, nA, nc, ns, npoly) for _ in range(W)]
+    B = W if W > 1 else max(nrob, 1)
+    robots = np.zeros((B, 3))
+    robots[:, 0:2] = rng.uniform(-6, 6, (B, 2)) if (W > 1 or nrob > 0) else 4096.0
+    prev = robots.copy()
+    prev[:, 0:2] -= rng.uniform(-0.05, 0.05, (B, 2))
+    return dict(name=name, worlds=worlds, robots=robots, prev=prev, radius=0.6, seg_limit=-1, par=dict(PAR), dt=0.1, n_speed=n_speed,
+                dirs=directions(n_dir) if n_dir else np.zeros((0, 2)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- the loops
+LANE = 8.0                    # robot b drives along y = LANE * b, heading +x
+LOOP_BEHAVIOUR = dict(weight=2.0, horizon=5.0, robot_share=0.5, range_low=(0.0, -2.0), range_high=(12.0, 18.0), seed=7, n_dir=20,
+                      n_speed=3)
+
+
+def loop_scenario(B=3):
+    """B robots at (0, LANE b) on straight paths; one shared world of four wander discs (two of them head-on to robots 0 and 2,
+    one crossing robot 1's lane, one that stands at its goal and draws a new one in cycle 0), a polygon agent (a square that
+    comes down robot 1's lane) and a wall below lane 0.  Returns dict(paths, poses, circles, segments, first, count, goals)."""
+    paths = [[np.array([[x], [LANE * b], [0.0], [1.0]]) for x in np.arange(0, 60) * 0.4] for b in range(B)]
+    poses = np.array([[0.0, LANE * b, 0.0] for b in range(B)])
+    circles = np.array([circle(5.0, 0.5, 0.4), circle(6.0, LANE - 2.5, 0.5), circle(4.0, LANE * (B - 1) + 0.25, 0.4), circle(9.0, 4.0, 0.3)])
+    h, c = 0.4, np.array([8.0, LANE + 0.5])
+    V = np.array([[-h, -h], [h, -h], [h, h], [-h, h]]) + c
+    segments = np.array([seg(-2.0, -3.0, 14.0, -3.0)] + [seg(*V[e], *V[(e + 1) % 4]) for e in range(4)])
+    goals = np.array([[-3.0, 0.5], [6.0, LANE + 4.0], [-4.0, LANE * (B - 1)], [9.0, 4.0], [-2.0, LANE]])
+    return dict(paths=paths, poses=poses, circles=circles, segments=segments, first=[0, 1, 2, 3, 4 + 1], count=[1, 1, 1, 1, 4], goals=goals)
+
+
+def loop_world(sc, device="cuda"):
+    from neupan_amd.world import LidarWorld
+    w = LidarWorld(sc["circles"], sc["segments"], device=device)
+    w.add_agents(sc["first"], sc["count"], v_max=1.0, goal_threshold=0.3, wander=True, goals=sc["goals"], **LOOP_BEHAVIOUR)
+    return w
