@@ -696,8 +696,36 @@ int npa_cycle_commit(int batch, int cycle, const double *state, const double *cl
  *   step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t), t = 1, 2, ... the step count; lo / hi: HOST arrays of 8 f32
  *   (null: -inf / +inf), copied into the launch.
  *
- * NPA_E_ARG (before anything touches a device): a null required pointer, batch < 1, cycle < 0, k < 0, receding outside
- *   [1, NPA_MAX_T], a column_mask with bits above 6. */
+ * Rows shared by groups of robots.  The reference tunes ONE parameter set by driving; with npa_lon_reduce and npa_lon_scatter a
+ *   row is trained from the rollouts of every robot that shares it (different corridors, obstacles, start poses, agents):
+ *       ... npa_lon_chain(first) -> npa_lon_reduce -> npa_lon_adam on the G group rows -> npa_lon_scatter
+ *   npa_lon_adam is unchanged: batch = G, tot = gtot, active = gactive, and the group's own gacc, m, v, theta, skipped.
+ *
+ * npa_lon_reduce sums the gradient rows of the robots of a group, one wave (a 64-thread workgroup) per group, in a fixed order.
+ *   The groups are a CSR table: group_first [groups + 1] int32 (group_first[0] = 0), group_members [group_first[groups]] int32,
+ *   robot indices, ascending inside a group.  CONTRACT: every index lies in [0, batch) and a robot appears in at most one
+ *   group (no two waves write one word; the indices are not checked).  Lane l holds column c = l & 7 of slot s = l >> 3.
+ *   For group g let n = group_first[g+1] - group_first[g] and b_j = group_members[group_first[g] + j], j = 0 .. n-1:
+ *     use_j   = active[b_j] != 0 and, for every c in column_mask, (float) tot[b_j][c] is finite (what npa_lon_adam would see);
+ *     x_j[c]  = use_j ? tot[b_j][c] : +0.0                                              for c = 0 .. 6,
+ *     x_j[7]  = (loss != NULL and active[b_j] != 0) ? (double) loss[b_j] : +0.0;
+ *     slot sums: a_s[c] = +0.0, then for j = s, s + 8, s + 16, ... < n in that order a_s[c] = a_s[c] + x_j[c] -- ceil(n / 8)
+ *             trips for the whole wave; a slot whose j is past the end reads the last member again and adds +0.0;
+ *     combine: a_s = a_s + a_{s+4} for s < 4, then a_s = a_s + a_{s+2} for s < 2, then a_0 = a_0 + a_1 (the lower slot is the
+ *             left operand), every addition one rounded f64 operation;
+ *     n_used[g] = #{j: use_j};  dropped[g] += #{j: active[b_j] != 0 and not use_j} (cumulative);  gactive[g] = n_used[g] > 0;
+ *     gtot[g][c] = (mean != 0 and n_used[g] > 0) ? a_0[c] / (double) n_used[g] : a_0[c] for c = 0 .. 6 (gtot [G][8] f64;
+ *             gtot[g][7] is not written);  gloss[g] = a_0[7] (f64, nullable; a sum, never divided);
+ *     tot[b_j][c] = 0 for c = 0 .. 6 of every member, used or not, as npa_lon_adam clears behind its read.
+ *   Column 7 of tot keeps its bits; rows of robots in no group are untouched.  An empty group: gactive 0, n_used 0, the sums
+ *   +0.0, dropped unchanged.
+ *
+ * npa_lon_scatter is the way back, one thread per robot: with g = group_of[b] (group_of [B] int32), when 0 <= g < groups
+ *   theta[b][c] = group_theta[g][c] for c = 0 .. 6 (group_theta [G][8], theta [B][8] f32); any other g (-1: a robot that keeps
+ *   a fixed row of its own) leaves the row as it is.  Column 7 is never written.
+ *
+ * NPA_E_ARG (before anything touches a device): a null required pointer, batch < 1, groups < 1, cycle < 0, k < 0, receding
+ *   outside [1, NPA_MAX_T], a column_mask with bits above 6. */
 int npa_lon_loss(int batch, int receding, int cycle, const double *state, double *last_xy, const float *opt_d,
                  const float *min_distance, const uint8_t *stop, const int32_t *arrived, const int32_t *collided,
                  float collision_threshold, double stuck_threshold, int stuck_patience, float loss_weight,
@@ -711,6 +739,10 @@ int npa_lon_adam(int batch, int column_mask, int accumulate, double *tot, float 
                  float *theta, const int32_t *active, float beta1, float one_minus_beta1, float beta2,
                  float one_minus_beta2, float step_size, float bc2_sqrt, float eps, const float *lo, const float *hi,
                  int32_t *skipped, void *stream);
+int npa_lon_reduce(int batch, int groups, int column_mask, int mean, const int32_t *group_first,
+                   const int32_t *group_members, double *tot, const int32_t *active, const float *loss, double *gtot,
+                   int32_t *gactive, int32_t *n_used, int32_t *dropped, double *gloss, void *stream);
+int npa_lon_scatter(int batch, int groups, const int32_t *group_of, const float *group_theta, float *theta, void *stream);
 
 /* ---- DUNE training labels (offline) ---------------------------------------------------------------
  * npa_dune_labels replaces DUNETrain.prob_solve / generate_data_set

@@ -12,7 +12,8 @@ _LAZY = {"PAN": ("pan", "PAN"), "forward_interleaved": ("pan", "forward_interlea
          "scan_to_point_velocity_batch": ("frontend", "scan_to_point_velocity_batch"),
          "DuneTrain": ("dune_train", "DuneTrain"), "neupan": ("planner", "neupan"),
          "InputPipeline": ("ingest", "InputPipeline"), "LonLoop": ("lon", "LonLoop"),
-         "train_closed_loop": ("lon", "train_closed_loop"), "lon_loss": ("lon", "lon_loss"), "lon_adam": ("lon", "lon_adam")}      # (dune_labels.dune_labels: import it from its module)
+         "train_closed_loop": ("lon", "train_closed_loop"), "lon_loss": ("lon", "lon_loss"), "lon_adam": ("lon", "lon_adam"),
+         "lon_reduce": ("lon", "lon_reduce"), "lon_scatter": ("lon", "lon_scatter"), "group_table": ("lon", "group_table")}      # (dune_labels.dune_labels: import it from its module)
 
 
 def __getattr__(name):

@@ -99,6 +99,8 @@ SYMBOLS = {
     "npa_lon_loss": (_I, [_I, _I, _I] + [_P] * 7 + [C.c_float, C.c_double, _I, C.c_float, C.c_float] + [_P] * 11 + [_P]),
     "npa_lon_chain": (_I, [_I, _I, _I] + [_P] * 8 + [_P]),
     "npa_lon_adam": (_I, [_I, _I, _I] + [_P] * 6 + [C.c_float] * 7 + [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),
+    "npa_lon_reduce": (_I, [_I, _I, _I, _I] + [_P] * 10 + [_P]),
+    "npa_lon_scatter": (_I, [_I, _I, _P, _P, _P, _P]),
     "npa_dune_labels": (_I, [_I, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "npa_profile_enable": (_I, [_P, _I]),
     "npa_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -1,16 +1,20 @@
 // Training the NRMP adjust parameters inside the device-resident closed loop (gfx950 only): what example/LON/LON_corridor.py does
-// on the host between its planner call and the next one, as three launches behind npa_cycle_commit.
+// on the host between its planner call and the next one, as three launches behind npa_cycle_commit -- and, where groups of
+// robots share a parameter row, two more around the Adam step.
 //   lon_loss_kernel   stuck bookkeeping, the distance loss and its upstream gradient, the episode's end   LON_corridor.py:10-19, :62-82, :102
 //   lon_chain_kernel  the body of the gradient chain through the PAN iterations                           pan.py (_grad_backward_rows)
 //   lon_adam_kernel   torch.optim.Adam.step and zero_grad, one parameter row per robot                    LON_corridor.py:41, :94-95, :127
+//   lon_reduce_kernel   the gradient rows of a group's robots summed into the group's row, one wave per group, fixed order
+//   lon_scatter_kernel  a group's parameter row copied to the rows of its robots
 // The launch sequence of one cycle (neupan_amd.lon.LonLoop), on one stream:
 //   npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states
 //   -> npa_forward_begin, K x { cur_s, cur_u -> snapshot k; npa_forward_iter(k); mu, lam, pts, count -> snapshot k }, npa_forward_end
 //   -> npa_cycle_act (override_row = the loop's override buffer) -> npa_world_step -> npa_cycle_commit
 //   -> npa_lon_loss
 //   -> for k = K-1 .. first: npa_nrmp_backward(snapshot k, gs, gu, gd) -> npa_lon_chain(k)
-//   -> npa_lon_adam(t)
-// One thread per robot, no workspace, no atomics, no device-side counter; handle-free and stream-ordered like cycle.hip.  Every
+//   -> npa_lon_adam(t)                                                 (one row per robot), or
+//   -> npa_lon_reduce -> npa_lon_adam(t) on the G group rows -> npa_lon_scatter        (rows shared by groups of robots)
+// One thread per robot (lon_reduce_kernel: one wave per group), no workspace, no atomics, no device-side counter; handle-free and stream-ordered like cycle.hip.  Every
 // per-robot decision is a select and every loop bound a launch argument.  Every arithmetic statement is ONE IEEE operation in
 // a stated order (contraction is off for the whole file), so numpy float32 / float64 restates the kernels bit for bit and a
 // host-paced loop that calls the same exports gives the same bits.
@@ -146,6 +150,72 @@ __global__ __launch_bounds__(LON_THREADS) void lon_adam_kernel(
   }
 }
 
+// One wave per group: lane l holds column c = l & 7 of slot s = l >> 3, so the 64-byte tot row of a robot is one load of 8
+// lanes.  Slot s sums the members s, s + 8, s + 16, ... in that order (the trip count ceil(n / 8) is the same for the whole wave:
+// the offsets are read through readfirstlane), then slots 4..7 are added to 0..3, 2..3 to 0..1, 1 to 0, the lower slot on the
+// left.  A lane past the end of the group reads the last member again and adds +0.0.  Column 7 carries the loss.
+__global__ __launch_bounds__(LON_THREADS) void lon_reduce_kernel(
+    int mask, int mean, const int* __restrict__ group_first, const int* __restrict__ group_members, double* __restrict__ tot,
+    const int* __restrict__ active, const float* __restrict__ loss, double* __restrict__ gtot, int* __restrict__ gactive,
+    int* __restrict__ n_used, int* __restrict__ dropped, double* __restrict__ gloss) {
+  const int g = blockIdx.x;
+  const int lane = threadIdx.x, c = lane & 7, s = lane >> 3;
+  const int first = __builtin_amdgcn_readfirstlane(group_first[g]);
+  const int n = __builtin_amdgcn_readfirstlane(group_first[g + 1]) - first;
+  const int trips = (n + 7) >> 3;
+  const bool in_mask = ((mask >> c) & 1) != 0;                       // (bit 7 is never set: the loss column always passes)
+  const bool has_loss = loss != nullptr;                             // (uniform: a launch argument)
+  double a = 0.0;
+  int used = 0, drop = 0;
+  for (int i = 0; i < trips; ++i) {
+    const int j = i * 8 + s;
+    const bool in = j < n;
+    const int b = group_members[first + (in ? j : n - 1)];
+    const size_t r = (size_t)b * 8 + c;
+    const double t = tot[r];
+    const bool on = active[b] != 0;
+    const float lv = has_loss ? loss[b] : 0.f;
+    const bool ok = !in_mask || __builtin_isfinite((float)t);       // what npa_lon_adam would see of this entry
+    const unsigned long long oks = __ballot(ok);
+    const bool fin = ((oks >> (s * 8)) & 0xffull) == 0xffull;        // ... of the whole row
+    const bool use = in && on && fin;
+    const double xg = use ? t : 0.0;
+    const double xl = (in && on && has_loss) ? (double)lv : 0.0;
+    const double x = c == 7 ? xl : xg;
+    a = a + x;
+    used += __popcll(__ballot(use && c == 0));
+    drop += __popcll(__ballot(in && on && !fin && c == 0));
+    tot[r] = c == 7 ? t : 0.0;                                       // cleared behind the read; column 7 keeps its bits
+  }
+  a = a + __shfl_down(a, 32);
+  a = a + __shfl_down(a, 16);
+  a = a + __shfl_down(a, 8);
+  const double q = a / (double)(used > 0 ? used : 1);
+  const double out = (mean != 0 && used > 0) ? q : a;
+  if (lane < LON_COLS) gtot[(size_t)g * 8 + lane] = out;
+  if (lane == 7 && gloss) gloss[g] = a;
+  if (lane == 0) {
+    gactive[g] = used > 0 ? 1 : 0;
+    n_used[g] = used;
+    dropped[g] = dropped[g] + drop;
+  }
+}
+
+__global__ __launch_bounds__(LON_THREADS) void lon_scatter_kernel(
+    int batch, int groups, const int* __restrict__ group_of, const float* __restrict__ group_theta, float* __restrict__ theta) {
+  const int b = blockIdx.x * LON_THREADS + threadIdx.x;
+  if (b >= batch) return;
+  const int g = group_of[b];
+  const bool member = g >= 0 && g < groups;
+  const float* src = group_theta + (size_t)(member ? g : 0) * 8;
+  float* dst = theta + (size_t)b * 8;
+#pragma unroll
+  for (int c = 0; c < LON_COLS; ++c) {
+    const float old = dst[c], nw = src[c];
+    dst[c] = member ? nw : old;
+  }
+}
+
 }  // namespace
 
 extern "C" int npa_lon_loss(int batch, int receding, int cycle, const double* state, double* last_xy, const float* opt_d,
@@ -192,6 +262,27 @@ extern "C" int npa_lon_adam(int batch, int column_mask, int accumulate, double* 
   hipLaunchKernelGGL(lon_adam_kernel, dim3((batch + LON_THREADS - 1) / LON_THREADS), dim3(LON_THREADS), 0, (hipStream_t)stream,
                      batch, column_mask, accumulate, tot, gacc, m, v, theta, active, beta1, one_minus_beta1, beta2,
                      one_minus_beta2, step_size, bc2_sqrt, eps, bounds, skipped);
+  HIP_TRY(hipGetLastError());
+  return NPA_OK;
+}
+
+extern "C" int npa_lon_reduce(int batch, int groups, int column_mask, int mean, const int32_t* group_first,
+                              const int32_t* group_members, double* tot, const int32_t* active, const float* loss, double* gtot,
+                              int32_t* gactive, int32_t* n_used, int32_t* dropped, double* gloss, void* stream) {
+  if (batch < 1 || groups < 1 || !group_first || !group_members || !tot || !active || !gtot || !gactive || !n_used || !dropped)
+    return fail(NPA_E_ARG, "npa_lon_reduce: bad argument");
+  if (column_mask < 0 || column_mask > 0x7f) return fail(NPA_E_ARG, "npa_lon_reduce: the column mask has bits above 6");
+  hipLaunchKernelGGL(lon_reduce_kernel, dim3(groups), dim3(LON_THREADS), 0, (hipStream_t)stream, column_mask, mean, group_first,
+                     group_members, tot, active, loss, gtot, gactive, n_used, dropped, gloss);
+  HIP_TRY(hipGetLastError());
+  return NPA_OK;
+}
+
+extern "C" int npa_lon_scatter(int batch, int groups, const int32_t* group_of, const float* group_theta, float* theta,
+                               void* stream) {
+  if (batch < 1 || groups < 1 || !group_of || !group_theta || !theta) return fail(NPA_E_ARG, "npa_lon_scatter: bad argument");
+  hipLaunchKernelGGL(lon_scatter_kernel, dim3((batch + LON_THREADS - 1) / LON_THREADS), dim3(LON_THREADS), 0, (hipStream_t)stream,
+                     batch, groups, group_of, group_theta, theta);
   HIP_TRY(hipGetLastError());
   return NPA_OK;
 }

@@ -16,9 +16,15 @@ QP and takes an Adam step; the episode ends on arrive, stop or stuck.  Here:
       -> for k = K-1 .. first: npa_nrmp_backward(snapshot k, gs, gu, gd) -> npa_lon_chain(k)
       -> npa_lon_adam(t)
 
+  With `groups` a parameter row is shared by a group of robots and trained from the rollouts of all of them -- the reference's
+  one tuned set, at scale.  The tail of the cycle is then
+
+      ... npa_lon_chain(first) -> npa_lon_reduce -> npa_lon_adam(t) on the G group rows -> npa_lon_scatter
+
 * `train_closed_loop`  the same cycle paced by the host: FleetPlanner.forward(adjust=theta) -> the loss as torch operations ->
                        backward() into theta.grad -> the Adam step; it is to `LonLoop` what `run_closed_loop` is to `ResidentLoop`.
-* `lon_loss`, `lon_adam`  thin wrappers of the two exports both loops share.
+* `lon_loss`, `lon_adam`, `lon_reduce`, `lon_scatter`  thin wrappers of the exports both loops share; `group_table` builds the
+                       tables of the last two on the host.
 
 The rules (csrc/lon.hip, include/neupan_amd.h) are stated as single IEEE operations in a fixed order, so the two loops give the
 same bits.  There is no CPU fallback.
@@ -153,6 +159,92 @@ def lon_adam(theta, tot, gacc, m, v, active, skipped, t, mask, lr=5e-3, betas=(0
     return theta
 
 
+def group_table(groups, B, G=None):
+    """`groups`: B integers, robot b's group number in -1 .. G-1 (-1: the robot keeps a fixed row of its own and trains nothing --
+    a baseline beside the trained ones) -> (group_of [B] int32, group_first [G+1] int32, group_members int32): the tables of
+    npa_lon_scatter and npa_lon_reduce (CSR, robot indices ascending inside a group), numpy arrays built on the host.  G: the
+    number of groups (default: the largest number + 1, at least 1); every group number may be empty."""
+    a = np.asarray(groups.cpu() if isinstance(groups, torch.Tensor) else groups)
+    if a.dtype.kind not in "iu" and not (a.dtype.kind == "f" and a.size and np.all(a == np.round(a))):
+        raise ValueError("groups must be integers")
+    if a.ndim != 1 or a.shape[0] != int(B) or B < 1:
+        raise ValueError(f"groups must be {B} group numbers, not an array of shape {list(a.shape)}")
+    a = a.astype(np.int64)
+    n = max(int(a.max()) + 1, 1) if G is None else int(G)
+    if n < 1 or int(a.min()) < -1 or int(a.max()) >= n:
+        raise ValueError(f"group numbers must lie in -1 .. {n - 1}")
+    member = np.nonzero(a >= 0)[0]
+    order = member[np.argsort(a[member], kind="stable")]             # (by group; ascending robot index inside a group)
+    first = np.zeros(n + 1, dtype=np.int32)
+    first[1:] = np.cumsum(np.bincount(a[member], minlength=n))
+    return a.astype(np.int32), first, order.astype(np.int32)
+
+
+def _group_tables(groups, B, dev):
+    """group_table on the device: (G, group_of, group_first, group_members (at least one entry), the lowest member per group)"""
+    of, first, members = group_table(groups, B)
+    G = first.shape[0] - 1
+    lowest = np.array([members[first[g]] if first[g + 1] > first[g] else -1 for g in range(G)], dtype=np.int64)
+    pad = members if members.size else np.zeros(1, dtype=np.int32)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    return G, up(of), up(first), up(pad), lowest
+
+
+def _group_rows(theta, lowest):
+    """the (G, 8) block the groups start from: the row of each group's lowest-numbered member (an empty group: zeros)"""
+    rows = torch.zeros((len(lowest), 8), dtype=torch.float32, device=theta.device)
+    for g, b in enumerate(lowest):
+        if b >= 0:
+            rows[g].copy_(theta[int(b)])
+    return rows
+
+
+def lon_reduce(tot, active, group_first, group_members, mask, mean=True, loss=None, dropped=None, want_loss=True):
+    """npa_lon_reduce on the current stream: the gradient rows tot [B, 8] f64 of every group's robots (cleared behind the read)
+    summed in the header's fixed order; active [B] int32, loss [B] f32 or None; group_first [G+1], group_members int32 device
+    tensors (`group_table`; every index in [0, B), a robot in at most one group); dropped [G] int32 is updated in place
+    (default: zeros).  Returns dict(gtot [G, 8] f64, gactive, n_used, dropped [G] int32, gloss [G] f64 or None)."""
+    B, dev = tot.shape[0], tot.device
+    i32, f64 = torch.int32, torch.float64
+    _want(tot, f64, (B, 8), "tot"); _want(active, i32, (B,), "active")
+    if loss is not None:
+        _want(loss, torch.float32, (B,), "loss")
+    if not isinstance(group_first, torch.Tensor) or group_first.dim() != 1 or group_first.shape[0] < 2:
+        raise ValueError("group_first must be a device tensor of G + 1 offsets")
+    G = group_first.shape[0] - 1
+    _want(group_first, i32, (G + 1,), "group_first")
+    if not isinstance(group_members, torch.Tensor) or group_members.dim() != 1 or group_members.shape[0] < 1:
+        raise ValueError("group_members must be a device tensor of at least one entry")
+    _want(group_members, i32, (group_members.shape[0],), "group_members")
+    if dropped is None:
+        dropped = torch.zeros((G,), dtype=i32, device=dev)
+    _want(dropped, i32, (G,), "dropped")
+    out = dict(gtot=torch.zeros((G, 8), dtype=f64, device=dev), gactive=torch.empty((G,), dtype=i32, device=dev),
+               n_used=torch.empty((G,), dtype=i32, device=dev), dropped=dropped,
+               gloss=torch.empty((G,), dtype=f64, device=dev) if want_loss else None)
+    with torch.cuda.device(dev):
+        check(_lib.load().npa_lon_reduce(B, G, int(mask), 1 if mean else 0, _ptr(group_first), _ptr(group_members), _ptr(tot),
+                                         _ptr(active), None if loss is None else _ptr(loss), _ptr(out["gtot"]), _ptr(out["gactive"]),
+                                         _ptr(out["n_used"]), _ptr(dropped), None if out["gloss"] is None else _ptr(out["gloss"]),
+                                         _stream(dev)), "npa_lon_reduce")
+    return out
+
+
+def lon_scatter(theta, group_theta, group_of):
+    """npa_lon_scatter on the current stream: theta [B, 8] f32 row b <- group_theta [G, 8] row group_of[b] (columns 0 .. 6),
+    in place; group_of [B] int32, a number outside 0 .. G-1 leaves the row as it is."""
+    B = theta.shape[0]
+    _want(theta, torch.float32, (B, 8), "theta"); _want(group_of, torch.int32, (B,), "group_of")
+    if not isinstance(group_theta, torch.Tensor) or group_theta.dim() != 2 or group_theta.shape[0] < 1:
+        raise ValueError("group_theta must be a [G, 8] device tensor")
+    G = group_theta.shape[0]
+    _want(group_theta, torch.float32, (G, 8), "group_theta")
+    with torch.cuda.device(theta.device):
+        check(_lib.load().npa_lon_scatter(B, G, _ptr(group_of), _ptr(group_theta), _ptr(theta), _stream(theta.device)),
+              "npa_lon_scatter")
+    return theta
+
+
 class LonLoop(ResidentLoop):
     """`ResidentLoop` that trains: one parameter row per robot, one Adam step per robot and cycle, everything on the device (the
     launch sequence: this module's header).  `fleet` as for ResidentLoop (fresh from `set_paths`); `theta0` (B, 7) or (B, 8): the
@@ -164,11 +256,19 @@ class LonLoop(ResidentLoop):
     `t`, the step count of the bias correction, counts cycles since construction and is not reset, as an optimiser object's.
     Attributes besides ResidentLoop's (device tensors, the same objects for the life of the loop): theta, m, v, gacc [B, 8] f32,
     loss [B] f32, active, ended, stuck_count, skipped (steps refused for a non-finite gradient), bad (re-solves whose status
-    was not 0) [B] int32, override [B, 2] f32."""
+    was not 0) [B] int32, override [B, 2] f32.
+    groups: None (one row per robot), or B group numbers in -1 .. G-1 (`group_table`): the robots of a group share one row,
+    trained from the gradients of all of them -- summed (group_mean=False) or averaged over the robots that contributed
+    (group_mean=True) in npa_lon_reduce's fixed order; -1 keeps the robot's own row fixed.  `theta0` stays (B, 7 | 8): a group
+    starts from the row of its lowest-numbered member, and `theta` stays the [B, 8] block on the fleet, rewritten by
+    npa_lon_scatter after every step.  Then the optimiser state is the group's -- group_theta, group_m, group_v, group_gacc
+    [G, 8] f32, group_active, group_skipped, group_used (members that contributed to the last step), group_dropped (members
+    left out for a non-finite gradient, cumulative) [G] int32, group_loss [G] f64 (the sum of the members' losses) -- and the
+    per-robot m, v, gacc and skipped stay zero."""
 
     def __init__(self, fleet, world, states, theta0, train=("p_u", "eta", "d_max"), lr=5e-3, betas=(0.9, 0.999), eps=1e-8,
                  loss_weight=10.0, loss_offset=50.0, stuck_threshold=0.01, stuck_patience=5, accumulate=True, bounds=None,
-                 scan=None, point_velocities=False, peers=False, max_points=None):
+                 scan=None, point_velocities=False, peers=False, max_points=None, groups=None, group_mean=True):
         if getattr(fleet, "B", 0) < 1:
             raise ValueError("LonLoop: the fleet has no paths (set_paths first)")
         pan = fleet.pan
@@ -183,6 +283,11 @@ class LonLoop(ResidentLoop):
         theta = adjust_block(theta0, fleet.B, world.device)
         if getattr(pan, "_untrained", False) or not pan._h.value:
             raise NeupanAmdError("LonLoop: the planner has no kernel handle (no DUNE checkpoint yet)")
+        self.G, self.group_mean = 0, bool(group_mean)
+        if groups is not None:
+            self.G, self.group_of, self._group_first, self._group_members, lowest = _group_tables(groups, fleet.B, world.device)
+            self.group_theta = _group_rows(theta, lowest)
+            lon_scatter(theta, self.group_theta, self.group_of)
         fleet.set_adjust(theta)
         super().__init__(fleet, world, states, scan=scan, point_velocities=point_velocities, certify=False, peers=peers,
                          max_points=max_points)
@@ -208,6 +313,12 @@ class LonLoop(ResidentLoop):
         for key, snap in self._snap.items():
             assert tuple(self._views[key].shape) == tuple(snap.shape[1:]), key
         self.K = K
+        if self.G:
+            G = self.G
+            self.group_m, self.group_v, self.group_gacc = zeros((G, 8), f32), zeros((G, 8), f32), zeros((G, 8), f32)
+            self.group_active, self.group_skipped = zeros((G,), i32), zeros((G,), i32)
+            self.group_used, self.group_dropped = zeros((G,), i32), zeros((G,), i32)
+            self.group_loss, self._gtot = zeros((G,), f64), zeros((G, 8), f64)
         # ---- what reset() restores
         c, s = self._held[2], self._held[3]
         self._saved = (self.states.clone(), c.clone(), s.clone(), self.cur_off.clone(), self.cur_len.clone())
@@ -289,11 +400,28 @@ class LonLoop(ResidentLoop):
             if rc:
                 check(rc, "npa_lon_chain")
         self.t += 1
-        rc = lib.npa_lon_adam(B, self.mask, 1 if self.accumulate else 0, _ptr(self._tot), _ptr(self.gacc), _ptr(self.m),
-                              _ptr(self.v), _ptr(self.theta), _ptr(self.active), *_adam_scalars(self.t, self.lr, self.betas, self.eps),
-                              self._lo, self._hi, _ptr(self.skipped), stream)
-        if rc:
-            check(rc, "npa_lon_adam")
+        if self.G:
+            G = self.G
+            rc = lib.npa_lon_reduce(B, G, self.mask, 1 if self.group_mean else 0, _ptr(self._group_first), _ptr(self._group_members),
+                                    _ptr(self._tot), _ptr(self.active), _ptr(self.loss), _ptr(self._gtot), _ptr(self.group_active),
+                                    _ptr(self.group_used), _ptr(self.group_dropped), _ptr(self.group_loss), stream)
+            if rc:
+                check(rc, "npa_lon_reduce")
+            rc = lib.npa_lon_adam(G, self.mask, 1 if self.accumulate else 0, _ptr(self._gtot), _ptr(self.group_gacc),
+                                  _ptr(self.group_m), _ptr(self.group_v), _ptr(self.group_theta), _ptr(self.group_active),
+                                  *_adam_scalars(self.t, self.lr, self.betas, self.eps), self._lo, self._hi,
+                                  _ptr(self.group_skipped), stream)
+            if rc:
+                check(rc, "npa_lon_adam")
+            rc = lib.npa_lon_scatter(B, G, _ptr(self.group_of), _ptr(self.group_theta), _ptr(self.theta), stream)
+            if rc:
+                check(rc, "npa_lon_scatter")
+        else:
+            rc = lib.npa_lon_adam(B, self.mask, 1 if self.accumulate else 0, _ptr(self._tot), _ptr(self.gacc), _ptr(self.m),
+                                  _ptr(self.v), _ptr(self.theta), _ptr(self.active), *_adam_scalars(self.t, self.lr, self.betas, self.eps),
+                                  self._lo, self._hi, _ptr(self.skipped), stream)
+            if rc:
+                check(rc, "npa_lon_adam")
         pan._last, pan.last_out = self._pan_last, self.out
         self._first = False
         self.cycles_done += 1
@@ -320,7 +448,8 @@ class LonLoop(ResidentLoop):
     def episode(self, cycles, actions=None):
         """`cycles` training cycles from where the loop stands (`reset` starts the robots over); returns run_closed_loop's dict
         plus loss [cycles, B] f32, stuck and ended [cycles, B] bool (after each cycle) and theta [cycles, B, 8] f32 (after each
-        cycle's step).  The logs are allocated here, once; nothing is read back."""
+        cycle's step) -- and, with groups, group_theta [cycles, G, 8] f32, group_loss [cycles, G] f64 and group_used [cycles, G]
+        int32 (after each cycle's step).  The logs are allocated here, once; nothing is read back."""
         B, T, dev = self.B, self.T, self.device
         cycles = int(cycles)
         f32, f64 = torch.float32, torch.float64
@@ -341,15 +470,25 @@ class LonLoop(ResidentLoop):
             if tuple(override.shape) != (cycles, B, 2):
                 raise ValueError(f"actions must be [{cycles}, {B}, 2], not {list(override.shape)}")
         logs = tuple(_ptr(t) for t in (acts, stops, ctrl, npt, hist, clrs, loss, stuck, ended)) if cycles > 0 else None
+        if self.G:
+            gth = torch.zeros((cycles, self.G, 8), dtype=f32, device=dev)
+            gls = torch.zeros((cycles, self.G), dtype=f64, device=dev)
+            gus = torch.zeros((cycles, self.G), dtype=torch.int32, device=dev)
         for i in range(cycles):
             self._on_device(override[i] if override is not None else None, logs, i)
             thetas[i].copy_(self.theta)
-        return dict(states=hist, actions=acts, arrive=self.arrived != 0, stop=stops, collided=self.collided != 0, clearance=clrs,
-                    controls=ctrl, n_points=npt, loss=loss, stuck=stuck, ended=ended, theta=thetas)
+            if self.G:
+                gth[i].copy_(self.group_theta); gls[i].copy_(self.group_loss); gus[i].copy_(self.group_used)
+        out = dict(states=hist, actions=acts, arrive=self.arrived != 0, stop=stops, collided=self.collided != 0, clearance=clrs,
+                   controls=ctrl, n_points=npt, loss=loss, stuck=stuck, ended=ended, theta=thetas)
+        if self.G:
+            out.update(group_theta=gth, group_loss=gls, group_used=gus)
+        return out
 
     def reset(self):
         """Start every robot over -- poses, path state, latches, warm start, stuck counters, the accumulated gradients, the
-        planner's state record, the world -- without touching theta, m, v or t.  copy_ / zero_ / fill_ only."""
+        planner's state record, the world -- without touching theta, m, v or t (nor, with groups, group_theta, group_m, group_v; the
+        groups' accumulated gradients are cleared too).  copy_ / zero_ / fill_ only."""
         st0, c0, s0, off0, len0 = self._saved
         self.states.copy_(st0)
         self.last_xy.copy_(st0[:, :2])
@@ -361,13 +500,16 @@ class LonLoop(ResidentLoop):
         for t in (self.curve_index, self.point_index, self.arrived, self.collided, self._curve_arrived, self.cur_vel,
                   self.stuck_count, self.ended, self.gacc, self._tot, self.fleet.pan._state):
             t.zero_()
+        if self.G:
+            self.group_gacc.zero_(); self._gtot.zero_()
         self.override.fill_(nan)
         self._first = True
 
 
 def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train=("p_u", "eta", "d_max"), lr=5e-3,
                       betas=(0.9, 0.999), eps=1e-8, loss_weight=10.0, loss_offset=50.0, stuck_threshold=0.01, stuck_patience=5,
-                      accumulate=True, bounds=None, scan=None, point_velocities=False, peers=False, max_points=None, actions=None):
+                      accumulate=True, bounds=None, scan=None, point_velocities=False, peers=False, max_points=None, actions=None,
+                      groups=None, group_mean=True):
     """One episode of `LonLoop`'s cycle paced by the host, for a fleet fresh from `set_paths` in a fresh `world`:
 
         scan -> scan_to_point[_velocity]_batch -> fleet.forward(adjust=theta) -> LidarWorld.step -> the loss (torch operations
@@ -376,7 +518,10 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
     `theta`: the (B, 8) float32 device block (`adjust_block`), stepped in place; `opt_state`: what `adam_state` made (m, v, t,
     skipped, bad), carried from episode to episode and updated in place (default: a fresh one).  The other arguments are
     LonLoop's and run_closed_loop's.  The host reads the device several times per cycle (fleet.forward's bookkeeping, the
-    gradient chain's flags).  Returns the dict LonLoop.episode returns."""
+    gradient chain's flags).  Returns the dict LonLoop.episode returns.
+    With `groups` (LonLoop's argument) the tail is lon_reduce -> lon_adam on the G group rows -> lon_scatter: `opt_state` comes
+    from `adam_state(G, dev)` (the loop adds "dropped" [G] and "robot_bad" [B] to it; its "bad" is not used), every group
+    takes the row of its lowest-numbered member of `theta` and the scatter runs once in front of the first cycle."""
     sp = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0)
     sp.update(scan or {})
     dev = world.device
@@ -388,7 +533,18 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
     B, T = st.shape[0], fleet.T
     f32, f64, i32 = torch.float32, torch.float64, torch.int32
     _want(theta, f32, (B, 8), "theta")
-    opt = adam_state(B, dev) if opt_state is None else opt_state
+    G = 0
+    if groups is not None:
+        G, group_of, group_first, group_members, lowest = _group_tables(groups, B, dev)
+        group_theta = _group_rows(theta, lowest)
+        lon_scatter(theta, group_theta, group_of)
+    opt = adam_state(G or B, dev) if opt_state is None else opt_state
+    if G:
+        opt.setdefault("dropped", torch.zeros((G,), dtype=i32, device=dev))
+        opt.setdefault("robot_bad", torch.zeros((B,), dtype=i32, device=dev))
+        gths = torch.zeros((cycles, G, 8), dtype=f32, device=dev)
+        glss = torch.zeros((cycles, G), dtype=f64, device=dev)
+        guss = torch.zeros((cycles, G), dtype=i32, device=dev)
     mask = column_mask(train)
     w, off, thr = float(loss_weight), float(loss_offset), float(fleet.collision_threshold)
     if peers:
@@ -406,7 +562,7 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
     collided = torch.zeros((B,), dtype=torch.bool, device=dev)
     arrive = torch.zeros((B,), dtype=torch.bool, device=dev)
     ended, stuck_count = torch.zeros((B,), dtype=i32, device=dev), torch.zeros((B,), dtype=i32, device=dev)
-    gacc = torch.zeros((B, 8), dtype=f32, device=dev)
+    gacc = torch.zeros((G or B, 8), dtype=f32, device=dev)
     last_xy = st[:, :2].clone()
     hist[0] = st
     scripted = None if actions is None else torch.as_tensor(actions).to(device=dev, dtype=f32)
@@ -455,10 +611,24 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
         loss = torch.where(book["active"] != 0, loss, zero)
         loss.sum().backward()
         losses[cyc], stucks[cyc], endeds[cyc] = loss.detach(), book["stuck"] != 0, ended != 0
-        opt["bad"] += fleet.pan.last_backward_bad
+        opt["robot_bad" if G else "bad"] += fleet.pan.last_backward_bad
         opt["t"] += 1
-        lon_adam(theta, leaf.grad.double().contiguous(), gacc, opt["m"], opt["v"], book["active"], opt["skipped"], opt["t"], mask,
-                 lr=lr, betas=betas, eps=eps, accumulate=accumulate, bounds=bounds)
+        if G:
+            # (the chain's own float64 rows: theta.grad is their float32 rounding, and the sum over a group is taken before it)
+            tot = torch.zeros((B, 8), dtype=f64, device=dev)
+            tot[:, :7] = fleet.pan.last_backward_rows
+            red = lon_reduce(tot, book["active"], group_first, group_members, mask, mean=group_mean, loss=book["loss"],
+                             dropped=opt["dropped"])
+            lon_adam(group_theta, red["gtot"], gacc, opt["m"], opt["v"], red["gactive"], opt["skipped"], opt["t"], mask,
+                     lr=lr, betas=betas, eps=eps, accumulate=accumulate, bounds=bounds)
+            lon_scatter(theta, group_theta, group_of)
+            gths[cyc], glss[cyc], guss[cyc] = group_theta, red["gloss"], red["n_used"]
+        else:
+            lon_adam(theta, leaf.grad.double().contiguous(), gacc, opt["m"], opt["v"], book["active"], opt["skipped"], opt["t"], mask,
+                     lr=lr, betas=betas, eps=eps, accumulate=accumulate, bounds=bounds)
         thetas[cyc] = theta
-    return dict(states=hist, actions=acts, arrive=arrive, stop=stops, collided=collided, clearance=clrs, controls=ctrl,
-                n_points=npt, loss=losses, stuck=stucks, ended=endeds, theta=thetas)
+    out = dict(states=hist, actions=acts, arrive=arrive, stop=stops, collided=collided, clearance=clrs, controls=ctrl,
+               n_points=npt, loss=losses, stuck=stucks, ended=endeds, theta=thetas)
+    if G:
+        out.update(group_theta=gths, group_loss=glss, group_used=guss)
+    return out

@@ -921,6 +921,7 @@ def _grad_backward_rows(ctx, gs, gu, gd):
         # has not run yet -- its loop ended before iteration k -- still holds the loss's own gradient in them)
         if not (bool((gs != 0).any()) or bool((gu != 0).any()) or (gd is not None and bool((gd != 0).any()))):
             break
+    pan.last_backward_rows = tot                   # (B, 7) float64: the rows themselves, before any rounding to float32
     return tot
 
 
