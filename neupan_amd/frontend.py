@@ -51,15 +51,10 @@ def _bcast(x, B, n=None):
     return np.broadcast_to(a, shape).copy()
 
 
-def _scan(mode, states, ranges, angle_min, angle_max, range_min, range_max, velocities, scan_offset, angle_range,
-          down_sample, n_beams, max_points, device):
-    lib = _lib.load()
-    dev = torch.device(device)
-    ranges = torch.as_tensor(np.asarray(ranges, dtype=np.float64) if not isinstance(ranges, torch.Tensor) else ranges)
-    ranges = ranges.to(device=dev, dtype=torch.float64).contiguous()
-    if ranges.dim() != 2:
-        raise ValueError("ranges must be [B, beams]")
-    B, R = ranges.shape
+def _scan_params(B, states, angle_min, angle_max, range_min, range_max, scan_offset=(0.0, 0.0, 0.0), angle_range=(-pi, pi),
+                 down_sample=1):
+    """the npa_scan_params records of B robots ([B] of _SCAN_DTYPE): every field a scalar (or one row) for all robots, or one
+    value (row) per robot -- the one place that fills the record"""
     par = np.zeros(B, dtype=_SCAN_DTYPE)
     par["angle_min"], par["angle_max"] = _bcast(angle_min, B), _bcast(angle_max, B)
     par["range_min"], par["range_max"] = _bcast(range_min, B), _bcast(range_max, B)
@@ -69,6 +64,19 @@ def _scan(mode, states, ranges, angle_min, angle_max, range_min, range_max, velo
     par["down_sample"] = np.broadcast_to(np.asarray(down_sample, dtype=np.int32), (B,))
     if (par["down_sample"] < 1).any():
         raise ValueError("down_sample must be >= 1")
+    return par
+
+
+def _scan(mode, states, ranges, angle_min, angle_max, range_min, range_max, velocities, scan_offset, angle_range,
+          down_sample, n_beams, max_points, device):
+    lib = _lib.load()
+    dev = torch.device(device)
+    ranges = torch.as_tensor(np.asarray(ranges, dtype=np.float64) if not isinstance(ranges, torch.Tensor) else ranges)
+    ranges = ranges.to(device=dev, dtype=torch.float64).contiguous()
+    if ranges.dim() != 2:
+        raise ValueError("ranges must be [B, beams]")
+    B, R = ranges.shape
+    par = _scan_params(B, states, angle_min, angle_max, range_min, range_max, scan_offset, angle_range, down_sample)
     par_d = torch.from_numpy(par.view(np.uint8).reshape(B, -1).copy()).to(dev)
     nb = None
     if n_beams is not None:

@@ -5,24 +5,29 @@ Per cycle the example plans, steps its simulator, computes a loss on info["dista
 min_distance is at or below the collision threshold, 50 + sum d when the robot is stuck, times 10), differentiates it through the
 QP and takes an Adam step; the episode ends on arrive, stop or stuck.  Here:
 
-* `LonLoop`            that cycle as a fixed launch sequence over buffers allocated once, with no host synchronisation:
+* `LonLoop`            that cycle as a fixed launch sequence over buffers allocated once, with no host synchronisation.  The
+  cycle itself is `ResidentLoop`'s (world.py: its front, tail and bookkeeping steps are defined there, once); this class replaces
+  the plan step and states what training adds -- marked + below:
 
-      npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states
-      -> npa_forward_begin, K x { copy cur_s, cur_u into snapshot k; npa_forward_iter(k); copy the mu / lam / pts / count rows
-         into snapshot k }, npa_forward_end
+      [+ the scripted row into the override buffer, ended robots' rows zeroed]
+      npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states                       (front)
+      + npa_forward_begin, K x { copy cur_s, cur_u into snapshot k; npa_forward_iter(k); copy the mu / lam / pts / count rows
+        into snapshot k }, npa_forward_end                                                                         (the plan step)
       -> npa_cycle_act (override_row = the loop's override buffer) [-> npa_world_behave, when the world has agents]
-      -> npa_world_step -> npa_cycle_commit
-      -> npa_lon_loss
-      -> for k = K-1 .. first: npa_nrmp_backward(snapshot k, gs, gu, gd) -> npa_lon_chain(k)
-      -> npa_lon_adam(t)
+      -> npa_world_step -> npa_cycle_commit                                                                        (tail)
+      + npa_lon_loss
+      + for k = K-1 .. first: npa_nrmp_backward(snapshot k, gs, gu, gd) -> npa_lon_chain(k)
+      + npa_lon_adam(t)
 
   With `groups` a parameter row is shared by a group of robots and trained from the rollouts of all of them -- the reference's
   one tuned set, at scale.  The tail of the cycle is then
 
       ... npa_lon_chain(first) -> npa_lon_reduce -> npa_lon_adam(t) on the G group rows -> npa_lon_scatter
 
-* `train_closed_loop`  the same cycle paced by the host: FleetPlanner.forward(adjust=theta) -> the loss as torch operations ->
-                       backward() into theta.grad -> the Adam step; it is to `LonLoop` what `run_closed_loop` is to `ResidentLoop`.
+* `train_closed_loop`  the same cycle paced by the host: world.py's host-paced cycle (the one `run_closed_loop` drives) with
+                       adjust=theta and the ended mask on the override, then what training adds: the loss as torch operations ->
+                       backward() into theta.grad -> [reduce ->] the Adam step [-> scatter]; it is to `LonLoop` what
+                       `run_closed_loop` is to `ResidentLoop`.
 * `lon_loss`, `lon_adam`, `lon_reduce`, `lon_scatter`  thin wrappers of the exports both loops share; `group_table` builds the
                        tables of the last two on the host.
 
@@ -32,15 +37,15 @@ same bits.  There is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-from math import inf, nan, pi, sqrt
+from math import inf, nan, sqrt
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import NeupanAmdError, check
-from .frontend import _ptr, scan_to_point_batch, scan_to_point_velocity_batch
-from .world import ResidentLoop, robot_radius, robot_vertices
+from .frontend import _ptr, _stream
+from .world import _LOG_ORDER, ResidentLoop, _HostCycle
 
 COLUMNS = ("q_s0", "q_s1", "q_s2", "p_u", "eta", "d_max", "d_min")      # the columns of a parameter row (the eighth is reserved)
 
@@ -93,10 +98,6 @@ def _adam_scalars(t, lr, betas, eps):
     """the scalars of step t as torch.optim.Adam computes them (Python floats, i.e. double)"""
     b1, b2 = float(betas[0]), float(betas[1])
     return (b1, 1.0 - b1, b2, 1.0 - b2, float(lr) / (1.0 - b1 ** t), sqrt(1.0 - b2 ** t), float(eps))
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _want(t, dtype, shape, what):
@@ -245,10 +246,24 @@ def lon_scatter(theta, group_theta, group_of):
     return theta
 
 
+def _lon_logs(cycles, B, device):
+    """the four logs training adds to a run's six (the shapes and dtypes `LonLoop.episode` documents), zeros"""
+    z = lambda dtype, *shape: torch.zeros((cycles, B) + shape, dtype=dtype, device=device)
+    return dict(loss=z(torch.float32), stuck=z(torch.bool), ended=z(torch.bool), theta=z(torch.float32, 8))
+
+
+def _group_logs(cycles, G, device):
+    """the three logs `groups` adds (after each cycle's step), zeros"""
+    z = lambda dtype, *shape: torch.zeros((cycles, G) + shape, dtype=dtype, device=device)
+    return dict(group_theta=z(torch.float32, 8), group_loss=z(torch.float64), group_used=z(torch.int32))
+
+
 class LonLoop(ResidentLoop):
     """`ResidentLoop` that trains: one parameter row per robot, one Adam step per robot and cycle, everything on the device (the
-    launch sequence: this module's header).  `fleet` as for ResidentLoop (fresh from `set_paths`); `theta0` (B, 7) or (B, 8): the
-    rows training starts from -- the loop owns a (B, 8) copy, installs it with `fleet.set_adjust` and the Adam kernel rewrites it
+    launch sequence: this module's header).  It overrides ResidentLoop's plan step (`_plan_step`: begin / iter / end with the
+    snapshots) and wraps its cycle (`_issue`: the override preparation in front; loss, backward chain and [reduce,] Adam [, scatter]
+    between the commit and the bookkeeping); front, tail, bookkeeping and the action-row conversion are inherited.
+    `fleet` as for ResidentLoop (fresh from `set_paths`); `theta0` (B, 7) or (B, 8): the rows training starts from -- the loop owns a (B, 8) copy, installs it with `fleet.set_adjust` and the Adam kernel rewrites it
     in place (`theta`).  train: the columns that are stepped; lr, betas, eps: torch.optim.Adam's; loss_weight, loss_offset,
     stuck_threshold, stuck_patience: the example's 10, 50, 0.01, 5; accumulate: gradients add up over an episode, as they do in
     the example, which clears them once per episode (False: every cycle steps on its own gradient); bounds: {name: (lo, hi)}
@@ -295,12 +310,13 @@ class LonLoop(ResidentLoop):
         K, M, E = pan.iter_num, max(pan.nrmp_max_num, 1), pan.E
         f32, f64, i32 = torch.float32, torch.float64, torch.int32
         zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
-        self.theta, self.t, self._first = theta, 0, True
+        self.theta, self.t = theta, 0
         self.m, self.v, self.gacc, self._tot = zeros((B, 8), f32), zeros((B, 8), f32), zeros((B, 8), f32), zeros((B, 8), f64)
         self.active, self.ended, self.stuck_count = zeros((B,), i32), zeros((B,), i32), zeros((B,), i32)
         self.skipped, self.bad, self.loss = zeros((B,), i32), zeros((B,), i32), zeros((B,), f32)
         self.last_xy = self.states[:, :2].clone()
         self.override = torch.full((B, 2), nan, dtype=f32, device=dev)
+        self._override_ptr = _ptr(self.override)
         self._ended_mask = torch.zeros((B, 1), dtype=torch.bool, device=dev)
         # ---- the backward pass: upstream gradients, one re-solve's outputs, the snapshots of the K iterations
         self._gs, self._gu, self._gd = zeros((B, 3, T + 1), f32), zeros((B, 2, T), f32), zeros((B, T), f32)
@@ -327,31 +343,14 @@ class LonLoop(ResidentLoop):
             ag, agi = world._upload_agents()[:2]
             self._saved_agents = (ag, agi, ag.clone(), agi.clone())
 
-    # ------------------------------------------------------------------ one cycle
-    def _issue(self, row, logs, i):
-        """one cycle; row: this cycle's scripted actions [B, 2] (contiguous f32 device tensor) or None; logs: the addresses of
-        the nine logs or None; i: the cycle's row in them"""
-        lib, pan, dev = self._lib, self.fleet.pan, self.device
-        ws, state = pan._ws, pan._state
-        if ws is None or state is None or (ws.data_ptr(), state.data_ptr()) != self._held_ptrs:
-            raise NeupanAmdError("LonLoop: the planner's workspace was re-made since the loop was prepared (another batch size "
-                                 "planned on the same PAN): make the loop again")
-        if pan.scene_adjust is None or pan.scene_adjust.data_ptr() != self.theta.data_ptr():
-            raise NeupanAmdError("LonLoop: another adjust block was installed on the fleet since the loop was prepared")
-        B, T, K = self.B, self.T, self.K
-        stream = _stream(dev)
-        if row is not None:                              # a scripted row does not move a robot whose episode has ended
-            self.override.copy_(row)
-            torch.ne(self.ended.view(B, 1), 0, out=self._ended_mask)
-            self.override.masked_fill_(self._ended_mask, 0.0)
-        for name, fn, args in self._front:
-            rc = fn(*args, stream)
-            if rc:
-                check(rc, name)
+    # ------------------------------------------------------------------ one cycle: ResidentLoop's steps and what training adds
+    def _plan_step(self, stream):
+        """the plan iteration by iteration (npa_forward_begin / _iter / _end: npa_forward_batch's bits), with the snapshots of
+        every iteration the backward pass re-solves"""
+        lib, snap, vw, h = self._lib, self._snap, self._views, self.fleet.pan._h
         check(lib.npa_forward_begin(*self._plan, stream, 0), "npa_forward_begin")
-        snap, vw, h = self._snap, self._views, pan._h
         try:
-            for k in range(K):
+            for k in range(self.K):
                 if k >= self._kfirst:
                     snap["cur_s"][k].copy_(vw["cur_s"]); snap["cur_u"][k].copy_(vw["cur_u"])
                 rc = lib.npa_forward_iter(h, k)
@@ -364,26 +363,30 @@ class LonLoop(ResidentLoop):
             lib.npa_forward_end(h)
             raise
         check(lib.npa_forward_end(h), "npa_forward_end")
-        la, ls, lc, ln, lh, lr, ll, lk, le = logs if logs is not None else (None,) * 9
-        rc = lib.npa_cycle_act(B, T, self._kin, 1 if self._first else 0, i, *self._act, _ptr(self.override), *self._act_out,
-                               la, ls, lc, ln, stream)
-        if rc:
-            check(rc, "npa_cycle_act")
-        if self._behave is not None:
-            self._issue_behave(self._first, stream)
-        rc = lib.npa_world_step(*self._step, stream)
-        if rc:
-            check(rc, "npa_world_step")
-        rc = lib.npa_cycle_commit(B, i, *self._commit, lh, lr, stream)
-        if rc:
-            check(rc, "npa_cycle_commit")
-        if row is not None:
+
+    def _issue(self, override, logs, row):
+        """ResidentLoop's cycle (override, logs, row as there; logs: nine addresses, the run's six, then loss, stuck, ended) with
+        the scripted row put into the override buffer in front of it and loss -> backward chain -> [reduce ->] Adam [-> scatter]
+        between its commit and its bookkeeping"""
+        lib, pan = self._lib, self.fleet.pan
+        if pan.scene_adjust is None or pan.scene_adjust.data_ptr() != self.theta.data_ptr():
+            raise NeupanAmdError("LonLoop: another adjust block was installed on the fleet since the loop was prepared")
+        B, T, K = self.B, self.T, self.K
+        if override is not None:                         # a scripted row does not move a robot whose episode has ended
+            self.override.copy_(override)
+            torch.ne(self.ended.view(B, 1), 0, out=self._ended_mask)
+            self.override.masked_fill_(self._ended_mask, 0.0)
+        stream = self._front_step()
+        self._plan_step(stream)
+        self._tail_step(self._override_ptr, None if logs is None else logs[:6], row, stream)
+        if override is not None:
             self.override.fill_(nan)
-        out = self.out
-        rc = lib.npa_lon_loss(B, T, i, _ptr(self.states), _ptr(self.last_xy), _ptr(out["opt_d"]), _ptr(out["min_distance"]),
+        ll, lk, le = logs[6:] if logs is not None else (None, None, None)
+        out, snap, h = self.out, self._snap, pan._h
+        rc = lib.npa_lon_loss(B, T, row, _ptr(self.states), _ptr(self.last_xy), _ptr(out["opt_d"]), _ptr(out["min_distance"]),
                               _ptr(self.stop), _ptr(self.arrived), _ptr(self.collided), *self._rule, _ptr(self.stuck_count),
                               _ptr(self.ended), _ptr(self.active), _ptr(self.loss), _ptr(self._gs), _ptr(self._gu), _ptr(self._gd),
-                              _ptr(self.override), ll, lk, le, stream)
+                              self._override_ptr, ll, lk, le, stream)
         if rc:
             check(rc, "npa_lon_loss")
         ref_s, ref_us = self.nominal[2], self.nominal[3]
@@ -422,23 +425,11 @@ class LonLoop(ResidentLoop):
                                   self._lo, self._hi, _ptr(self.skipped), stream)
             if rc:
                 check(rc, "npa_lon_adam")
-        pan._last, pan.last_out = self._pan_last, self.out
-        self._first = False
-        self.cycles_done += 1
-        if (self.cycles_done & 63) == 0:             # (a host read of one pinned word: no synchronisation)
-            pan.check_audit()
-
-    def _row(self, t):
-        if t is None:
-            return None
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.states.device
-                and tuple(t.shape) == (self.B, 2) and t.is_contiguous()):
-            t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32).reshape(self.B, 2).contiguous()
-        return t
+        self._finish_step()
 
     def cycle(self, actions_row=None):
         """One training cycle on the current stream; actions_row as for ResidentLoop.cycle (rows of robots whose episode has ended
-        count as zeros).  Returns `action`."""
+        count as zeros; the row is copied into the loop's override buffer, so it is not held).  Returns `action`."""
         self._on_device(self._row(actions_row), None, 0)
         return self.action
 
@@ -450,40 +441,18 @@ class LonLoop(ResidentLoop):
         plus loss [cycles, B] f32, stuck and ended [cycles, B] bool (after each cycle) and theta [cycles, B, 8] f32 (after each
         cycle's step) -- and, with groups, group_theta [cycles, G, 8] f32, group_loss [cycles, G] f64 and group_used [cycles, G]
         int32 (after each cycle's step).  The logs are allocated here, once; nothing is read back."""
-        B, T, dev = self.B, self.T, self.device
         cycles = int(cycles)
-        f32, f64 = torch.float32, torch.float64
-        hist = torch.empty((cycles + 1, B, 3), dtype=f64, device=dev)
-        acts = torch.zeros((cycles, B, 2), dtype=f32, device=dev)
-        stops = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-        clrs = torch.full((cycles, B), float("inf"), dtype=f64, device=dev)
-        ctrl = torch.zeros((cycles, B, 2, T), dtype=f32, device=dev)
-        npt = torch.zeros((cycles, B), dtype=torch.int32, device=dev)
-        loss = torch.zeros((cycles, B), dtype=f32, device=dev)
-        stuck = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-        ended = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-        thetas = torch.zeros((cycles, B, 8), dtype=f32, device=dev)
-        hist[0].copy_(self.states)
-        override = None
-        if actions is not None:
-            override = torch.as_tensor(actions).to(device=dev, dtype=f32).contiguous()
-            if tuple(override.shape) != (cycles, B, 2):
-                raise ValueError(f"actions must be [{cycles}, {B}, 2], not {list(override.shape)}")
-        logs = tuple(_ptr(t) for t in (acts, stops, ctrl, npt, hist, clrs, loss, stuck, ended)) if cycles > 0 else None
-        if self.G:
-            gth = torch.zeros((cycles, self.G, 8), dtype=f32, device=dev)
-            gls = torch.zeros((cycles, self.G), dtype=f64, device=dev)
-            gus = torch.zeros((cycles, self.G), dtype=torch.int32, device=dev)
+        lon = _lon_logs(cycles, self.B, self.device)
+        grp = _group_logs(cycles, self.G, self.device) if self.G else {}
+        logs, rows = self._open_run(cycles, actions)
+        ptrs = tuple(_ptr(t) for t in [logs[k] for k in _LOG_ORDER] + [lon[k] for k in ("loss", "stuck", "ended")]) if cycles > 0 else None
+        thetas, gth, gls, gus = lon["theta"], grp.get("group_theta"), grp.get("group_loss"), grp.get("group_used")
         for i in range(cycles):
-            self._on_device(override[i] if override is not None else None, logs, i)
+            self._on_device(rows[i], ptrs, i)
             thetas[i].copy_(self.theta)
             if self.G:
                 gth[i].copy_(self.group_theta); gls[i].copy_(self.group_loss); gus[i].copy_(self.group_used)
-        out = dict(states=hist, actions=acts, arrive=self.arrived != 0, stop=stops, collided=self.collided != 0, clearance=clrs,
-                   controls=ctrl, n_points=npt, loss=loss, stuck=stuck, ended=ended, theta=thetas)
-        if self.G:
-            out.update(group_theta=gth, group_loss=gls, group_used=gus)
-        return out
+        return dict(self._result(logs), **lon, **grp)
 
     def reset(self):
         """Start every robot over -- poses, path state, latches, warm start, stuck counters, the accumulated gradients, the
@@ -522,15 +491,11 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
     With `groups` (LonLoop's argument) the tail is lon_reduce -> lon_adam on the G group rows -> lon_scatter: `opt_state` comes
     from `adam_state(G, dev)` (the loop adds "dropped" [G] and "robot_bad" [B] to it; its "bad" is not used), every group
     takes the row of its lowest-numbered member of `theta` and the scatter runs once in front of the first cycle."""
-    sp = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0)
-    sp.update(scan or {})
     dev = world.device
     if fleet.pan.no_obs:
         raise NeupanAmdError("train_closed_loop: the planner has no obstacle stage: there is no opt_d, and opt_d is the loss's input")
-    V = robot_vertices(fleet.robot)
-    kin, L, dt = fleet.robot.kinematics, getattr(fleet.robot, "L", 0.0) or 0.0, fleet.dt
-    st = world._states(states).clone()
-    B, T = st.shape[0], fleet.T
+    host = _HostCycle(fleet, world, states, cycles, scan, point_velocities, peers, max_points)     # (the cycle up to the step: world.py)
+    B, T = host.B, fleet.T
     f32, f64, i32 = torch.float32, torch.float64, torch.int32
     _want(theta, f32, (B, 8), "theta")
     G = 0
@@ -542,67 +507,24 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
     if G:
         opt.setdefault("dropped", torch.zeros((G,), dtype=i32, device=dev))
         opt.setdefault("robot_bad", torch.zeros((B,), dtype=i32, device=dev))
-        gths = torch.zeros((cycles, G, 8), dtype=f32, device=dev)
-        glss = torch.zeros((cycles, G), dtype=f64, device=dev)
-        guss = torch.zeros((cycles, G), dtype=i32, device=dev)
     mask = column_mask(train)
     w, off, thr = float(loss_weight), float(loss_offset), float(fleet.collision_threshold)
-    if peers:
-        world.set_peers(st, V)
-    hist = torch.empty((cycles + 1, B, 3), dtype=f64, device=dev)
-    acts = torch.zeros((cycles, B, 2), dtype=f32, device=dev)
-    stops = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-    clrs = torch.full((cycles, B), float("inf"), dtype=f64, device=dev)
-    ctrl = torch.zeros((cycles, B, 2, T), dtype=f32, device=dev)
-    npt = torch.zeros((cycles, B), dtype=i32, device=dev)
-    losses = torch.zeros((cycles, B), dtype=f32, device=dev)
-    stucks = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-    endeds = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-    thetas = torch.zeros((cycles, B, 8), dtype=f32, device=dev)
-    collided = torch.zeros((B,), dtype=torch.bool, device=dev)
-    arrive = torch.zeros((B,), dtype=torch.bool, device=dev)
+    lon, grp = _lon_logs(cycles, B, dev), (_group_logs(cycles, G, dev) if G else {})
     ended, stuck_count = torch.zeros((B,), dtype=i32, device=dev), torch.zeros((B,), dtype=i32, device=dev)
     gacc = torch.zeros((G or B, 8), dtype=f32, device=dev)
-    last_xy = st[:, :2].clone()
-    hist[0] = st
+    last_xy = host.st[:, :2].clone()
     scripted = None if actions is None else torch.as_tensor(actions).to(device=dev, dtype=f32)
-    extra = {k: sp[k] for k in ("angle_range", "down_sample") if k in sp}
-    offset = sp.get("scan_offset", (0.0, 0.0, 0.0))
     zero = torch.zeros((B,), dtype=f32, device=dev)
-    agents = world.has_agents
-    prev, rad = (torch.empty_like(st), robot_radius(fleet.robot)) if agents else (None, 0.0)
     for cyc in range(cycles):
-        st_h = st.cpu().numpy()
-        ranges, bvel, _ = world.scan(st, sp["n_beams"], sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"], offset)
-        if point_velocities:
-            pts, pvel, npts = scan_to_point_velocity_batch(st_h, ranges, sp["angle_min"], sp["angle_max"], sp["range_min"],
-                                                           sp["range_max"], velocities=bvel, scan_offset=offset,
-                                                           max_points=max_points, device=dev, **extra)
-        else:
-            pts, npts = scan_to_point_batch(st_h, ranges, sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"],
-                                            scan_offset=offset, max_points=max_points, device=dev, **extra)
-            pvel = None
         leaf = theta.detach().clone().requires_grad_(True)
-        act, info = fleet.forward(st_h, pts, pvel, npts, adjust=leaf)
-        act = act.detach()
         # the override: the scripted row (NaN = the planner's action); a robot whose episode has ended stands still
         ov = torch.full((B, 2), nan, dtype=f32, device=dev) if scripted is None else scripted[cyc]
         ov = torch.where(ended[:, None] != 0, torch.zeros_like(ov), ov)
-        act = torch.where(torch.isnan(ov), act, ov)
-        arrive = info["arrive"]
-        frozen = (arrive | collided).to(i32)
-        act = torch.where(frozen[:, None] != 0, torch.zeros_like(act), act)
-        if agents:
-            world.behave(st, prev if cyc > 0 else None, dt, rad)
-            prev.copy_(st)
-        st, clr = world.step(st, act, dt, kin, L, frozen=frozen, robot_vertices=V, peers=peers)
-        collided = collided | (clr <= 0)
-        acts[cyc], stops[cyc], clrs[cyc], hist[cyc + 1] = act, info["stop"], clr, st
-        ctrl[cyc], npt[cyc] = info["opt_u"].detach(), npts
+        info, st, _ = host.cycle(cyc, ov, adjust=leaf)
         # the loss: the bookkeeping by the kernel both loops share, the differentiable part as torch operations
         md = info["min_distance"]
-        book = lon_loss(st, last_xy, info["opt_d"].detach().contiguous(), md, info["stop"].to(torch.uint8), arrive.to(i32),
-                        collided.to(i32), stuck_count, ended, thr, stuck_threshold, stuck_patience, w, off)
+        book = lon_loss(st, last_xy, info["opt_d"].detach().contiguous(), md, info["stop"].to(torch.uint8), host.arrive.to(i32),
+                        host.collided.to(i32), stuck_count, ended, thr, stuck_threshold, stuck_patience, w, off)
         d = info["opt_d"][:, 0, :]
         S = torch.zeros((B,), dtype=f32, device=dev)
         for t in range(T):
@@ -610,7 +532,7 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
         loss = torch.where(md <= thr, w * (off - S), torch.where(book["stuck"] != 0, w * (off + S), zero))
         loss = torch.where(book["active"] != 0, loss, zero)
         loss.sum().backward()
-        losses[cyc], stucks[cyc], endeds[cyc] = loss.detach(), book["stuck"] != 0, ended != 0
+        lon["loss"][cyc], lon["stuck"][cyc], lon["ended"][cyc] = loss.detach(), book["stuck"] != 0, ended != 0
         opt["robot_bad" if G else "bad"] += fleet.pan.last_backward_bad
         opt["t"] += 1
         if G:
@@ -622,13 +544,9 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
             lon_adam(group_theta, red["gtot"], gacc, opt["m"], opt["v"], red["gactive"], opt["skipped"], opt["t"], mask,
                      lr=lr, betas=betas, eps=eps, accumulate=accumulate, bounds=bounds)
             lon_scatter(theta, group_theta, group_of)
-            gths[cyc], glss[cyc], guss[cyc] = group_theta, red["gloss"], red["n_used"]
+            grp["group_theta"][cyc], grp["group_loss"][cyc], grp["group_used"][cyc] = group_theta, red["gloss"], red["n_used"]
         else:
             lon_adam(theta, leaf.grad.double().contiguous(), gacc, opt["m"], opt["v"], book["active"], opt["skipped"], opt["t"], mask,
                      lr=lr, betas=betas, eps=eps, accumulate=accumulate, bounds=bounds)
-        thetas[cyc] = theta
-    out = dict(states=hist, actions=acts, arrive=arrive, stop=stops, collided=collided, clearance=clrs, controls=ctrl,
-               n_points=npt, loss=losses, stuck=stucks, ended=endeds, theta=thetas)
-    if G:
-        out.update(group_theta=gths, group_loss=glss, group_used=guss)
-    return out
+        lon["theta"][cyc] = theta
+    return dict(host.result(), **lon, **grp)

@@ -7,7 +7,8 @@ simulator plays (example/run_exp.py: env.get_lidar_scan() -> scan_to_point -> ne
                       lidars (npa_world_scan), `step` advances robots and world and measures every robot's exact clearance to
                       the world (npa_world_step).  `from_yaml` reads the `obstacle:` list of an IR-SIM environment file; with
                       behaviours=True its `rvo` groups become agents.
-* `run_closed_loop`   scan -> scan_to_point[_velocity]_batch -> FleetPlanner.forward -> step, for B robots and a number of cycles.
+* `run_closed_loop`   scan -> scan_to_point[_velocity]_batch -> FleetPlanner.forward -> step, for B robots and a number of cycles
+                      (the cycle itself: `_HostCycle`, which lon.train_closed_loop drives too).
 * `ResidentLoop`      the same cycle as a fixed sequence of launches over buffers that never move: the path bookkeeping, the action
                       and the latches are kernels too (csrc/cycle.hip), so the host neither reads the device nor allocates.
 
@@ -29,7 +30,7 @@ import torch
 
 from . import _lib
 from ._lib import KIN, NeupanAmdError, NpaBehaveParams, check
-from .frontend import _SCAN_DTYPE, _bcast, _ptr, _stream, scan_to_point_batch, scan_to_point_velocity_batch
+from .frontend import _SCAN_DTYPE, _bcast, _ptr, _scan_params, _stream, scan_to_point_batch, scan_to_point_velocity_batch
 
 _PARAM_DOUBLES = _SCAN_DTYPE.itemsize // 8         # npa_scan_params as a row of float64 words (13; the last holds two int32)
 assert _SCAN_DTYPE.itemsize % 8 == 0
@@ -104,6 +105,21 @@ def _rows(a, width, what):
     out = np.zeros(a.shape[:2] + (6,))
     out[..., :a.shape[2]] = a
     return out
+
+
+def _scan_block(st, angle_min, angle_max, range_min, range_max, scan_offset, device):
+    """npa_world_scan's parameter block for the B robots at the poses st [B, 3] (a float64 tensor on `device`): [B, _PARAM_DOUBLES]
+    float64 rows angle_min, angle_max, range_min, range_max, the pose, the offset, zeros (scalars, or one value per robot) -- the
+    one place that fills it"""
+    B = st.shape[0]
+    par = torch.zeros((B, _PARAM_DOUBLES), dtype=torch.float64, device=device)
+    head = np.zeros((B, 4))
+    for k, x in enumerate((angle_min, angle_max, range_min, range_max)):
+        head[:, k] = np.broadcast_to(np.asarray(x, dtype=np.float64), (B,))
+    par[:, 0:4] = torch.from_numpy(head).to(device)
+    par[:, 4:7] = st
+    par[:, 7:10] = torch.from_numpy(np.broadcast_to(np.asarray(scan_offset, dtype=np.float64), (B, 3)).copy()).to(device)
+    return par
 
 
 class LidarWorld:
@@ -434,13 +450,7 @@ class LidarWorld:
         if out is not None:                    # the rows are as far apart as `out` is wide; the counts go in n_beams
             R = self._check_out(out, B, R)
         nb = None if nb_h is None else torch.from_numpy(nb_h).to(dev)
-        par = torch.zeros((B, _PARAM_DOUBLES), dtype=torch.float64, device=dev)
-        head = np.zeros((B, 4))
-        for k, x in enumerate((angle_min, angle_max, range_min, range_max)):
-            head[:, k] = np.broadcast_to(np.asarray(x, dtype=np.float64), (B,))
-        par[:, 0:4] = torch.from_numpy(head).to(dev)
-        par[:, 4:7] = st
-        par[:, 7:10] = torch.from_numpy(np.broadcast_to(np.asarray(scan_offset, dtype=np.float64), (B, 3)).copy()).to(dev)
+        par = _scan_block(st, angle_min, angle_max, range_min, range_max, scan_offset, dev)
         if out is None:
             ranges = torch.zeros((B, R), dtype=torch.float64, device=dev)
             vel = torch.zeros((B, 2, R), dtype=torch.float64, device=dev)
@@ -532,6 +542,88 @@ def robot_radius(robot):
     return float(np.sqrt((V * V).sum(axis=1)).max())
 
 
+_SCAN_DEFAULTS = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0, scan_offset=(0.0, 0.0, 0.0),
+                      angle_range=(-pi, pi), down_sample=1)
+_LIMITS = ("angle_min", "angle_max", "range_min", "range_max")
+_LOG_ORDER = ("actions", "stop", "controls", "n_points", "states", "clearance")      # as npa_cycle_act, then npa_cycle_commit take them
+
+
+def _scan_fields(scan):
+    """the loops' `scan` argument over the defaults: 100 beams over (-pi, pi), 0 .. 10 m (the example environments' sensor), no
+    offset, every beam kept"""
+    return dict(_SCAN_DEFAULTS, **(scan or {}))
+
+
+def _run_logs(cycles, B, T, device):
+    """the six logs of a run (the shapes and dtypes `run_closed_loop` documents): zeros, clearance inf, states uninitialised --
+    row 0, the poses at the start, is the caller's to fill"""
+    z = lambda dtype, *shape: torch.zeros((cycles, B) + shape, dtype=dtype, device=device)
+    return dict(states=torch.empty((cycles + 1, B, 3), dtype=torch.float64, device=device), actions=z(torch.float32, 2),
+                stop=z(torch.bool), clearance=torch.full((cycles, B), float("inf"), dtype=torch.float64, device=device),
+                controls=z(torch.float32, 2, T), n_points=z(torch.int32))
+
+
+class _HostCycle:
+    """The host-paced cycle, defined once: `run_closed_loop` and `lon.train_closed_loop` both drive this.
+
+        scan -> scan_to_point[_velocity]_batch -> fleet.forward -> override, freeze [-> behave] -> step -> collision latch, log rows
+
+    It owns the poses (`st`), the latches (`collided`, `arrive`), the agents' earlier poses and the robots' radius for them, the
+    robot's vertices and the six logs.  The arguments are `run_closed_loop`'s."""
+
+    def __init__(self, fleet, world, states, cycles, scan, point_velocities, peers, max_points):
+        sp = _scan_fields(scan)
+        dev = world.device
+        self.fleet, self.world, self.point_velocities, self.peers = fleet, world, point_velocities, peers
+        self.V = robot_vertices(fleet.robot)
+        self.st = world._states(states).clone()
+        self.B = B = self.st.shape[0]
+        if peers:
+            world.set_peers(self.st, self.V)
+        self.logs = _run_logs(cycles, B, fleet.T, dev)
+        self.logs["states"][0] = self.st
+        self.collided = torch.zeros((B,), dtype=torch.bool, device=dev)
+        self.arrive = torch.zeros((B,), dtype=torch.bool, device=dev)
+        self._beams, self._limits, self._offset = sp["n_beams"], tuple(sp[k] for k in _LIMITS), sp["scan_offset"]
+        self._to_points = dict(scan_offset=sp["scan_offset"], angle_range=sp["angle_range"], down_sample=sp["down_sample"],
+                               max_points=max_points, device=dev)
+        self.prev, self.radius = (torch.empty_like(self.st), robot_radius(fleet.robot)) if world.has_agents else (None, 0.0)
+
+    def cycle(self, cyc, override=None, certify=False, adjust=None):
+        """Cycle number `cyc`.  override [B, 2] float32 (entries that are not NaN replace the planner's action) or None; certify,
+        adjust: `FleetPlanner.forward`'s.  Returns (info, the poses after the step, the world clearance after it).
+        `fleet.forward` synchronises once for its path bookkeeping; nothing here adds to that: the poses it needs are read once
+        at the top and handed to it as a host array."""
+        fleet, world, st, logs = self.fleet, self.world, self.st, self.logs
+        st_h = st.cpu().numpy()                                 # (the cycle's one read of the poses: forward needs them on the host)
+        ranges, bvel, _ = world.scan(st, self._beams, *self._limits, self._offset)
+        if self.point_velocities:
+            pts, pvel, npts = scan_to_point_velocity_batch(st_h, ranges, *self._limits, velocities=bvel, **self._to_points)
+        else:
+            (pts, npts), pvel = scan_to_point_batch(st_h, ranges, *self._limits, **self._to_points), None
+        act, info = fleet.forward(st_h, pts, pvel, npts, certify=certify, adjust=adjust)
+        act = act.detach()
+        if override is not None:
+            act = torch.where(torch.isnan(override), act, override)
+        self.arrive = info["arrive"]
+        frozen = (self.arrive | self.collided).to(torch.int32)
+        act = torch.where(frozen[:, None] != 0, torch.zeros_like(act), act)
+        if self.prev is not None:                               # the agents choose: the robots count as standing in the first cycle
+            world.behave(st, self.prev if cyc > 0 else None, fleet.dt, self.radius)
+            self.prev.copy_(st)
+        robot = fleet.robot
+        self.st, clr = world.step(st, act, fleet.dt, robot.kinematics, getattr(robot, "L", 0.0) or 0.0, frozen=frozen,
+                                  robot_vertices=self.V, peers=self.peers)
+        self.collided = self.collided | (clr <= 0)
+        logs["actions"][cyc], logs["stop"][cyc], logs["clearance"][cyc], logs["states"][cyc + 1] = act, info["stop"], clr, self.st
+        logs["controls"][cyc], logs["n_points"][cyc] = info["opt_u"].detach(), npts
+        return info, self.st, clr
+
+    def result(self):
+        """the dict `run_closed_loop` returns, without plan_clearance"""
+        return dict(self.logs, arrive=self.arrive, collided=self.collided)
+
+
 def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=False, certify=False, peers=False,
                     max_points=None, actions=None):
     """example/run_exp.py's loop for the B robots of `fleet` (a FleetPlanner whose paths are set) in `world`:
@@ -550,60 +642,13 @@ def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=Fa
     collided [B] bool, clearance [cycles, B] f64 (the world clearance after each step), controls [cycles, B, 2, T] f32 (the
     plans' opt_u), n_points [cycles, B] int32 (the clouds' sizes); with certify, plan_clearance [B, T+1] of the last cycle),
     device tensors."""
-    sp = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0)
-    sp.update(scan or {})
-    dev = world.device
-    V = robot_vertices(fleet.robot)
-    kin, L, dt = fleet.robot.kinematics, getattr(fleet.robot, "L", 0.0) or 0.0, fleet.dt
-    st = world._states(states).clone()
-    B = st.shape[0]
-    if peers:
-        world.set_peers(st, V)
-    hist = torch.empty((cycles + 1, B, 3), dtype=torch.float64, device=dev)
-    acts = torch.zeros((cycles, B, 2), dtype=torch.float32, device=dev)
-    stops = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-    clrs = torch.full((cycles, B), float("inf"), dtype=torch.float64, device=dev)
-    ctrl = torch.zeros((cycles, B, 2, fleet.T), dtype=torch.float32, device=dev)
-    npt = torch.zeros((cycles, B), dtype=torch.int32, device=dev)
-    collided = torch.zeros((B,), dtype=torch.bool, device=dev)
-    arrive = torch.zeros((B,), dtype=torch.bool, device=dev)
-    hist[0] = st
-    override = None if actions is None else torch.as_tensor(actions).to(device=dev, dtype=torch.float32)
-    extra = {k: sp[k] for k in ("angle_range", "down_sample") if k in sp}
-    offset = sp.get("scan_offset", (0.0, 0.0, 0.0))
-    agents = world.has_agents
-    prev, rad = (torch.empty_like(st), robot_radius(fleet.robot)) if agents else (None, 0.0)
+    loop = _HostCycle(fleet, world, states, cycles, scan, point_velocities, peers, max_points)
+    override = None if actions is None else torch.as_tensor(actions).to(device=world.device, dtype=torch.float32)
     for cyc in range(cycles):
-        st_h = st.cpu().numpy()                                 # (the cycle's one read of the poses: forward needs them on the host)
-        ranges, bvel, _ = world.scan(st, sp["n_beams"], sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"], offset)
-        if point_velocities:
-            pts, pvel, npts = scan_to_point_velocity_batch(st_h, ranges, sp["angle_min"], sp["angle_max"], sp["range_min"],
-                                                           sp["range_max"], velocities=bvel, scan_offset=offset,
-                                                           max_points=max_points, device=dev, **extra)
-        else:
-            pts, npts = scan_to_point_batch(st_h, ranges, sp["angle_min"], sp["angle_max"], sp["range_min"], sp["range_max"],
-                                            scan_offset=offset, max_points=max_points, device=dev, **extra)
-            pvel = None
-        act, info = fleet.forward(st_h, pts, pvel, npts, certify=certify)
-        act = act.detach()
-        if override is not None:
-            act = torch.where(torch.isnan(override[cyc]), act, override[cyc])
-        arrive = info["arrive"]
-        frozen = (arrive | collided).to(torch.int32)
-        act = torch.where(frozen[:, None] != 0, torch.zeros_like(act), act)
-        if agents:                                              # the agents choose: the robots count as standing in the first cycle
-            world.behave(st, prev if cyc > 0 else None, dt, rad)
-            prev.copy_(st)
-        st, clr = world.step(st, act, dt, kin, L, frozen=frozen, robot_vertices=V, peers=peers)
-        collided = collided | (clr <= 0)
-        acts[cyc], stops[cyc], clrs[cyc], hist[cyc + 1] = act, info["stop"], clr, st
-        ctrl[cyc], npt[cyc] = info["opt_u"].detach(), npts
-        if certify:
-            last_info = info
-    out = dict(states=hist, actions=acts, arrive=arrive, stop=stops, collided=collided, clearance=clrs, controls=ctrl,
-               n_points=npt)
+        info, _, _ = loop.cycle(cyc, None if override is None else override[cyc], certify)
+    out = loop.result()
     if certify and cycles > 0:
-        out["plan_clearance"] = last_info["clearance"]
+        out["plan_clearance"] = info["clearance"]
     return out
 
 
@@ -635,9 +680,13 @@ class ResidentLoop:
     sequence on the current stream, with no host synchronisation and no allocation:
 
         npa_cycle_progress (path progress, curve switch, arrival latch, poses -> both scan parameter blocks)
-        -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states -> npa_forward_batch_flags
-        [-> npa_plan_clearance] -> npa_cycle_act (warm start, stop, action, override, freeze)
+        -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states                                    (_front_step)
+        -> npa_forward_batch_flags [-> npa_plan_clearance]                                                    (_plan_step)
+        -> npa_cycle_act (warm start, stop, action, override, freeze)
         [-> npa_world_behave, when the world has agents] -> npa_world_step -> npa_cycle_commit (collision latch, log rows)
+                                                                                                              (_tail_step)
+    followed by the host's bookkeeping (_finish_step: the planner's last call, `cycles_done`, the audit every 64 cycles).  This is
+    the one definition of the resident cycle: `lon.LonLoop` replaces the plan step and adds its own steps around these.
 
     The arguments are `run_closed_loop`'s.  `fleet` must be fresh from `set_paths` (its host bookkeeping -- curve_index, arrived,
     cur_vel -- is not used again: this object owns the device copy, and `fleet.forward` must not be mixed in until the next
@@ -671,8 +720,7 @@ class ResidentLoop:
                              f"{pan._cfg.iter_num}; the prepared plan call runs the handle's count")
         if certify and pan.no_obs:
             raise NeupanAmdError("ResidentLoop: certify needs the planner's obstacle stage (PAN.plan_clearance)")
-        sp = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0)
-        sp.update(scan or {})
+        sp = _scan_fields(scan)
         lib, dev = _lib.load(), world.device
         if torch.device(fleet.device).type != dev.type:
             raise ValueError(f"ResidentLoop: the fleet is on {fleet.device}, the world on {dev}")
@@ -688,7 +736,7 @@ class ResidentLoop:
         kin, L = fleet.robot.kinematics, getattr(fleet.robot, "L", 0.0) or 0.0
         if peers:
             world.set_peers(st, V)
-        self.B, self.T, self.certify, self.cycles_done = B, T, bool(certify), 0
+        self.B, self.T, self.certify, self.cycles_done, self._first = B, T, bool(certify), 0, True
         self.states = st
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
@@ -700,8 +748,7 @@ class ResidentLoop:
         self.cur_off, self.cur_len = i32(off[first[:-1]]), i32(ln[first[:-1]])
         self.point_index, self.arrived, self.collided = zeros((B,), torch.int32), zeros((B,), torch.int32), zeros((B,), torch.int32)
         self._curve_arrived = zeros((B,), torch.int32)
-        # ---- the two parameter blocks: the world scan's (as LidarWorld.scan fills it) and npa_scan_to_points' (as _scan does)
-        offset = sp.get("scan_offset", (0.0, 0.0, 0.0))
+        # ---- the two parameter blocks: the world scan's and npa_scan_to_points' (npa_cycle_progress rewrites their poses)
         if isinstance(sp["n_beams"], (int, np.integer)):
             R, nb = int(sp["n_beams"]), None
         else:
@@ -709,22 +756,9 @@ class ResidentLoop:
             R, nb = int(nb_h.max()), i32(nb_h)
         if R < 1:
             raise ValueError("ResidentLoop: a scan needs at least one beam")
-        par_w = zeros((B, _PARAM_DOUBLES), torch.float64)
-        head = np.zeros((B, 4))
-        for k, key in enumerate(("angle_min", "angle_max", "range_min", "range_max")):
-            head[:, k] = np.broadcast_to(np.asarray(sp[key], dtype=np.float64), (B,))
-        par_w[:, 0:4] = torch.from_numpy(head).to(dev)
-        par_w[:, 4:7] = st
-        par_w[:, 7:10] = torch.from_numpy(np.broadcast_to(np.asarray(offset, dtype=np.float64), (B, 3)).copy()).to(dev)
-        par = np.zeros(B, dtype=_SCAN_DTYPE)
-        par["angle_min"], par["angle_max"] = head[:, 0], head[:, 1]
-        par["range_min"], par["range_max"] = head[:, 2], head[:, 3]
-        par["state"] = st.cpu().numpy()
-        par["offset"] = _bcast(offset, B, 3)
-        par["angle_range"] = _bcast(sp.get("angle_range", (-pi, pi)), B, 2)
-        par["down_sample"] = np.broadcast_to(np.asarray(sp.get("down_sample", 1), dtype=np.int32), (B,))
-        if (par["down_sample"] < 1).any():
-            raise ValueError("down_sample must be >= 1")
+        limits = tuple(sp[k] for k in _LIMITS)
+        par_w = _scan_block(st, *limits, sp["scan_offset"], dev)
+        par = _scan_params(B, st.cpu().numpy(), *limits, sp["scan_offset"], sp["angle_range"], sp["down_sample"])
         par_s = torch.from_numpy(par.view(np.uint8).reshape(B, -1).copy()).to(dev)
         self._params = (par_w, par_s)
         # ---- scan outputs and the cloud
@@ -804,20 +838,24 @@ class ResidentLoop:
             world._held_by_loop = True
         fleet.cur_vel = self.cur_vel                 # (the fleet has planned from here on: a second loop needs set_paths)
 
-    # ------------------------------------------------------------------ one cycle
-    def _issue(self, override, logs, row):
-        """the nine calls of one cycle; override: a device address or None; logs: six device addresses (actions, stop, controls,
-        n_points, states, clearance) or None; row: the cycle's row in them"""
-        lib, pan = self._lib, self.fleet.pan
+    # ------------------------------------------------------------------ one cycle, in four steps
+    def _front_step(self):
+        """the workspace check, then the launches in front of the plan; returns the cycle's stream"""
+        pan = self.fleet.pan
         ws, state = pan._ws, pan._state
         if ws is None or state is None or (ws.data_ptr(), state.data_ptr()) != self._held_ptrs:
-            raise NeupanAmdError("ResidentLoop: the planner's workspace was re-made since the loop was prepared (another batch "
-                                 "size planned on the same PAN): make the loop again")
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            raise NeupanAmdError(f"{type(self).__name__}: the planner's workspace was re-made since the loop was prepared (another "
+                                 "batch size planned on the same PAN): make the loop again")
+        stream = C.c_void_p(torch.cuda.current_stream(self._idx).cuda_stream)     # (_on_device made _idx the current device)
         for name, fn, args in self._front:
             rc = fn(*args, stream)
             if rc:
                 check(rc, name)
+        return stream
+
+    def _plan_step(self, stream):
+        """the plan over the loop's tensors and, with certify, its exact clearance (LonLoop plans iteration by iteration instead)"""
+        lib = self._lib
         rc = lib.npa_forward_batch_flags(*self._plan, stream, 0)
         if rc:
             check(rc, "npa_forward_batch_flags")
@@ -825,31 +863,45 @@ class ResidentLoop:
             rc = lib.npa_plan_clearance(*self._certify, stream)
             if rc:
                 check(rc, "npa_plan_clearance")
+
+    def _tail_step(self, override, logs, row, stream):
+        """act [-> behave] -> step -> commit; override: the device address of the row npa_cycle_act applies, or None; logs: the
+        addresses of the six run logs (_LOG_ORDER) or None; row: the cycle's row in them"""
+        lib, first = self._lib, self._first
         la, ls, lc, ln, lh, lr = logs if logs is not None else (None,) * 6
-        rc = lib.npa_cycle_act(self.B, self.T, self._kin, 1 if self.cycles_done == 0 else 0, row, *self._act, override,
-                               *self._act_out, la, ls, lc, ln, stream)
+        rc = lib.npa_cycle_act(self.B, self.T, self._kin, 1 if first else 0, row, *self._act, override, *self._act_out,
+                               la, ls, lc, ln, stream)
         if rc:
             check(rc, "npa_cycle_act")
-        if self._behave is not None:
-            self._issue_behave(self.cycles_done == 0, stream)
+        if self._behave is not None:                     # the agents choose (first cycle: the robots count as standing), then the
+            head, tail = self._behave                    # poses are kept for the next cycle's call
+            rc = lib.npa_world_behave(*head, None if first else self._prev_ptr, *tail, stream)
+            if rc:
+                check(rc, "npa_world_behave")
+            self.prev_states.copy_(self.states)
         rc = lib.npa_world_step(*self._step, stream)
         if rc:
             check(rc, "npa_world_step")
         rc = lib.npa_cycle_commit(self.B, row, *self._commit, lh, lr, stream)
         if rc:
             check(rc, "npa_cycle_commit")
+
+    def _finish_step(self):
+        """the host's bookkeeping behind a cycle: what the planner reports as its last call, the counters, the audit"""
+        pan = self.fleet.pan
         pan._last, pan.last_out = self._pan_last, self.out
+        self._first = False
         self.cycles_done += 1
         if (self.cycles_done & 63) == 0:             # (a host read of one pinned word: no synchronisation)
             pan.check_audit()
 
-    def _issue_behave(self, first, stream):
-        """npa_world_behave (first: the robots count as standing), then the poses kept for the next cycle's call"""
-        head, tail = self._behave
-        rc = self._lib.npa_world_behave(*head, None if first else self._prev_ptr, *tail, stream)
-        if rc:
-            check(rc, "npa_world_behave")
-        self.prev_states.copy_(self.states)
+    def _issue(self, override, logs, row):
+        """one cycle; override: the cycle's scripted actions, a contiguous float32 device tensor [B, 2], or None; logs: the device
+        addresses of the run's logs (the six of _LOG_ORDER; LonLoop: its three behind them) or None; row: the cycle's row in them"""
+        stream = self._front_step()
+        self._plan_step(stream)
+        self._tail_step(None if override is None else C.c_void_p(override.data_ptr()), logs, row, stream)
+        self._finish_step()
 
     def _on_device(self, override, logs, row):
         if torch.cuda.current_device() != self._idx:   # the launches must see the device of the handle
@@ -858,45 +910,49 @@ class ResidentLoop:
         else:
             self._issue(override, logs, row)
 
+    def _row(self, t):
+        """a scripted action row as the cycle takes it: a contiguous float32 device tensor [B, 2] (anything else is converted,
+        which allocates); None stays None"""
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.states.device
+                                  and tuple(t.shape) == (self.B, 2) and t.is_contiguous()):
+            t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32).reshape(self.B, 2).contiguous()
+        return t
+
     def cycle(self, actions_row=None):
         """One control cycle on the current stream.  actions_row: a contiguous float32 DEVICE tensor [B, 2] whose entries that
         are not NaN replace the planner's action (anything else is converted first, which allocates).  Returns `action`, the
         loop's own [B, 2] tensor: valid in stream order, overwritten by the next cycle."""
-        ov = None
-        if actions_row is not None:
-            t = actions_row
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.states.device
-                    and tuple(t.shape) == (self.B, 2) and t.is_contiguous()):
-                t = torch.as_tensor(t).to(device=self.device, dtype=torch.float32).reshape(self.B, 2).contiguous()
+        t = self._row(actions_row)
+        if t is not None:
             self._override = t                       # (held until the next cycle)
-            ov = _ptr(t)
-        self._on_device(ov, None, 0)
+        self._on_device(t, None, 0)
         return self.action
+
+    def _open_run(self, cycles, actions):
+        """what a run of `cycles` cycles starts from: the six logs with states[0] = the poses at the call, and the rows of
+        `actions` [cycles, B, 2] as a tuple of `cycles` device tensors (without actions: of Nones)"""
+        logs = _run_logs(cycles, self.B, self.T, self.device)
+        logs["states"][0].copy_(self.states)
+        if actions is None:
+            return logs, (None,) * cycles
+        override = torch.as_tensor(actions).to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(override.shape) != (cycles, self.B, 2):
+            raise ValueError(f"actions must be [{cycles}, {self.B}, 2], not {list(override.shape)}")
+        return logs, override.unbind(0)
+
+    def _result(self, logs):
+        return dict(logs, arrive=self.arrived != 0, collided=self.collided != 0)
 
     def run(self, cycles, actions=None):
         """`cycles` cycles; returns the dict run_closed_loop returns (same keys, shapes and dtypes; states[0] = the poses at the
         call).  `actions` [cycles, B, 2] as there.  The logs are allocated here, once; nothing is read back."""
-        B, T, dev = self.B, self.T, self.device
         cycles = int(cycles)
-        hist = torch.empty((cycles + 1, B, 3), dtype=torch.float64, device=dev)
-        acts = torch.zeros((cycles, B, 2), dtype=torch.float32, device=dev)
-        stops = torch.zeros((cycles, B), dtype=torch.bool, device=dev)
-        clrs = torch.full((cycles, B), float("inf"), dtype=torch.float64, device=dev)
-        ctrl = torch.zeros((cycles, B, 2, T), dtype=torch.float32, device=dev)
-        npt = torch.zeros((cycles, B), dtype=torch.int32, device=dev)
-        hist[0].copy_(self.states)
-        override, base = None, 0
-        if actions is not None:
-            override = torch.as_tensor(actions).to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(override.shape) != (cycles, B, 2):
-                raise ValueError(f"actions must be [{cycles}, {B}, 2], not {list(override.shape)}")
-            base = override.data_ptr()
-        logs = (_ptr(acts), _ptr(stops), _ptr(ctrl), _ptr(npt), _ptr(hist), _ptr(clrs)) if cycles > 0 else None
+        logs, rows = self._open_run(cycles, actions)
+        ptrs = tuple(_ptr(logs[k]) for k in _LOG_ORDER) if cycles > 0 else None
         for i in range(cycles):
-            self._on_device(C.c_void_p(base + i * B * 2 * 4) if override is not None else None, logs, i)
-        self._override = override                    # (held: the last launches may still read it)
-        out = dict(states=hist, actions=acts, arrive=self.arrived != 0, stop=stops, collided=self.collided != 0, clearance=clrs,
-                   controls=ctrl, n_points=npt)
+            self._on_device(rows[i], ptrs, i)
+        self._override = rows                        # (held: the last launches may still read them)
+        out = self._result(logs)
         if self.certify and cycles > 0:
             out["plan_clearance"] = self.plan_clearance["clearance"].clone()
         return out

@@ -7,7 +7,7 @@
   error is about 1e-6 of lr, far below half an ulp of theta = 1 .. 10: only the rounding position of each subtraction can differ; measured on the MI355X: 0 ulp at every one of the eight steps);
 * LonLoop.episode against train_closed_loop, the same cycle paced by the host, with torch.equal on every key from cycle 0: both
   sides run the same kernels on the same bits.  Omni is in under the rule tests/test_resident_loop_gpu.py states for it;
-* lr = 0 against ResidentLoop.run; no synchronisation, no allocation; cycles by hand; a population of 70 against 70 single runs."""
+* lr = 0 against ResidentLoop.run, and host-paced against run_closed_loop; no synchronisation, no allocation; cycles by hand; a population of 70 against 70 single runs."""
 import ctypes as C
 from math import pi
 
@@ -378,6 +378,27 @@ def test_training_off_is_the_plain_loop():
     common = {k: got[k] for k in ref}
     assert_same(common, ref, RUN_KEYS)
     assert torch.equal(got["theta"], block[None].expand(16, 6, 8)) and torch.equal(loop.theta, block)
+    for f in (fa, fb):
+        f.set_adjust(None)
+
+
+def test_training_off_is_the_plain_host_paced_loop():
+    """the host-paced counterpart of the test above: train_closed_loop and run_closed_loop drive the one host cycle the same way"""
+    import torch
+    from neupan_amd.lon import adjust_block, train_closed_loop
+    from neupan_amd.world import LidarWorld, run_closed_loop
+    fa, fb = pair("diff", 3, 64)
+    paths, poses, circles = lr.straight_cases()
+    start((fa, fb), paths)
+    block = adjust_block(lr.THETA0, 6, "cuda")
+    fa.set_adjust(block)
+    ref = run_closed_loop(fa, LidarWorld(circles), poses, 16, scan=scan_of(64))
+    theta = adjust_block(lr.THETA0, 6, "cuda")
+    got = train_closed_loop(fb, LidarWorld(circles), poses, 16, theta, lr=0.0, scan=scan_of(64))
+    assert not bool(got["stop"].any()) and not bool(got["stuck"].any()) and not bool(got["ended"].any())
+    common = {k: got[k] for k in ref}
+    assert_same(common, ref, RUN_KEYS)
+    assert torch.equal(got["theta"], block[None].expand(16, 6, 8)) and torch.equal(theta, block)
     for f in (fa, fb):
         f.set_adjust(None)
 

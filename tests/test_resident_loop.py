@@ -1,7 +1,8 @@
 """CPU tests of the device-resident closed loop (neupan_amd.world.ResidentLoop, csrc/cycle.hip): the curve table, the argument
 checks of the three exports, the ABI's agreement on them, the numpy restatement of the bookkeeping rules (tests/resident_ref.py)
-on hand-made tables, and the decided cases the GPU tests run -- that their paths really produce the switches, the cycle-0
-arrival and the collision within the run, by the path restatement of oracle/frontend_oracle.py."""
+on hand-made tables, the decided cases the GPU tests run -- that their paths really produce the switches, the cycle-0
+arrival and the collision within the run, by the path restatement of oracle/frontend_oracle.py -- and the builders all four
+closed loops share: the two scan parameter blocks and the log allocators, on the CPU."""
 import ctypes as C
 import os
 import re
@@ -226,3 +227,73 @@ def test_decided_cases_happen_within_the_run(kin, kw):
     assert ev["switch"][1] == [6, 12] and ev["switch"][2] == [4, 8, 12] and ev["switch"][3][:2] == [4, 5]
     assert ev["switch"][4] == [] or ev["switch"][4][0] == 0      # a one-curve path starts over in place (curve 0 -> curve 0)
     assert set(ev["collide"]) == {5}
+
+
+# ---------------------------------------------------------------------------------------------------- the shared builders
+def test_scan_params_builder_fills_the_record_field_by_field():
+    """the one builder of the npa_scan_params records (frontend._scan and ResidentLoop both use it): its bytes are those of two
+    NpaScanParams structures filled by hand"""
+    from neupan_amd.frontend import NpaScanParams, _SCAN_DTYPE, _scan_params
+    states = [[1.0, 2.0, 0.5], [3.0, 4.0, -0.25]]
+    par = _scan_params(2, states, -3.0, (3.0, 2.5), 0.1, (10.0, 8.0), scan_offset=(0.1, 0.0, 0.05), angle_range=(-1.5, 2.0),
+                       down_sample=(1, 3))
+    assert par.dtype == _SCAN_DTYPE and par.shape == (2,)
+    want = b""
+    for b in range(2):
+        p = NpaScanParams()
+        p.angle_min, p.angle_max, p.range_min, p.range_max = -3.0, (3.0, 2.5)[b], 0.1, (10.0, 8.0)[b]
+        p.state[:] = states[b]
+        p.offset[:] = (0.1, 0.0, 0.05)
+        p.angle_range[:] = (-1.5, 2.0)
+        p.down_sample, p.reserved = (1, 3)[b], 0
+        want += bytes(p)
+    assert par.tobytes() == want
+    # the defaults: no offset, every angle, every beam
+    d = _scan_params(1, [states[0]], -3.0, 3.0, 0.1, 10.0)
+    assert d["offset"].tolist() == [[0.0, 0.0, 0.0]] and d["angle_range"].tolist() == [[-np.pi, np.pi]] and d["down_sample"].tolist() == [1]
+
+
+def test_scan_params_builder_refuses_down_sample_zero():
+    from neupan_amd.frontend import _scan_params
+    with pytest.raises(ValueError, match="down_sample must be >= 1"):
+        _scan_params(2, np.zeros((2, 3)), -3.0, 3.0, 0.1, 10.0, down_sample=(1, 0))
+    with pytest.raises(ValueError, match="down_sample must be >= 1"):
+        _scan_params(2, np.zeros((2, 3)), -3.0, 3.0, 0.1, 10.0, down_sample=0)
+
+
+def test_world_scan_block_builder():
+    """the one builder of npa_world_scan's parameter block (LidarWorld.scan and ResidentLoop both use it)"""
+    import torch
+    from neupan_amd.world import _PARAM_DOUBLES, _scan_block
+    st = torch.tensor([[1.0, 2.0, 0.5], [3.0, 4.0, -0.25]], dtype=torch.float64)
+    par = _scan_block(st, (-3.0, -2.0), (3.0, 2.0), 0.1, 10.0, (0.2, 0.0, 0.1), "cpu")
+    assert tuple(par.shape) == (2, _PARAM_DOUBLES) and _PARAM_DOUBLES == 13 and par.dtype == torch.float64
+    assert par.device.type == "cpu"
+    a = par.numpy()
+    np.testing.assert_array_equal(a[:, 0:4], [[-3.0, 3.0, 0.1, 10.0], [-2.0, 2.0, 0.1, 10.0]])
+    np.testing.assert_array_equal(a[:, 4:7], [[1.0, 2.0, 0.5], [3.0, 4.0, -0.25]])
+    np.testing.assert_array_equal(a[:, 7:10], [[0.2, 0.0, 0.1], [0.2, 0.0, 0.1]])
+    assert (a[:, 10:] == 0).all() and not np.signbit(a[:, 10:]).any()
+
+
+@pytest.mark.parametrize("cycles", [0, 2])
+@pytest.mark.parametrize("T", [1, 10])
+def test_log_allocators_match_the_documented_table(cycles, T):
+    """keys, shapes, dtypes and initial fills of the logs: the table of run_closed_loop's docstring and LonLoop.episode's"""
+    import torch
+    from neupan_amd.lon import _group_logs, _lon_logs
+    from neupan_amd.world import _LOG_ORDER, _run_logs
+    B, G, c = 1, 3, cycles
+    f32, f64, i32, bl = torch.float32, torch.float64, torch.int32, torch.bool
+    run = {"states": ((c + 1, B, 3), f64, None), "actions": ((c, B, 2), f32, 0), "stop": ((c, B), bl, False),
+           "clearance": ((c, B), f64, float("inf")), "controls": ((c, B, 2, T), f32, 0), "n_points": ((c, B), i32, 0)}
+    lon = {"loss": ((c, B), f32, 0), "stuck": ((c, B), bl, False), "ended": ((c, B), bl, False), "theta": ((c, B, 8), f32, 0)}
+    grp = {"group_theta": ((c, G, 8), f32, 0), "group_loss": ((c, G), f64, 0), "group_used": ((c, G), i32, 0)}
+    for got, table in ((_run_logs(c, B, T, "cpu"), run), (_lon_logs(c, B, "cpu"), lon), (_group_logs(c, G, "cpu"), grp)):
+        assert set(got) == set(table)
+        for k, (shape, dtype, fill) in table.items():
+            t = got[k]
+            assert tuple(t.shape) == shape and t.dtype == dtype and t.device.type == "cpu" and t.is_contiguous(), k
+            if fill is not None:                                 # (states: uninitialised; row 0 is the caller's to fill)
+                assert bool((t == fill).all()), k
+    assert sorted(_LOG_ORDER) == sorted(run)                     # the six addresses the kernels take are these six logs
