@@ -12,12 +12,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libneupan_amd.so")
-# The product build.  NPA_EXPERIMENTS=1 in the environment adds the experiments on record (the active-set
-# launch, the first form of the geometric selection) and their knobs.
+# The product build.  NPA_EXPERIMENTS=1 in the environment adds the one experiment on record that is still compiled (DESIGN.md
+# section 7: the first form of the geometric selection, select_kernel<E, true>) and its knob, NPA_SELECT_V1.
 EXPERIMENTS = os.environ.get("NPA_EXPERIMENTS", "0") not in ("", "0")
 SOURCES = ["dune.hip", "nrmp_qp.hip", "frontend.hip", "dune_labels.hip", "c_api.hip", "create.hip", "pack_image.hip", "serve_group.hip",
-           "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip"] + \
-          (["aset_reduce.hip"] if EXPERIMENTS else [])
+           "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip"]
 # -ffp-contract=fast-honor-pragmas is hipcc's default for device code, stated here so that it is the BUILD's property, not the
 # compiler's: the bit-exact legs (A / B / C, fa against the reference's tensors) are written with __f*_rn intrinsics where the
 # reference rounds every operation, and with explicit fmaf where it does not

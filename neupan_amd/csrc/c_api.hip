@@ -21,12 +21,13 @@ extern "C" hipError_t npa_launch_select_geo(const DevParams& P, const float* wpa
                                             unsigned* stats, int debug, unsigned* audit, unsigned audit_thresh,
                                             unsigned audit_seed, float margin_scale, int rows_bf16, hipStream_t stream,
                                             hipEvent_t ev_start, hipEvent_t ev_stop);
-// Experiments on record (measured slower than the default path, or not finished) are compiled only with
-// -DNPA_EXPERIMENTS (NPA_EXPERIMENTS=1 python -m neupan_amd.build): the active-set launch in front of the interior-point launch
-// (aset_reduce.*), the first form of the geometric selection.  The default build has neither their kernels nor their environment
-// knobs.  (Round 6 retired the two one-launch experiments -- the forward call as one launch, the selection with one wave per
-// scene: a wave that walks the ten slices of its scene one after the other cannot win where launches are cheap and the chip is
-// empty, and lost 2 x where it is full)
+// The one experiment on record that is still compiled (measured slower than the default path) is the
+// first form of the geometric selection, select_kernel<E, true> behind NPA_SELECT_V1, and only with -DNPA_EXPERIMENTS
+// (NPA_EXPERIMENTS=1 python -m neupan_amd.build).  The default build has neither its kernel nor its environment knob.
+// (Retired from the tree, their measurements kept in DESIGN.md sections 3.3 and 7: round 6's two one-launch experiments -- the
+// forward call as one launch, the selection with one wave per scene: a wave that walks the ten slices of its scene one after
+// the other cannot win where launches are cheap and the chip is empty, and lost 2 x where it is full -- then the active-set
+// launch in front of the interior-point launch and the T = 20 QP instantiation with a stored Phi.)
 #ifdef NPA_EXPERIMENTS
 #define NPA_VERSION_SUFFIX " +experiments"
 #else
@@ -45,7 +46,7 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                                     float* out_s, float* out_u, float* out_d, float* out_min_distance,
                                     int* out_iters, float* out_nrmp_points, int* flags, float* state,
                                     double* qp_info, double* warm, float* trig_out, float* dbg_abc, float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, int aset_launch, const float* theta);
+                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta);
 extern "C" int npa_select_geo_group_supported(int E);
 extern "C" hipError_t npa_launch_select_geo_group(const DevParams& P, const SelGeoGroup& G, int n, int batch, int t0, int n_stride_max,
                                                   int debug, unsigned audit_thresh, float margin_scale, int rows_bf16,
@@ -68,7 +69,7 @@ extern "C" hipError_t npa_launch_ingest_unpack(int batch, int T, int n_stride, i
                                                hipStream_t stream);
 
 extern "C" const char* npa_last_error(void) { return g_err.c_str(); }
-extern "C" const char* npa_version(void) { return "neupan_amd 0.5.1 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
+extern "C" const char* npa_version(void) { return "neupan_amd 0.5.2 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
 // per-slice stride of the key buffer inside the workspace: none with geometric keys (select_kernel keeps them in LDS)
 static int kstride(const npa_handle* h) { return h->key_terms == 4 ? 0 : h->P.key_stride; }
 
@@ -115,7 +116,7 @@ static EventPair* next_event(npa_handle* h, std::vector<EventPair>& pool, size_t
 extern "C" int npa_profile_enable(npa_handle* h, int enable) {
   if (!h) return fail(NPA_E_ARG, "null handle");
   h->prof = enable != 0;
-  h->n_dune = h->n_sel = h->n_qp = h->n_aset = 0;
+  h->n_dune = h->n_sel = h->n_qp = 0;
   return NPA_OK;
 }
 
@@ -138,17 +139,8 @@ extern "C" int npa_profile_read(npa_handle* h, double* dune_ms_avg, double* sele
   HIP_TRY(avg(h->ev_dune, h->n_dune, dune_ms_avg));
   HIP_TRY(avg(h->ev_sel, h->n_sel, select_ms_avg));
   HIP_TRY(avg(h->ev_qp, h->n_qp, nrmp_ms_avg));
-  HIP_TRY(avg(h->ev_aset, h->n_aset, &h->last_aset_ms));
-  h->last_aset_n = (long long)h->n_aset;
   if (launches) *launches = (int64_t)h->n_qp;
-  h->n_dune = h->n_sel = h->n_qp = h->n_aset = 0;
-  return NPA_OK;
-}
-
-extern "C" int npa_profile_read_aset(npa_handle* h, double* aset_ms_avg, int64_t* launches) {
-  if (!h) return fail(NPA_E_ARG, "null handle");
-  if (aset_ms_avg) *aset_ms_avg = h->last_aset_ms;
-  if (launches) *launches = (int64_t)h->last_aset_n;
+  h->n_dune = h->n_sel = h->n_qp = 0;
   return NPA_OK;
 }
 
@@ -205,7 +197,7 @@ extern "C" int npa_nrmp_stage(npa_handle* h, int batch, const float* nom_s, cons
   if (int rc = check_theta_batch(h, batch, "npa_nrmp_stage")) return rc;
   HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
                         out_s, out_u, out_d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        qp_info, nullptr, nullptr, nullptr, nullptr, x64, (hipStream_t)stream, nullptr, nullptr, 0, h->theta));
+                        qp_info, nullptr, nullptr, nullptr, nullptr, x64, (hipStream_t)stream, nullptr, nullptr, h->theta));
   return NPA_OK;
 }
 
@@ -218,7 +210,7 @@ extern "C" int npa_nrmp_params(npa_handle* h, int batch, const float* nom_s, con
   // (the reference trajectory only enters the cost: the nominal arrays stand in for it, the kernel returns before the solve)
   HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, nom_s, nom_u, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, out_abc, h->P.M > 0 ? out_f : nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, 0,
+                        nullptr, nullptr, nullptr, out_abc, h->P.M > 0 ? out_f : nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr,
                         nullptr));         // (the linearisation and the hinge rows do not depend on the adjust parameters)
   return NPA_OK;
 }
@@ -397,9 +389,7 @@ extern "C" int npa_group_mergeable(int n, const npa_forward_call* calls) {
   const DevParams& P = h0->P;
   const bool dune0 = P.M > 0 && calls[0].points != nullptr;
   if (dune0 && !(h0->key_terms == 4 && !h0->select_v1 && !h0->rows_bf16 && npa_select_geo_group_supported(P.E))) return 0;
-  if (!npa_qp_group_supported(P.T, P.M) || h0->qp_generic || P.qp_aset || (h0->aset_auto && calls[0].batch <= h0->aset_small_batch) ||
-      h0->cal.key_auto)
-    return 0;
+  if (!npa_qp_group_supported(P.T, P.M) || h0->qp_generic || h0->cal.key_auto) return 0;
   if (calls[0].iter_num < 1 || calls[0].iter_num > P.K) return 0;       // (the call-by-call path reports that)
   for (int c = 0; c < n; ++c) {
     const npa_handle* h = calls[c].h;
@@ -559,26 +549,12 @@ extern "C" int npa_forward_iter(npa_handle* h, int k) {
                                 pc->n_points, flags, gkeys, ws + L.trig, mu, lam, pts, dist, count, h->key_terms, h->key_e0,
                                 h->sel_stats_dev, 0, stream, evs ? evs->a : nullptr, evs ? evs->b : nullptr));
   }
-  // the active-set launch in front of the interior-point launch (nrmp_qp.hip, top of the kernel): scenes it finishes are skipped
-  // by the launch behind it.  Register-resident T = 10 / M = 10 instantiation only; small batches keep the single launch (a
-  // launch boundary costs ~10 us of a latency-bound chain: NPA_QP_ASET_MIN_BATCH, default 32)
-  const bool aset_forced = P.qp_aset && batch >= h->aset_min_batch;
-  const bool aset_small = h->aset_auto && batch <= h->aset_small_batch && k >= h->aset_from_iter;
-  if ((aset_forced || aset_small) && h->qp_warm && P.T == 10 && P.M == 10 && !h->qp_generic) {
-    EventPair* eva = next_event(h, h->ev_aset, h->n_aset);
-    DevParams Pa = P;
-    Pa.qp_aset = 1;
-    HIP_TRY(npa_launch_qp(Pa, batch, 0, cur_s, cur_u, pc->ref_s, pc->ref_us, mu, lam, pts, dist, count, cur_s, cur_u,
-                          cur_d, pc->out_s, pc->out_u, pc->out_d, pc->out_md, pc->out_iters, pc->out_np, flags,
-                          pc->state, qp_info, (double*)(ws + L.warm), pc->dune ? ws + L.trig : nullptr,
-                          nullptr, nullptr, nullptr, stream, eva ? eva->a : nullptr, eva ? eva->b : nullptr, 1, pc->theta));
-  }
   EventPair* ev = next_event(h, h->ev_qp, h->n_qp);
   HIP_TRY(npa_launch_qp(P, batch, 0, cur_s, cur_u, pc->ref_s, pc->ref_us, mu, lam, pts, dist, count, cur_s, cur_u,
                         cur_d, pc->out_s, pc->out_u, pc->out_d, pc->out_md, pc->out_iters, pc->out_np, flags,
                         pc->state, qp_info, h->qp_warm ? (double*)(ws + L.warm) : nullptr, pc->dune ? ws + L.trig : nullptr,
                         nullptr, nullptr, nullptr, stream,
-                        ev ? ev->a : nullptr, ev ? ev->b : nullptr, 0, pc->theta));
+                        ev ? ev->a : nullptr, ev ? ev->b : nullptr, pc->theta));
   if (h->cal.key_auto && pc->dune && k == P.K - 1)
     HIP_TRY(hipMemcpyAsync(h->sel_stats_host, h->sel_stats_dev, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   return NPA_OK;

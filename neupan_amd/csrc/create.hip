@@ -73,16 +73,8 @@ static Knobs read_knobs() {
 }
 
 #ifdef NPA_EXPERIMENTS
-// the knobs of the experiments build, per handle
-static void read_experiment_knobs(npa_handle* h) {
-  h->qp_scan_wide = getenv("NPA_QP_NOSCAN_WIDE") == nullptr;
-  h->P.qp_aset = (getenv("NPA_QP_ASET") != nullptr && atoi(getenv("NPA_QP_ASET")) != 0) ? 1 : 0;
-  h->aset_auto = getenv("NPA_QP_ASET") == nullptr;
-  if (const char* env = getenv("NPA_QP_ASET_SMALL")) { int v = atoi(env); if (v >= 0) h->aset_small_batch = v; }
-  if (const char* env = getenv("NPA_QP_ASET_FROM")) { int v = atoi(env); if (v >= 1) h->aset_from_iter = v; }
-  if (const char* env = getenv("NPA_QP_ASET_MIN_BATCH")) { int v = atoi(env); if (v >= 1) h->aset_min_batch = v; }
-  h->select_v1 = getenv("NPA_SELECT_V1") != nullptr;
-}
+// the knob of the experiments build, per handle
+static void read_experiment_knobs(npa_handle* h) { h->select_v1 = getenv("NPA_SELECT_V1") != nullptr; }
 #endif
 
 // ---- calibration ------------------------------------------------------------------------------------------------------------
@@ -539,7 +531,6 @@ extern "C" int npa_destroy(npa_handle* h) {
   for (auto& p : h->ev_dune) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (auto& p : h->ev_sel) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   for (auto& p : h->ev_qp) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
-  for (auto& p : h->ev_aset) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
   h->wpack = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_pack_mu);           // (the last owner frees the buffer; a create of the same key waits or misses)

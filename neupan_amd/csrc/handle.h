@@ -147,19 +147,9 @@ struct npa_handle {
   int calls_window = 0, hold = 0;
   // profiling (bench.py): HIP events on the launch stream around every stage launch
   bool prof = false;
-  std::vector<EventPair> ev_dune, ev_sel, ev_qp, ev_aset;
-  size_t n_dune = 0, n_sel = 0, n_qp = 0, n_aset = 0;
-  double last_aset_ms = 0.0;             // average of the active-set launches seen by the last npa_profile_read
-  long long last_aset_n = 0;
-  int aset_min_batch = 32;               // NPA_QP_ASET_MIN_BATCH: smallest batch that gets the extra active-set launch when NPA_QP_ASET=1
-  // a call of very few scenes is bound by the LATENCY of its solves (one wave each, nothing else on the chip), not by wave
-  // slots; measured over 24 scenes one at a time (profiles/r04_latency_breakdown.txt) the active-set launch from PAN iteration
-  // 4 on takes 2.5 % off the mean and 9 % off the median of a single-scene call -- too little to put another code path on the
-  // default single-scene route, so the rule ships switched off: NPA_QP_ASET_SMALL=1 (largest batch it applies to) turns it on,
-  // NPA_QP_ASET_FROM moves its first iteration.
-  bool aset_auto = true, qp_generic = false;
-  int aset_small_batch = 0, aset_from_iter = 4;
-  bool qp_scan_wide = true;              // (NPA_QP_NOSCAN_WIDE unset: the wide-scan T = 20 instantiation; experiments build only otherwise)
+  std::vector<EventPair> ev_dune, ev_sel, ev_qp;
+  size_t n_dune = 0, n_sel = 0, n_qp = 0;
+  bool qp_generic = false;
 };
 
 inline int mdim(const DevParams& P) { return P.M > 0 ? P.M : 1; }

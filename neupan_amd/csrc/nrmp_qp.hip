@@ -30,7 +30,6 @@
 // wave reductions are DPP (quad_perm / row_mirror) + 4 readlanes, and every division in a
 // serial loop is replaced by a reciprocal computed once per iteration.
 #include "pan_common.h"
-#include "aset_reduce.h"
 #include <hip/hip_ext.h>
 #include <cstdlib>
 #include <type_traits>
@@ -39,18 +38,9 @@
 
 static bool qp_fast_path(int T, int M) { return (T == 10 || T == 20) && M == 10; }
 
-// LDS bytes of one scene; `fast` = the register-resident instantiation (packed H, L and P staging)
-static bool qp_scan_wide() {
-#ifdef NPA_EXPERIMENTS       // (NPA_QP_NOSCAN_WIDE=1: the T = 20 instantiation with a stored Phi, for A/B measurements)
-  static const bool v = getenv("NPA_QP_NOSCAN_WIDE") == nullptr;
-  return v;
-#else
-  return true;
-#endif
-}
-// LDS bytes of one scene; fast = the register-resident instantiation (packed H, L and P staging); scan = its form
-// without a stored Phi (T <= 16, or T <= 32 with the wide scans)
-extern "C" size_t npa_qp_shmem_bytes_path2(int T, int M, int fast, int scan) {
+// LDS bytes of one scene; `fast` = the register-resident instantiation (packed H, L and P staging, the scan forms in place
+// of a stored Phi)
+extern "C" size_t npa_qp_shmem_bytes_path(int T, int M, int fast) {
   const bool obs = M > 0;
   size_t nu = 2 * T, ldp = nu + 1, mcd = 8 * T - 4 + 2 * T, mf = obs ? (size_t)T * M : 0, npair = nu * (nu + 1) / 2;
   const size_t mfe = (mf + 1) & ~(size_t)1;
@@ -58,17 +48,13 @@ extern "C" size_t npa_qp_shmem_bytes_path2(int T, int M, int fast, int scan) {
   const bool regrows = fast && M > 0 && M % 2 == 0 && T * M / 2 <= QP_THREADS && 5 * T - 2 <= QP_THREADS;
   const size_t rows = (regrows ? 3 : 6) * mcd + (regrows ? 5 : 9) * mfe;
   // (SLIM, nrmp_qp_body.inc: the wide-scan instantiation folds the packed H and the packed factor L into one block)
-  const bool slim = fast && scan && T > 16;
+  const bool slim = fast && T > 16;
   const size_t mats = slim ? nu * (nu + 1) / 2 : (fast ? nu * (nu + 1) / 2 + nu * ldp : (size_t)T * 2 * ldp + 2 * nu * ldp);
-  const size_t phi = (fast && scan) ? 0 : (size_t)T * 3 * ldp;
+  const size_t phi = fast ? 0 : (size_t)T * 3 * ldp;
   size_t d = rows + phi + mats + 4 * (T * 3) + T * QP_ABC_LD + (((size_t)T * QP_ST_LD + 1) & ~(size_t)1) + nu + T + (nu + T) + nu + T + nu +
-             ((fast && scan) ? 2 * (size_t)T : 0);
+             (fast ? 2 * (size_t)T : 0);
   size_t bytes = d * sizeof(double) + (fast ? 0 : 2 * ((npair + 7) & ~(size_t)7));
   return (bytes + 15) & ~(size_t)15;
-}
-extern "C" size_t npa_qp_shmem_bytes_path(int T, int M, int fast) {
-  const bool scan = fast && (T <= 16 || (T <= 32 && qp_scan_wide()));
-  return npa_qp_shmem_bytes_path2(T, M, fast, scan ? 1 : 0);
 }
 
 extern "C" size_t npa_qp_shmem_bytes(int T, int M) { return npa_qp_shmem_bytes_path(T, M, 0); }
@@ -81,24 +67,16 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                                     float* out_min_distance, int* out_iters, float* out_nrmp_points, int* flags,
                                     float* state, double* qp_info, double* warm, float* trig_out, float* dbg_abc,
                                     float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, int aset_launch,
-                                    const float* theta) {
+                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;     // tests: the generic (LDS) instantiation for every (T, M)
   const bool fast = qp_fast_path(P.T, P.M) && !force_generic;
   const size_t shmem = npa_qp_shmem_bytes_path(P.T, P.M, fast ? 1 : 0);      // one scene (wave) per workgroup, see the kernel
-  // (T = 20 without the wide scans keeps Phi: npa_qp_shmem_bytes_path follows the same switch)
   const int nblocks = batch;
   static NpaDeviceOnce attr_set;       // (per device: the attribute is, and a process may hold handles on several GPUs)
   int dev_ = 0;
   if (attr_set.need(&dev_)) {
     hipFuncSetAttribute(reinterpret_cast<const void*>(nrmp_qp_kernel<0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute(reinterpret_cast<const void*>(nrmp_qp_kernel<10, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#ifdef NPA_EXPERIMENTS
-    hipFuncSetAttribute(reinterpret_cast<const void*>(nrmp_qp_kernel<10, 10, false, false, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#endif
-#ifdef NPA_EXPERIMENTS
-    hipFuncSetAttribute(reinterpret_cast<const void*>(nrmp_qp_kernel<20, 10>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#endif
     hipFuncSetAttribute(reinterpret_cast<const void*>(nrmp_qp_kernel<20, 10, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set.done(dev_);
   }
@@ -108,21 +86,8 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                         cur_s_out, cur_u_out, cur_d_out, out_s, out_u, out_d, out_min_distance, out_iters,            \
                         out_nrmp_points, flags, state, qp_info, warm, scene0, batch,                                 \
                         QpBackward{nullptr, nullptr, nullptr, nullptr, nullptr, dbg_abc, dbg_f, dbg_x}, trig_out, theta)
-  const bool scan_wide = qp_scan_wide();
-  if (aset_launch) {
-    // the active-set launch that precedes the interior-point launch of the same PAN iteration (see the kernel's top)
-#ifdef NPA_EXPERIMENTS
-    if (!(P.T == 10 && P.M == 10 && !force_generic && P.qp_aset && warm && flags)) return hipErrorInvalidValue;
-    QP_LAUNCH(10, 10, false, false, 2, true);
-#else
-    return hipErrorInvalidValue;          // (the active-set instantiation exists in the experiments build only)
-#endif
-  }
-  else if (P.T == 10 && P.M == 10 && !force_generic) QP_LAUNCH(10, 10);
-  else if (P.T == 20 && P.M == 10 && !force_generic && scan_wide) QP_LAUNCH(20, 10, false, true);
-#ifdef NPA_EXPERIMENTS
-  else if (P.T == 20 && P.M == 10 && !force_generic) QP_LAUNCH(20, 10);
-#endif
+  if (fast && P.T == 10) QP_LAUNCH(10, 10);
+  else if (fast && P.T == 20) QP_LAUNCH(20, 10, false, true);
   else QP_LAUNCH(0, 0);
 #undef QP_LAUNCH
   return hipGetLastError();
@@ -132,7 +97,7 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
 // grid (batch, n).  The register-resident instantiations only (c_api.hip keeps everything else call by call).
 extern "C" int npa_qp_group_supported(int T, int M) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;
-  return !force_generic && M == 10 && (T == 10 || (T == 20 && qp_scan_wide())) ? 1 : 0;
+  return !force_generic && M == 10 && (T == 10 || T == 20) ? 1 : 0;
 }
 extern "C" hipError_t npa_launch_qp_group(const DevParams& P, const QpGroup& G, int n, int batch, hipStream_t stream,
                                           hipEvent_t ev_start, hipEvent_t ev_stop) {
@@ -160,7 +125,7 @@ extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, cons
                                              const float* grad_u, const float* grad_d, float* grad_theta,
                                              float* grad_nom_s, double* qp_info, hipStream_t stream, const float* theta) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;
-  const bool fast = qp_fast_path(P.T, P.M) && !force_generic && (P.T <= 16 || qp_scan_wide());
+  const bool fast = qp_fast_path(P.T, P.M) && !force_generic;
   const size_t wave_bytes = npa_qp_shmem_bytes_path(P.T, P.M, fast ? 1 : 0);
   static NpaDeviceOnce attr_set;
   int dev_ = 0;

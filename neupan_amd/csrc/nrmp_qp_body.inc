@@ -6,17 +6,14 @@
 // (the GLOBAL scene number: the row of every per-scene array, theta included).
   double* sm = sm_all;
   if (flags && flags[b * 4 + 0]) return;
-  // Two launches per PAN iteration when the active-set iteration is on (P.qp_aset): the ASET instantiation goes first and tries
-  // the scenes whose previous solve converged; a scene it finishes (solution, warm record, stop test: the same tail as here)
-  // is marked in flags[3], and the interior-point instantiation that follows skips it.  A scene the attempt gives up on is
-  // left untouched (nothing of this kernel reaches global memory before its tail).
-  if constexpr (ASET_T) {
-    if (!(warm && flags && flags[b * 4 + 2] && P.qp_aset)) return;
-  } else {
-    if (flags && flags[b * 4 + 3]) {
-      if (lane == 0) flags[b * 4 + 3] = 0;
-      return;
-    }
+  // ASET_T is still a template parameter because the counter records of profiles/ and tests/test_bench_contract.py look the
+  // kernels up by their demangled names, which spell every argument out
+  static_assert(!ASET_T, "the active-set launch is retired (DESIGN.md 3.3): ASET_T only keeps the kernels' names");
+  // REMNANT of the retired active-set launch, kept because removing it changes the pinned machine code: nothing sets flags[3]
+  // any more, so this skip never fires.  It leaves with the next counter collection (DESIGN.md section 7).
+  if (flags && flags[b * 4 + 3]) {
+    if (lane == 0) flags[b * 4 + 3] = 0;
+    return;
   }
   // this wave is a long dependent chain that shares its SIMD with throughput-bound selection waves of
   // the other batches in flight: win the issue arbitration, it needs few slots but needs them promptly
@@ -51,6 +48,8 @@
   // SCAN: the products with Phi, the blocks of P_t and the rows of K' are built from per-step sums over the horizon (lane =
   // t, DPP row scans) -- Phi itself is never stored (5 KB of the scene's LDS block at T = 10, 20 KB at T = 20)
   constexpr bool SCAN = TT > 0 && (TT <= 16 || (SCANW && TT <= 32));
+  // SCANW is still a template parameter for the kernels' names (as ASET_T above): every fixed horizon takes the scan forms
+  static_assert(TT == 0 || SCAN, "a fixed horizon without SCAN was the stored-Phi fast path, retired (DESIGN.md 3.3)");
   constexpr bool WIDE = TT > 16;
   // SLIM (the T = 20 instantiation, round 6): the scene's LDS block was 51 KB -- three scenes per CU, 0.75 waves per SIMD, a quarter
   // of the SIMDs without a QP wave.  Two of its blocks are folded: (i) the packed triangle Hm (band terms only, zero elsewhere;
@@ -69,7 +68,7 @@
   // D0 rows that exist once in the row that does not need them alone (j < D0 going down, j >= 16 going up: those keep the v_readlane
   // route, 6 of the 190 trailing updates, 4 of the 20 steps of each substitution).  `va` = the matrix row of a lane, `von` = the
   // lane holds one; every other instantiation: va = lane, von = lane < 2T, the code it had.
-  constexpr bool DPPB = TT > 0 && NU > 16 && NU <= 20 && !BWD && !ASET_T && SCAN;
+  constexpr bool DPPB = SCAN && NU > 16 && NU <= 20 && !BWD;
   constexpr int D0 = DPPB ? NU - 16 : 0;
   const int va = DPPB ? (lane < NU ? lane : (lane < 32 ? lane - 16 : 0)) : lane;
   const bool von = DPPB ? lane < 32 : lane < nu;
@@ -264,19 +263,16 @@
       acc += W0 * Pt[a] * Pt[c] + W1 * Pt[ldp + a] * Pt[ldp + c] + W2 * Pt[2 * ldp + a] * Pt[2 * ldp + c];
     }
     if (a == c && !(a & 1)) acc += 2.0 * pu * pu;
-    if constexpr (TT > 0) {
-      Hm[p] = acc;                          // p = a(a+1)/2 + c: the packed lower triangle
-    } else {
-      Hm[a * ldk + c] = acc;
-      Hm[c * ldk + a] = acc;
-    }
+    Hm[a * ldk + c] = acc;
+    Hm[c * ldk + a] = acc;
   }
   if constexpr (TT > 0 && !SLIM) {              // the pair table is done with: its block becomes the zero-padded L
     LSYNC();
     for (int q = lane; q < nu * ldk; q += QP_THREADS) Km[q] = 0.0;
   }
   // fast path: this lane's entries of H that receive the band terms of C_u' D C_u
-  double hdiag = 0, hoff = 0;
+  double hdiag = 0;
+  const double hoff = 0;                        // (the [a][a-2] entry of the constant block: zero now that H carries no Phi' W Phi)
   for (int q = lane; q < 3 * T; q += QP_THREADS) {
     int t = q / 3, k = q - 3 * t;
     const float qsk = k == 0 ? qs0 : (k == 1 ? qs1 : qs2);
@@ -369,14 +365,7 @@
   const double inv_m = uni64(1.0 / m_tot);
   const double pub = (von && !(va & 1)) ? -2.0 * pu * (double)__fmul_rn(p_u, rus[va >> 1]) : 0.0;
   LSYNC();
-  if constexpr (SCAN) {
-    hdiag = (lane < NU && !(lane & 1)) ? 2.0 * pu * pu : 0.0;
-  } else if constexpr (TT > 0) {
-    if (lane < NU) {
-      hdiag = Hm[lane * (lane + 1) / 2 + lane];
-      hoff = lane >= 2 ? Hm[lane * (lane + 1) / 2 + lane - 2] : 0.0;
-    }
-  }
+  if constexpr (SCAN) hdiag = (lane < NU && !(lane & 1)) ? 2.0 * pu * pu : 0.0;
 
   double best_merit = 1e300, last_mu = 0;
   int best_it = 0, stall = 0, status = 0, it = 0;
@@ -407,13 +396,8 @@
       int t = q / 3, k = q - 3 * t;
       const double* Pr = Phi + ((size_t)t * 3 + k) * ldp;
       double a0 = 0, a1 = 0;
-      if constexpr (TT > 0) {          // Phi[t][k][c] is stored as 0 beyond column 2t+1
-#pragma unroll
-        for (int c = 0; c < NU; c += 2) { a0 = fma(Pr[c], v[c], a0); a1 = fma(Pr[c + 1], v[c + 1], a1); }
-      } else {
-        const int cend = 2 * (t + 1);
-        for (int c = 0; c < cend; c += 2) { a0 = fma(Pr[c], v[c], a0); a1 = fma(Pr[c + 1], v[c + 1], a1); }
-      }
+      const int cend = 2 * (t + 1);
+      for (int c = 0; c < cend; c += 2) { a0 = fma(Pr[c], v[c], a0); a1 = fma(Pr[c + 1], v[c + 1], a1); }
       out3[q] = a0 + a1;
     }
   };
@@ -438,32 +422,9 @@
     }
     if (lane < nu) {
       const int a = lane;
-      if constexpr (TT > 0) {        // Phi[t][k][a] is stored as 0 for t < a/2: no lane-dependent trip count
-        double a0 = 0, a1 = 0, a2 = 0;
-        if constexpr (TT <= 10) {
-          // column a of Phi on its way before the sums start (the loads were issued six at a time with a wait after each
-          // batch); at T = 20 the 60 values do not fit beside the rest
-          double ph[3 * TT];
-#pragma unroll
-          for (int q = 0; q < 3 * TT; ++q) ph[q] = Phi[(size_t)q * ldp + a];
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int t = 0; t < TT; ++t) {
-            a0 = fma(ph[t * 3], in3[t * 3], a0); a1 = fma(ph[t * 3 + 1], in3[t * 3 + 1], a1); a2 = fma(ph[t * 3 + 2], in3[t * 3 + 2], a2);
-          }
-        } else {
-#pragma unroll
-          for (int t = 0; t < TT; ++t) {
-            const double* Pt = Phi + (size_t)t * 3 * ldp;
-            a0 = fma(Pt[a], in3[t * 3], a0); a1 = fma(Pt[ldp + a], in3[t * 3 + 1], a1); a2 = fma(Pt[2 * ldp + a], in3[t * 3 + 2], a2);
-          }
-        }
-        acc = a0 + a1 + a2;
-      } else {
-        for (int t = a >> 1; t < T; ++t) {
-          const double* Pt = Phi + (size_t)t * 3 * ldp;
-          acc += Pt[a] * in3[t * 3] + Pt[ldp + a] * in3[t * 3 + 1] + Pt[2 * ldp + a] * in3[t * 3 + 2];
-        }
+      for (int t = a >> 1; t < T; ++t) {
+        const double* Pt = Phi + (size_t)t * 3 * ldp;
+        acc += Pt[a] * in3[t * 3] + Pt[ldp + a] * in3[t * 3 + 1] + Pt[2 * ldp + a] * in3[t * 3 + 2];
       }
     }
     return acc;
@@ -507,36 +468,11 @@
   int it_total = 0, warm_code = 0;       // diagnostics: iterations over all attempts; 1 warm start used, 2 / 3 dropped at it 0 / 6, 4 not converged, 5 cold retry
   bool warm_now = can_warm;              // the solve in progress started from the previous solution
   bool need_cold = false;                // re-initialise at the top of the next iteration (a dropped warm attempt)
-  // ---- active-set iteration on the warm solves (branch qp-active-set; NPA_QP_ASET=1; T = 10 / M = 10 instantiation) ----------
-  // tests/tools/qp_active_set_study.py states the method (active_set_solve_kernel_form with project_d) and measures it: from the
-  // previous PAN iteration's solution the guess of the active set reproduces itself after 1.0 - 1.3 factorisations on ~90 % of the
-  // QPs behind the warm-start gate.  Here the loop body below is REUSED: seeded with l = ro e, w = 0 on the hinge rows that are on
-  // (l = 0, w = slack on the others) and with l = 0 on every linear row, its residual phase, per-step blocks, K' build,
-  // factorisation and predictor pass compute exactly the Newton step of the guessed equality-constrained QP in (u, d) -- d
-  // eliminated per step as always, or frozen (1/kappa := 0) where it sits on a bound it is pushed against.  What is new: the
-  // tight speed / rate rows are eliminated from K' before the factorisation (aset::reduce_matrix), the right-hand side follows
-  // (reduce_rhs), the step is expanded (expand) and taken in full, d is clipped, and the next pass of the residual phase
-  // recovers the multipliers of the tight rows (multipliers) and makes the next guess.  A guess that repeats is a KKT point:
-  // accepted when what is left of the dual residual is below QP_ASET_TOL; anything else falls back to the interior-point warm
-  // start (warm_init once more).  NOT VALIDATED ON A GPU yet (only aset_reduce.h's parts were, in their first form).
-  constexpr bool ASET = ASET_T && WARM && REGROWS && SCAN && (NU <= 20);      // (its own instantiation: the extra state spills for now)
-  bool aset = false, aset_done = false;
-  int aset_guess = 0;
-  int aset_why = 0;                      // diagnostics (qp_info[5..7]): 1 accepted, 2 a repeated guess left a residual, 3 guesses used up, 4 restarted cold
-  double aset_left = 0.0;                // the scaled residual of the last repeated guess
-  double aset_first = 0.0;               // merit of the seeded warm point (first pass)
-  unsigned long long ag_on0 = 0, ag_on1 = 0, ag_tp = 0, ag_tm = 0, ag_d = 0;      // the guess in force, as ballots
-  bool aset_onx = false, aset_ony = false, aset_dtp = false, aset_dtm = false, aset_dfix = false, aset_tied = false;
-  double aset_lam_p = 0.0, aset_lam_m = 0.0, aset_cx = 0.0, aset_resd = 0.0;
-  aset::Lane AL{};
-  const aset::Scratch AS{s3, dxu, Km, reinterpret_cast<int*>(dxd), ldk};      // all dead while reduce_matrix runs
-  if constexpr (ASET) aset = true;       // (this instantiation does nothing else: the gate is at the kernel's top)
   auto warm_init = [&]() __attribute__((always_inline)) {
     const double dl = QP_WARM_DELTA;
     for (int a = lane; a < nu; a += QP_THREADS) { xu[a] = wrm[a]; xbest[a] = wrm[a]; }
     for (int t = lane; t < T; t += QP_THREADS) { xd[t] = fmin(fmax(wrm[nu + t], dmin0), dmaxv); xbest[nu + t] = xd[t]; }
     LSYNC();
-    if constexpr (ASET) return;            // (the active-set iteration seeds its own rows from x in its residual phase)
     phi_mul(xu, s3);
     LSYNC();
     if constexpr (REGROWS) {
@@ -567,16 +503,8 @@
     LSYNC();
   };
   if (WARM && warm_now) warm_init();
-  if constexpr (ASET) {
-    if (aset) {
-      // an interior-point iterate sits 1e-15 inside its bounds: snap d, and take the record's multipliers of this lane's pair raw
-      for (int t = lane; t < T; t += QP_THREADS) { const double dv = xd[t]; xd[t] = dv >= dmaxv - 1e-8 ? dmaxv : (dv <= dmin0 + 1e-8 ? dmin0 : dv); }
-      if (lane < npu && my_pair.actf != 0.0) { const double* wl = wrm + nu + T + mf + 2 * lane; aset_lam_p = wl[0]; aset_lam_m = wl[1]; }
-      LSYNC();
-    }
-  }
   for (it = 0; it <= QP_MAX_IT; ++it) {
-    if constexpr (WARM && !ASET) {
+    if constexpr (WARM) {
       if (need_cold) {                     // restart of a dropped warm attempt, or of a jammed cold one: the cold start again
         need_cold = false;
         QP_COLD_INIT();
@@ -596,17 +524,6 @@
         double2 l = ld2(lf + i), w = LD_WF(h);
         const double2 a0 = ld2(fa0 + i), a1 = ld2(fa1 + i), f = LD_FF(h);
         const double sx = s3[t * 3], sy = s3[t * 3 + 1], d = xd[t];
-        if constexpr (ASET) {
-          if (aset) {                        // seed: a row that is on carries l = ro e and no slack, the others l = 0 and their slack
-            const double ex = f.x + d - (a0.x * sx + a1.x * sy), ey = f.y + d - (a0.y * sx + a1.y * sy);
-            aset_onx = ex > 0.0; aset_ony = ey > 0.0;
-            const double ro = (double)P.ro_obs;
-            l = make_double2(aset_onx ? ro * ex : 0.0, aset_ony ? ro * ey : 0.0);
-            w = make_double2(aset_onx ? 0.0 : fmax(-ex, 1e-300), aset_ony ? 0.0 : fmax(-ey, 1e-300));
-            st2(lf + i, l.x, l.y);
-            ST_ROW(Rwf, wf, h, w.x, w.y);
-          }
-        }
         const double rx = a0.x * sx + a1.x * sy - d - f.x + l.x * iro - w.x;
         const double ry = a0.y * sx + a1.y * sy - d - f.y + l.y * iro - w.y;
         ST_ROW(Rr3, r3, h, rx, ry);
@@ -630,15 +547,6 @@
       const PairC c = PAIR_C(p);
       double2 l = ld2(lc + 2 * p), w = LD_WC(p);
       const double cx = fma(-c.sb, xu[c.ib], xu[c.ia]);
-      if constexpr (ASET) {
-        if (aset) {                          // no weight from any linear row (the tight ones are eliminated, not penalised)
-          l = make_double2(0.0, 0.0);
-          w = c.actf != 0.0 ? make_double2(fmax(c.bp - cx, 1e-300), fmax(c.bm + cx, 1e-300)) : make_double2(1.0, 1.0);   // (a switched-off pair has no finite bound)
-          st2(lc + 2 * p, 0.0, 0.0);
-          ST_ROW(Rwc, wc, p, w.x, w.y);
-          aset_cx = cx;
-        }
-      }
       const double rp = (cx + w.x - c.bp) * c.actf, rm = (w.y - cx - c.bm) * c.actf;
       ST_ROW(Rr2, r2, p, rp, rm);
       if (BWD && adj_cap) st2(iwc + 2 * p, fmin(fast_rcp(w.x), QP_ADJ_DMAX / l.x), fmin(fast_rcp(w.y), QP_ADJ_DMAX / l.y));
@@ -686,19 +594,7 @@
         kap += ld_[2 * t] * iwd[2 * t] + ld_[2 * t + 1] * iwd[2 * t + 1];
         r1d = -(double)eta + ld_[2 * t] - ld_[2 * t + 1] + zs;       // g_d + C'lam - F'lam
       }
-      double ik = obs ? fast_rcp(kap) : 0.0;
-      if constexpr (ASET) {
-        if (aset) {
-          // d of this step: frozen where it sits on a bound it is pushed against (its row then carries eta - zs as a multiplier),
-          // frozen as well when no hinge row is on (nothing to eliminate it through; eta pushes it up: consistent only on d_max),
-          // else eliminated as always (no weight from its rows: kappa = ro |rows on|)
-          const double resd = (double)eta - zs, dcur = xd[t];
-          aset_dtp = obs && dcur >= dmaxv && resd > 0.0; aset_dtm = obs && dcur <= dmin0 && resd < 0.0;
-          aset_dfix = aset_dtp || aset_dtm || !(sg > 0.0);
-          aset_resd = resd;
-          if (aset_dfix) { ik = 0.0; r1d = 0.0; }
-        }
-      }
+      const double ik = obs ? fast_rcp(kap) : 0.0;
       double* S = St + t * QP_ST_LD;
       S[0] = s00 - v0 * v0 * ik; S[1] = s01 - v0 * v1 * ik; S[2] = s11 - v1 * v1 * ik;
       S[3] = v0; S[4] = v1; S[5] = sg; S[6] = ik; S[7] = r1d;
@@ -725,71 +621,7 @@
     const double mu = gsum * inv_m;
     const double merit = fmax(rmax, mu);
     last_mu = mu;
-#ifdef NPA_QP_DBGTRACE
-    if (qp_info && lane == 0 && it < 4) { double* qq = qp_info + (size_t)b * QP_INFO_STRIDE; qq[5 + 2 * it] = merit; qq[6 + 2 * it] = mu; }
-#endif
     if (!(merit == merit) || !(merit < 1e300)) { status = 2; break; }
-    if constexpr (ASET) {
-      if (aset) {
-        if (aset_guess == 0) {
-          aset_first = merit;
-          if (merit > QP_ASET_FIRST_MAX) { aset_why = 5; break; }      // far from a KKT point of any guess: the interior-point launch takes it
-        }
-        // (a) multipliers of the tight rows of the guess in force, from the gradient at this point (first pass: the warm record's)
-        double run_sum = 0.0;
-        const bool is_rate = lane >= 2 * T && lane < npu;
-        if (aset_guess > 0) {
-          double vt, bb;
-          aset::multipliers<NU>(lane < nu ? -r1u : 0.0, aset_tied, lane, AL, vt, bb, run_sum);
-          // a speed pair sits in its variable's lane; rate pair p = 2T + q leads INTO variable q + 2 and reads that lane
-          const double vt_r = aset::bperm_f64(vt, is_rate ? lane - 2 * T + 2 : lane);
-          const bool tp_prev = ((ag_tp >> lane) & 1ull) != 0, tm_prev = ((ag_tm >> lane) & 1ull) != 0;
-          if (lane < 2 * T) { aset_lam_p = tp_prev ? bb : 0.0; aset_lam_m = tm_prev ? -bb : 0.0; }
-          else if (is_rate) { aset_lam_p = tp_prev ? vt_r : 0.0; aset_lam_m = tm_prev ? -vt_r : 0.0; }
-        }
-        // (b) the next guess: a linear row is tight iff its multiplier plus its violation is positive
-        bool tp = false, tm = false;
-        if (lane < npu && my_pair.actf != 0.0) {
-          tp = aset_lam_p + (aset_cx - my_pair.bp) > 0.0;
-          tm = aset_lam_m + (-aset_cx - my_pair.bm) > 0.0;
-        }
-        const unsigned long long n_on0 = __ballot(aset_onx && lane < mf / 2), n_on1 = __ballot(aset_ony && lane < mf / 2);
-        const unsigned long long n_tp = __ballot(tp), n_tm = __ballot(tm);
-        const unsigned long long n_d = __ballot(aset_dtp && lane < T) | (__ballot(aset_dtm && lane < T) << 16) | (__ballot(aset_dfix && lane < T) << 32);
-        const bool same = aset_guess > 0 && n_on0 == ag_on0 && n_on1 == ag_on1 && n_tp == ag_tp && n_tm == ag_tm && n_d == ag_d;
-        bool give_up = false;
-        if (same) {
-          // this point is the KKT point of its own guess.  What can be left of the dual residual: the sum over a run that no
-          // speed row anchors (at its head), and eta - zs on a step whose d is not on a bound it is pushed against
-          double left = 0.0, viol = 0.0;
-          if (lane < nu && AL.head == lane && !AL.anchored) left = fabs(run_sum);
-          if (lane < T && obs && !(aset_dtp || aset_dtm)) left = fmax(left, fabs(aset_resd));
-          if (lane < npu && my_pair.actf != 0.0) viol = fmax(0.0, fmax(tp ? 0.0 : aset_cx - my_pair.bp, tm ? 0.0 : -aset_cx - my_pair.bm));
-          const double merit_a = wave_reduce<OpMax>(fmax(left * iscale_d, viol * iscale_p));
-          aset_left = merit_a;
-          if (merit_a <= QP_ASET_TOL) {
-            aset_why = 1;
-            best_merit = merit_a; best_it = it; last_mu = 0.0; stall = 0;
-            for (int a = lane; a < nu; a += QP_THREADS) xbest[a] = xu[a];
-            for (int t = lane; t < T; t += QP_THREADS) xbest[nu + t] = xd[t];
-            // the record the next solve starts from: the hinge rows carry theirs already; the linear rows get them here
-            if (lane < npu) st2(lc + 2 * lane, tp ? fmax(aset_lam_p, 0.0) : 0.0, tm ? fmax(aset_lam_m, 0.0) : 0.0);
-            if (lane < T && obs) st2(ld_ + 2 * lane, aset_dtp ? aset_resd : 0.0, aset_dtm ? -aset_resd : 0.0);
-            LSYNC();
-            aset_done = true;
-            break;
-          }
-          give_up = true;
-        }
-        if (give_up || aset_guess >= QP_ASET_MAX_GUESS) {     // not this time: the interior-point launch solves this scene
-          aset_why = give_up ? 2 : 3;
-          break;
-        }
-        ag_on0 = n_on0; ag_on1 = n_on1; ag_tp = n_tp; ag_tm = n_tm; ag_d = n_d;
-        ++aset_guess;
-      }
-    }
-    if constexpr (!ASET) {
     // a warm start that is not paying off is dropped at once: a good one starts at merit <= 1.2e-2 and needs 3 - 5
     // iterations with the adaptive step; one that starts far from feasibility is dropped before its first iteration, one
     // that is not below 3e-3 after three or has not reached 1e-4 after six is stuck (the one case in 1360 QPs went on for
@@ -850,7 +682,6 @@
         break;
       }
     }
-    }   // !ASET
     PROF(1); PROF_B(6);
 
     // ================= reduced KKT matrix, Cholesky =================
@@ -863,44 +694,25 @@
       // block row i are  K'[a][c] += (P_i B_i[:,a&1]) . Phi_i[:,c]  for c <= a   (3 FMAs each).
       {
         double* Pst = Yt;                              // [T][6] staging of P_t
-        if constexpr (SCAN) {
-          // A(t+1)...A(s) = I + (c_s - c_t) e_2' with c the prefix sum of a, so the blocks of P_t are suffix sums over
-          // s >= t of S_s, S_s c_s and c_s'S_s c_s (lane = t; no serial recursion, no broadcast of S'):
-          //   P_xy,xy = sS ;  P_xy,2 = sSc - sS c_t ;  P_22 = scSc - 2 c_t . sSc + c_t' sS c_t
-          // The state cost's weights W = diag(W0, W1, W2) enter here as well (S_s -> S_s + diag(W0, W1); W2 sits on the
-          // theta entry only and reaches P_22 as W2 x the number of steps s >= t): K' = band + sum_t Phi_t' (S'_t + W) Phi_t
-          // with no precomputed Phi' W Phi.
-          const bool on = lane < TT;
-          const double2 cp = ld2(cpre + 2 * (on ? lane : 0));
-          const double c0 = on ? cp.x : 0.0, c1 = on ? cp.y : 0.0;
-          const double s00 = on ? S0r + W0 : 0.0, s01 = on ? S1r : 0.0, s11 = on ? S2r + W1 : 0.0;
-          const double sc0 = s00 * c0 + s01 * c1, sc1 = s01 * c0 + s11 * c1;
-          double p00 = s00, p01 = s01, p11 = s11, t0 = sc0, t1 = sc1, t2 = c0 * sc0 + c1 * sc1;
-          scan_suffix3<WIDE>(p00, p01, p11, row0);
-          scan_suffix3<WIDE>(t0, t1, t2, row0);
-          const double u0 = p00 * c0 + p01 * c1, u1 = p01 * c0 + p11 * c1;
-          if (on) {
-            st2(Pst + lane * 6, p00, p01);
-            st2(Pst + lane * 6 + 2, t0 - u0, p11);
-            st2(Pst + lane * 6 + 4, t1 - u1, t2 - 2.0 * (c0 * t0 + c1 * t1) + (c0 * u0 + c1 * u1) + W2 * (double)(TT - lane));
-          }
-        } else {
-        double p00 = 0, p01 = 0, p02 = 0, p11 = 0, p12 = 0, p22 = 0;
-        // A_t = I + (a0, a1, 0)' e_2': lane t fetches its pair once, the chain below broadcasts them with v_readlane
-        // (an LDS load per step would sit on the serial path)
-        const double2 a01 = ld2(Abc + (lane < TT ? lane : 0) * QP_ABC_LD);
-#pragma unroll
-        for (int t = TT - 1; t >= 0; --t) {
-          if (t < TT - 1) {
-            const double a0 = readlane_f64(a01.x, t + 1), a1 = readlane_f64(a01.y, t + 1);
-            const double pa0 = p00 * a0 + p01 * a1, pa1 = p01 * a0 + p11 * a1, pa2 = p02 * a0 + p12 * a1;
-            p22 += 2.0 * pa2 + (a0 * pa0 + a1 * pa1);
-            p02 += pa0; p12 += pa1;
-          }
-          p00 += readlane_f64(S0r, t); p01 += readlane_f64(S1r, t); p11 += readlane_f64(S2r, t);
-          Pst[t * 6 + 0] = p00; Pst[t * 6 + 1] = p01; Pst[t * 6 + 2] = p02;
-          Pst[t * 6 + 3] = p11; Pst[t * 6 + 4] = p12; Pst[t * 6 + 5] = p22;
-        }
+        // A(t+1)...A(s) = I + (c_s - c_t) e_2' with c the prefix sum of a, so the blocks of P_t are suffix sums over
+        // s >= t of S_s, S_s c_s and c_s'S_s c_s (lane = t; no serial recursion, no broadcast of S'):
+        //   P_xy,xy = sS ;  P_xy,2 = sSc - sS c_t ;  P_22 = scSc - 2 c_t . sSc + c_t' sS c_t
+        // The state cost's weights W = diag(W0, W1, W2) enter here as well (S_s -> S_s + diag(W0, W1); W2 sits on the
+        // theta entry only and reaches P_22 as W2 x the number of steps s >= t): K' = band + sum_t Phi_t' (S'_t + W) Phi_t
+        // with no precomputed Phi' W Phi.
+        const bool on = lane < TT;
+        const double2 cp = ld2(cpre + 2 * (on ? lane : 0));
+        const double c0 = on ? cp.x : 0.0, c1 = on ? cp.y : 0.0;
+        const double s00 = on ? S0r + W0 : 0.0, s01 = on ? S1r : 0.0, s11 = on ? S2r + W1 : 0.0;
+        const double sc0 = s00 * c0 + s01 * c1, sc1 = s01 * c0 + s11 * c1;
+        double p00 = s00, p01 = s01, p11 = s11, t0 = sc0, t1 = sc1, t2 = c0 * sc0 + c1 * sc1;
+        scan_suffix3<WIDE>(p00, p01, p11, row0);
+        scan_suffix3<WIDE>(t0, t1, t2, row0);
+        const double u0 = p00 * c0 + p01 * c1, u1 = p01 * c0 + p11 * c1;
+        if (on) {
+          st2(Pst + lane * 6, p00, p01);
+          st2(Pst + lane * 6 + 2, t0 - u0, p11);
+          st2(Pst + lane * 6 + 4, t1 - u1, t2 - 2.0 * (c0 * t0 + c1 * t1) + (c0 * u0 + c1 * u1) + W2 * (double)(TT - lane));
         }
       }
       const int ar = DPPB ? va : (lane < NU ? lane : 0);
@@ -929,44 +741,32 @@
         const double g0 = Pi[0] * b0 + Pi[1] * b1 + Pi[2] * b2;
         const double g1 = Pi[1] * b0 + Pi[3] * b1 + Pi[4] * b2;
         const double g2 = Pi[2] * b0 + Pi[4] * b1 + Pi[5] * b2;
-        if constexpr (SCAN) {
-          // Phi_i[:, 2r + k] = (I + (c_i - c_r) e_2') B_r[:, k] for r <= i, so with G2 = g2 + g . c_i the entry is
-          //   g0 B_r[0,k] + g1 B_r[1,k] + (G2 - g . c_r) B_r[2,k]
-          // from wave-uniform loads of step r's B and c (two columns per step); columns beyond the row's own are garbage
-          // that nobody reads, as before
-          const double2 ci = ld2(cpre + 2 * i);
-          const double G2 = g2 + g0 * ci.x + g1 * ci.y;
-          // (software pipeline of depth one: step r + 1's five loads go out before step r's arithmetic -- with the loads
-          // and their use in the same step every step waited a full LDS latency, ~1 000 of this phase's 1 450 cycles; a
-          // deeper prefetch does not fit the register file here, where the demand of the kernel peaks)
-          const double* hrow = Hm + ar * (ar + 1) / 2;
-          double2 nb0 = ld2(Abc + 2), nb1 = ld2(Abc + 4), nb2 = ld2(Abc + 6), ncr = ld2(cpre);
-          double nh0 = hrow[0], nh1 = hrow[1];
+        // Phi_i[:, 2r + k] = (I + (c_i - c_r) e_2') B_r[:, k] for r <= i, so with G2 = g2 + g . c_i the entry is
+        //   g0 B_r[0,k] + g1 B_r[1,k] + (G2 - g . c_r) B_r[2,k]
+        // from wave-uniform loads of step r's B and c (two columns per step); columns beyond the row's own are garbage
+        // that nobody reads, as before
+        const double2 ci = ld2(cpre + 2 * i);
+        const double G2 = g2 + g0 * ci.x + g1 * ci.y;
+        // (software pipeline of depth one: step r + 1's five loads go out before step r's arithmetic -- with the loads
+        // and their use in the same step every step waited a full LDS latency, ~1 000 of this phase's 1 450 cycles; a
+        // deeper prefetch does not fit the register file here, where the demand of the kernel peaks)
+        const double* hrow = Hm + ar * (ar + 1) / 2;
+        double2 nb0 = ld2(Abc + 2), nb1 = ld2(Abc + 4), nb2 = ld2(Abc + 6), ncr = ld2(cpre);
+        double nh0 = hrow[0], nh1 = hrow[1];
 #pragma unroll
-          for (int r = 0; r < TT; ++r) {
-            const double2 bb0 = nb0, bb1 = nb1, bb2 = nb2, cr = ncr;
-            const double h0 = nh0, h1 = nh1;
-            if (r + 1 < TT) {
-              const double* o = Abc + (r + 1) * QP_ABC_LD;
-              nb0 = ld2(o + 2); nb1 = ld2(o + 4); nb2 = ld2(o + 6); ncr = ld2(cpre + 2 * (r + 1));
-              nh0 = hrow[2 * r + 2]; nh1 = hrow[2 * r + 3];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const double e = G2 - (g0 * cr.x + g1 * cr.y);
-            arow[2 * r] = fma(g0, bb0.x, fma(g1, bb1.x, fma(e, bb2.x, h0)));
-            arow[2 * r + 1] = fma(g0, bb0.y, fma(g1, bb1.y, fma(e, bb2.y, h1)));
-            __builtin_amdgcn_sched_barrier(0);
+        for (int r = 0; r < TT; ++r) {
+          const double2 bb0 = nb0, bb1 = nb1, bb2 = nb2, cr = ncr;
+          const double h0 = nh0, h1 = nh1;
+          if (r + 1 < TT) {
+            const double* o = Abc + (r + 1) * QP_ABC_LD;
+            nb0 = ld2(o + 2); nb1 = ld2(o + 4); nb2 = ld2(o + 6); ncr = ld2(cpre + 2 * (r + 1));
+            nh0 = hrow[2 * r + 2]; nh1 = hrow[2 * r + 3];
           }
-        } else {
-        const double* Ph = Phi + (size_t)i * 3 * ldp;  // Phi_i rows (zero beyond column 2i+1)
-#pragma unroll
-        for (int c = 0; c < NU; ++c) {
-          // (entries c > ar read other rows of the packed triangle: finite, and never used)
-          arow[c] = fma(g0, Ph[c], fma(g1, Ph[ldp + c], fma(g2, Ph[2 * ldp + c], Hm[ar * (ar + 1) / 2 + c])));
-          // (keep the scheduler from issuing all 4 NU loads ahead of the arithmetic: that is where the register
-          // demand of this kernel peaked, above the 256 a wave may hold at two waves per SIMD)
-          if ((c & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-        }
+          __builtin_amdgcn_sched_barrier(0);
+          const double e = G2 - (g0 * cr.x + g1 * cr.y);
+          arow[2 * r] = fma(g0, bb0.x, fma(g1, bb1.x, fma(e, bb2.x, h0)));
+          arow[2 * r + 1] = fma(g0, bb0.y, fma(g1, bb1.y, fma(e, bb2.y, h1)));
+          __builtin_amdgcn_sched_barrier(0);
         }
       }
       PROF(3);
@@ -974,42 +774,6 @@
       // computes on and above its diagonal are unused garbage and are not stored)
       // (written so that the next pivot's reciprocal square root -- the serial chain -- starts before the trailing
       // update of the current column, which is independent of it)
-      if constexpr (ASET) {
-        if (aset) {
-          // this lane's variable a = lane: the tight rate row into it (pair 2T + a - 2: u_a - u_(a-2) <= bp, -(..) <= bm) and its tight
-          // speed row (pair a: u_a <= bp, -u_a <= bm), from the guess in force
-          const bool isv = lane < nu, has_r = isv && lane >= 2;
-          const int pr = 2 * T + lane - 2;
-          const bool t_p = has_r && ((ag_tp >> pr) & 1ull) != 0, t_m = has_r && ((ag_tm >> pr) & 1ull) != 0;
-          const double rbp = aset::bperm_f64(my_pair.bp, has_r ? pr : lane), rbm = aset::bperm_f64(my_pair.bm, has_r ? pr : lane);
-          const double tieoff = t_p ? rbp : (t_m ? -rbm : 0.0);
-          const bool b_p = isv && ((ag_tp >> lane) & 1ull) != 0, b_m = isv && ((ag_tm >> lane) & 1ull) != 0;
-          aset_tied = t_p || t_m;
-          // the row build only fills the lower triangle (the factorisation reads nothing else); the reduction folds whole rows
-          // AND columns: complete the row from the other lanes' lower parts through the LDS matrix (free until L is parked)
-          if (lane < NU) {
-#pragma unroll
-            for (int c = 0; c < NU; ++c) Km[lane * ldk + c] = arow[c];
-          }
-          LSYNC();
-          {
-            const int a = lane < NU ? lane : 0;
-            int lo = lane;
-            asm volatile("" : "+v"(lo));
-#pragma unroll
-            // (both operands from LDS: with `c > lo ? Km[..] : arow[c]` the compiler selects between the two ADDRESSES, and an
-            // address of the register row escaping sends the whole row to scratch memory)
-            for (int c = 0; c < NU; ++c) { const double up = Km[c * ldk + a], low = Km[a * ldk + c]; arow[c] = c > lo ? up : low; }
-          }
-          LSYNC();
-          double adj;
-          aset::reduce_matrix<NU>(arow, tieoff, b_p || b_m, b_p ? my_pair.bp : -my_pair.bm, isv ? xu[lane] : 0.0, lane, AS, AL, adj);
-          r1u += adj;                        // the pass forms its right-hand side as (...) - r1u: K' offd leaves it through here
-          LSYNC();
-          if (lane < NU) Km[lane * ldk + NU - 1] = 0.0;       // (Km served as the transposition buffer: its last column is never parked)
-          LSYNC();
-        }
-      }
       double piv = readlane_f64(arow[0], 0);
       if (!(piv > 0.0)) chol_ok = false;
       double rinv = fast_rsqrt(piv);
@@ -1025,7 +789,7 @@
       // first chunk's loads in front of the pivot chain), the column staged in the Hm | L block -- free between the row build and the
       // parking of the factor -- in two alternating slots, so that pivot k's loads of column k - 1 may stand after its own store.
       // Without it every trailing update of the 40 x 40 factorisation takes the v_readlane route (LOOK = NU).
-      constexpr bool WLDS = NPA_QP_WIDE_LDS && SLIM && !ASET_T && !BWD && NU > 20;      // (the gradient instantiation has no registers to spare)
+      constexpr bool WLDS = NPA_QP_WIDE_LDS && SLIM && !BWD && NU > 20;      // (the gradient instantiation has no registers to spare)
       constexpr int LOOK = (NU > 20 && !WLDS) ? NU : QP_CHOL_LOOK;
       double lprev = 0.0;
       if constexpr (DPPB) {
@@ -1235,7 +999,6 @@
     }
     // (past 1e-11 the reduced matrix can lose positive definiteness in fp64: the best iterate stands, converged)
     if (!chol_ok) {
-      if constexpr (ASET) { aset_why = 4; break; }        // (the reduced matrix of the guess does not factor: the interior-point launch)
       if constexpr (WARM) {
         if (warm_now && !(best_merit <= 1e-10)) { warm_code = 4; it_total += it; warm_now = false; need_cold = true; it = -1; continue; }
       }
@@ -1273,9 +1036,8 @@
     // ================= predictor / corrector =================
     double sigma_mu = 0, alpha = 1.0, corr_w = 1.0;      // (corr_w: 1 with the second-order corrector, 0 for a plain centring step)
 #pragma nounroll
-    for (int pass = 0; pass < ((adj || ASET) ? 1 : 2); ++pass) {
+    for (int pass = 0; pass < (adj ? 1 : 2); ++pass) {
       PROF_C(7);
-      if constexpr (!ASET) {
       // per-row weights of the rhs, staged in dwf/dwc/dwd (overwritten by the directions below)
       //   tfw = (r4f + lf r3)/(wf + lf/ro) ; tcw = (lc r2 - r4c)/wc ; r4 = lam w [+ dw dl - sigma mu]
       // (pass 0 must not read dw / dl: they hold the previous iteration's directions, nothing at all in the first one)
@@ -1302,14 +1064,11 @@
         st2(dwc + i, af * ((l.x * r.x - r4x) * iw.x), af * ((l.y * r.y - r4y) * iw.y));
       }
       LSYNC();
-      }   // !ASET
       PROF_C(1);
       double pq0 = 0, pq1 = 0, rdr = 0;
       for (int t = lane; t < T; t += QP_THREADS) {
         double z0 = 0, z1 = 0, zs = 0;
-        if constexpr (ASET) {
-          // (the seeded rows carry no weights: nothing to sum)
-        } else if constexpr (HPAIR) {
+        if constexpr (HPAIR) {
           constexpr int HB = WV >= 3 ? 2 : MM / 2;
 #pragma unroll
           for (int j0 = 0; j0 < MM / 2; j0 += HB) {
@@ -1334,7 +1093,7 @@
         }
         double rd = 0;
         const double* S = St + t * QP_ST_LD;                                       // v0 v1 at [3] [4], 1/kappa [6], r1_d [7]
-        if (obs) rd = -S[7] - (ASET ? 0.0 : dwd[2 * t] - dwd[2 * t + 1]) + zs;           // rhs of the d rows
+        if (obs) rd = -S[7] - (dwd[2 * t] - dwd[2 * t + 1]) + zs;          // rhs of the d rows
         double e = rd * S[6];                                               // rhs_d / kappa
         rdr = rd;
         pq0 = -(z0 - S[3] * e);
@@ -1346,10 +1105,7 @@
       LSYNC();
       PROF_C(2);
       rr = phi_tmul(q3);
-      if (von) rr += -r1u - (ASET ? 0.0 : ct_mul(dwc, va));
-      if constexpr (ASET) {
-        if (aset) rr = aset::reduce_rhs<NU>(lane < nu ? rr : 0.0, lane, AL);      // Z'(r - K' offd) (offd went in with r1u), zero on the members that left
-      }
+      if (von) rr += -r1u - ct_mul(dwc, va);
       PROF_C(3);
       if constexpr (TT > 0) {
         // forward substitution L y = rhs, backward L' dx = y; lane i owns entry i and reads row i / column i of the
@@ -1404,7 +1160,7 @@
             for (int k = NU - 1; k >= 0; --k) rr = fma(-Lcol[k], readlane_f64(rr, k), rr);     // -> z
             }
           }
-        } else if constexpr (SLIM) {
+        } else if constexpr (SLIM) {         // (2T > 20)
           // packed L: entry (i, k) at i(i-1)/2 + k for k < i, the ZERO slot otherwise (one select on the address per element)
           // (the lane index opaque: else the 78 selected addresses are hoisted out of the solver loop and spilled)
           int lq = lr;
@@ -1415,16 +1171,8 @@
           asm volatile("" : "+v"(lq));
 #pragma unroll
           for (int k = NU - 1; k >= 1; --k) rr = fma(-Km[lq < k ? k * (k - 1) / 2 + lq : LZERO], readlane_f64(rr, k), rr);   // column lr -> z
-        } else {                             // (T = 20: 2 x 40 doubles ahead of the chains do not fit the register file)
-#pragma unroll
-          for (int k = 0; k < NU; ++k) rr = fma(-Km[lr * ldk + k], readlane_f64(rr, k), rr);
-#pragma unroll
-          for (int k = NU - 1; k >= 0; --k) rr = fma(-Km[k * ldk + lr], readlane_f64(rr, k), rr);
         }
         rr *= myinv;                         // dx_u
-        if constexpr (ASET) {
-          if (aset) rr = aset::expand<NU>(rr, lane, AS, AL);                        // du = Z z + offd (offd waits in s3[0 .. NU): nothing writes s3 before phi_mul(dxu) below)
-        }
       } else {
         for (int k = 0; k < nu; ++k) {
           double yk = readlane_f64(rr * myinv, k);
@@ -1446,9 +1194,6 @@
         dxd[t] = (rdr + St[t * QP_ST_LD + 3] * s3[t * 3] + St[t * QP_ST_LD + 4] * s3[t * 3 + 1]) * St[t * QP_ST_LD + 6];
       LSYNC();
       PROF_C(5);
-      if constexpr (ASET) {
-        if (aset) { alpha = 1.0; break; }    // the Newton step of the guess is taken in full; the rows are re-seeded, not moved
-      }
       // directions of multipliers / slacks and the step to the boundary
       double amax = 1.0, gap_aff = 0;
       // step to the boundary: dl, dw < 0 bound alpha by -l/dl, -w/dw -- taken as 1/alpha = max(1, -dl/l, -dw/w) over all rows: a
@@ -1517,31 +1262,29 @@
         // mu = 1e-3 for 27 iterations with every residual at 1e-10.  A step shorter than QP_CENTRAL_ALPHA (a blocked one: the full steps
         // of the end game keep the products balanced by themselves and skip this) is shortened x QP_CENTRAL_SHRINK, at most
         // QP_CENTRAL_TRIES times, until the products stay inside that wide neighbourhood.  oracle/condensed_ipm.py carries the same rule.
-        if constexpr (!ASET) {
-          for (int tr = 0; tr < QP_CENTRAL_TRIES && alpha < QP_CENTRAL_ALPHA; ++tr) {
-            double psum = 0.0, pmin = 1e300;
-            if constexpr (HPAIR) {
-              for (int h = lane; h < mf / 2; h += QP_THREADS) {
-                const double2 l = ld2(lf + 2 * h), w = LD_WF(h), dl = LD_DLF(h), dw = ld2(dwf + 2 * h);
-                const double px = (l.x + alpha * dl.x) * (w.x + alpha * dw.x), py = (l.y + alpha * dl.y) * (w.y + alpha * dw.y);
-                psum += px + py; pmin = fmin(pmin, fmin(px, py));
-              }
-            } else {
-              for (int i = lane; i < mf; i += QP_THREADS) {
-                const double pr = (lf[i] + alpha * dlf[i]) * (wf[i] + alpha * dwf[i]);
-                psum += pr; pmin = fmin(pmin, pr);
-              }
-            }
-            for (int p = lane; p < npc; p += QP_THREADS) {
-              const PairC c = PAIR_C(p);
-              const double2 l = ld2(lc + 2 * p), w = LD_WC(p), dl = LD_DLC(p), dw = ld2(dwc + 2 * p);
+        for (int tr = 0; tr < QP_CENTRAL_TRIES && alpha < QP_CENTRAL_ALPHA; ++tr) {
+          double psum = 0.0, pmin = 1e300;
+          if constexpr (HPAIR) {
+            for (int h = lane; h < mf / 2; h += QP_THREADS) {
+              const double2 l = ld2(lf + 2 * h), w = LD_WF(h), dl = LD_DLF(h), dw = ld2(dwf + 2 * h);
               const double px = (l.x + alpha * dl.x) * (w.x + alpha * dw.x), py = (l.y + alpha * dl.y) * (w.y + alpha * dw.y);
-              if (c.actf != 0.0) { psum += px + py; pmin = fmin(pmin, fmin(px, py)); }      // (a switched-off pair keeps l = 0: not a product)
+              psum += px + py; pmin = fmin(pmin, fmin(px, py));
             }
-            wave_reduce2<OpSum, OpMin>(psum, pmin);
-            if (pmin >= QP_CENTRAL_GAMMA * psum * inv_m) break;
-            alpha *= QP_CENTRAL_SHRINK;
+          } else {
+            for (int i = lane; i < mf; i += QP_THREADS) {
+              const double pr = (lf[i] + alpha * dlf[i]) * (wf[i] + alpha * dwf[i]);
+              psum += pr; pmin = fmin(pmin, pr);
+            }
           }
+          for (int p = lane; p < npc; p += QP_THREADS) {
+            const PairC c = PAIR_C(p);
+            const double2 l = ld2(lc + 2 * p), w = LD_WC(p), dl = LD_DLC(p), dw = ld2(dwc + 2 * p);
+            const double px = (l.x + alpha * dl.x) * (w.x + alpha * dw.x), py = (l.y + alpha * dl.y) * (w.y + alpha * dw.y);
+            if (c.actf != 0.0) { psum += px + py; pmin = fmin(pmin, fmin(px, py)); }      // (a switched-off pair keeps l = 0: not a product)
+          }
+          wave_reduce2<OpSum, OpMin>(psum, pmin);
+          if (pmin >= QP_CENTRAL_GAMMA * psum * inv_m) break;
+          alpha *= QP_CENTRAL_SHRINK;
         }
       }
       LSYNC();
@@ -1595,9 +1338,6 @@
     }
     for (int a = lane; a < nu; a += QP_THREADS) xu[a] += alpha * dxu[a];
     for (int t = lane; t < T && obs; t += QP_THREADS) xd[t] += alpha * dxd[t];
-    if constexpr (ASET) {                    // d is projected onto its bounds (a frozen d then never has to travel); the rows are re-seeded, not moved
-      for (int t = lane; t < T && obs; t += QP_THREADS) xd[t] = fmin(fmax(xd[t], dmin0), dmaxv);
-    } else {
     if constexpr (HPAIR) {
       for (int h = lane; h < mf / 2; h += QP_THREADS) {
         const double2 l = ld2(lf + 2 * h), w = LD_WF(h), dl = LD_DLF(h), dw = ld2(dwf + 2 * h);
@@ -1610,25 +1350,12 @@
       const double2 l = ld2(lc + 2 * p), w = LD_WC(p), dl = LD_DLC(p), dw = ld2(dwc + 2 * p);
       st2(lc + 2 * p, l.x + alpha * dl.x, l.y + alpha * dl.y); ST_ROW(Rwc, wc, p, w.x + alpha * dw.x, w.y + alpha * dw.y);
     }
-    }   // !ASET
     LSYNC();
     PROF(8);
   }
   LSYNC();
   it_total += it;
-  if constexpr (ASET) {
-    if (!aset_done) {                      // nothing was written: the interior-point launch behind this one solves the scene
-#ifndef NPA_QP_PROF
-      if (qp_info && lane == 0) {
-        double* qi = qp_info + (size_t)b * QP_INFO_STRIDE;
-        qi[5] = aset_guess; qi[6] = aset_left; qi[7] = status == 2 ? 6 : aset_why; qi[8] = aset_first;
-      }
-#endif
-      return;
-    }
-  }
   if (warm_now) warm_code = 1;
-  if (aset_done) warm_code = 6;          // the active-set iteration delivered this solve
   if (status == 0 && !(best_merit <= QP_RETRY_MERIT)) status = 4;      // both cold attempts ended short of convergence
 
   if (bw.dbg_x)
@@ -1681,18 +1408,16 @@
     // by its merit anyway (> 0.05), and the moderately far ones that get through save more iterations than the few that
     // are dropped at iteration 6 cost -- 7.7 vs 8.1 iterations per solve on configs[1], 7.4 vs 7.5 on the car.  So the
     // condition is gone, on purpose.)
-    if (flags && lane == 0) {
-      flags[b * 4 + 2] = (status == 0 && best_merit <= 1e-12) ? 1 : 0;
-      if constexpr (ASET) flags[b * 4 + 3] = 1;          // (the interior-point launch behind this one skips the scene)
-    }
+    if (flags && lane == 0) flags[b * 4 + 2] = (status == 0 && best_merit <= 1e-12) ? 1 : 0;
   }
   if (qp_info && lane == 0) {
     double* qi = qp_info + (size_t)b * QP_INFO_STRIDE;
     qi[0] = best_it; qi[1] = best_merit; qi[2] = last_mu; qi[3] = status; qi[4] = it;
     qi[14] = it_total; qi[15] = warm_code;
 #ifndef NPA_QP_PROF
-    if constexpr (ASET) { qi[5] = aset_guess; qi[6] = aset_left; qi[7] = aset_why; qi[8] = aset_first; }
-    else if (P.qp_aset && !(can_warm)) { qi[5] = 0; qi[6] = 0; qi[7] = 0; qi[8] = 0; }      // (no attempt was made on this scene)
+    // REMNANT of the retired active-set launch, kept because removing it changes the pinned machine code: P.qp_aset is always 0,
+    // so nothing is cleared.  It leaves with the next counter collection (DESIGN.md section 7).
+    if (P.qp_aset && !(can_warm)) { qi[5] = 0; qi[6] = 0; qi[7] = 0; qi[8] = 0; }
 #endif
 #ifdef NPA_QP_PROF
     PROF(9);

@@ -27,9 +27,6 @@
 #ifndef QP_CHOL_LOOK
 #define QP_CHOL_LOOK 3         // columns behind the pivot whose trailing update is broadcast with v_readlane (the rest: LDS, one pivot late)
 #endif
-#define QP_ASET_FIRST_MAX 0.05 // the attempt is not made from a warm point whose seeded merit is above this (most of those cycle: 85 % of the failures)
-#define QP_ASET_MAX_GUESS 2     // factorisations the active-set iteration may spend before the interior-point warm start takes over
-#define QP_ASET_TOL 1e-13      // what may be left of the scaled dual residual at a guess that repeated
 #define QP_RETRY_MERIT 1e-9    // a cold solve that ends above this is repeated once from round 2's start (unit multipliers)
 #define QP_SIGMA_MU_MIN 1e-15  // floor of the centring target: a gap driven to 1e-20 leaves the Newton matrix too ill
                                //   conditioned for the residuals to follow (solves that ended at 1e-11: 8 -> 1 of 640)
@@ -369,7 +366,9 @@ __device__ __forceinline__ PairC qp_pair(int p, int T, int npu, double sb0, doub
 
 // SCANW: the scan forms of the Phi products and the P_t blocks also for horizons of 17..32 steps (two DPP rows); the
 // launcher's default at T = 20 (acker: 69 k -> 79 k plans/s; the parity verdicts of tests/test_gpu_parity.py are the
-// same with and without them).  NPA_QP_NOSCAN_WIDE=1 selects the dense-product instantiation for A/B measurements.
+// same with and without them).  A fixed horizon above 16 must set it, and ASET_T must be false: the dense-product T = 20
+// instantiation and the active-set launch are retired (the body asserts both), the two parameters stay because
+// the counter records of profiles/ name the kernels by their full argument lists.
 template <int TT, int MM, bool BWD = false, bool SCANW = false, int WV = NPA_QP_WAVES, bool ASET_T = false>
 // (two waves per SIMD: <= 256 registers.  tests/test_abi.py reads the counts of the built code object and fails on any
 // spill or scratch use)

@@ -46,7 +46,8 @@ struct DevParams {
   // bounding box (the key pass of select_geo_kernel ranks on the distance to it, pan_common.h WP_TABH[4])
   int geo_rect;
   float rcx, rcy, rhx, rhy;
-  int qp_aset;                // (experiments build only: the QP's warm solves try the active-set iteration first, NPA_QP_ASET)
+  int qp_aset;                // always 0: a layout placeholder of the retired active-set launch.  Removing it shifts geo_tab and the
+                              // kernarg offsets of the pinned selection kernels: it leaves with the next counter collection
   int geo_tab;                // the weight pack carries the correction table of the geometric key (WP_TAB) and its margins (WP_KTAB)
 };
 

@@ -242,6 +242,28 @@ def test_hot_kernels_have_no_spills_and_no_scratch():
         assert not any("aset" in n or "select_kernelILi4ELb1" in n for n in res), "experiment kernels in the product build"
         assert os.path.getsize(kr.LIB) < 2 * 1024 * 1024, os.path.getsize(kr.LIB)
 
+
+def test_product_qp_instantiations_are_the_ones_the_launchers_name():
+    """The QP kernels of the built library are exactly the eight that nrmp_qp.hip launches: <TT, MM, BWD, SCANW, WV, ASET_T> of
+    nrmp_qp_kernel for the generic, the T = 10 and the T = 20 problem, forward and gradient, and <TT, MM, SCANW> of the merged
+    launch.  ASET_T (the last argument: `Lb1E` in its position was the retired active-set launch) is false in every one, and
+    a fixed horizon of 20 steps exists with the wide scans only (SCANW; without them it was the retired stored-Phi form)."""
+    import re
+    sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import kernel_resources as kr
+    if not kr.tools_available():
+        pytest.skip("ROCm LLVM tools not installed")
+    names = list(kr.kernel_resources())
+    single = [re.fullmatch(r"_Z14nrmp_qp_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])ELi(\d+)ELb([01])EEv.*", n) for n in names if "nrmp_qp_kernel" in n]
+    assert all(single), [n for n in names if "nrmp_qp_kernel" in n]
+    assert not any(m.group(6) == "1" for m in single), "an active-set instantiation (ASET_T = true) in the built library"
+    got = sorted(tuple(int(g) for g in m.groups()) for m in single)
+    assert len({g[4] for g in got}) == 1                        # (WV: the build's waves-per-SIMD target, the same for all)
+    assert [g[:4] + g[5:] for g in got] == [(0, 0, 0, 0, 0), (0, 0, 1, 0, 0), (10, 10, 0, 0, 0), (10, 10, 1, 0, 0),
+                                            (20, 10, 0, 1, 0), (20, 10, 1, 1, 0)], got
+    group = [re.fullmatch(r"_Z20nrmp_qp_group_kernelILi(\d+)ELi(\d+)ELb([01])EEv.*", n) for n in names if "nrmp_qp_group_kernel" in n]
+    assert all(group) and sorted(tuple(int(g) for g in m.groups()) for m in group) == [(10, 10, 0), (20, 10, 1)], names
+
 def test_no_kernel_has_instructions_that_only_run_with_exec_zero():
     """The root cause of the register-starved-build hazard (rounds 2 - 4: corrupted loop scalars in spilled QP builds, the
     faulting two-waves-per-SIMD scene kernel), found in round 5 under rocgdb: hipcc 7.2's register allocator puts live-range

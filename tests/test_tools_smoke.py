@@ -22,6 +22,19 @@ def test_active_set_study_one_scene():
     assert max(r["lane"] for r in rows) <= 1e-12
 
 
+def test_isa_diff_of_the_built_library_against_itself_is_empty():
+    """tests/tools/isa_diff.py, the check behind a refactoring of device code: the built library against itself has no
+    kernel on one side only and no differing fingerprint, and it saw the whole library (90 kernels when this was written)."""
+    import pytest
+    import isa_diff
+    from neupan_amd import build
+    if not isa_diff.kr.tools_available():
+        pytest.skip("ROCm LLVM tools not installed")
+    lib = build.build(force=False, verbose=False)
+    n, lines = isa_diff.isa_diff(lib, lib)
+    assert lines == [] and n >= 80, (n, lines)
+
+
 def test_step_study_rules_one_scene():
     """tests/tools/qp_step_study.py on one scene: the shipped rules need fewer interior-point iterations than round 2's and
     leave no solve above 1e-9."""

@@ -42,8 +42,8 @@ def run(n_scenes=1):
                 ts.append(time.perf_counter() - t0)
             med.append(1e3 * np.median(ts[4:]))
         prof = pan.profile_read() if hasattr(pan, "profile_read") and n_scenes > 1 and False else None
-        print("%s host call -> synchronised, %d scene(s) one at a time: mean of the per-scene medians %.4f ms, median %.4f, min %.4f, max %.4f  (NPA_QP_ASET=%r FROM=%r)"
-              % (tag, n_scenes, np.mean(med), np.median(med), np.min(med), np.max(med), os.environ.get("NPA_QP_ASET"), os.environ.get("NPA_QP_ASET_FROM")), flush=True)
+        print("%s host call -> synchronised, %d scene(s) one at a time: mean of the per-scene medians %.4f ms, median %.4f, min %.4f, max %.4f"
+              % (tag, n_scenes, np.mean(med), np.median(med), np.min(med), np.max(med)), flush=True)
         del pan
 
 
