@@ -588,13 +588,76 @@ int npa_world_behave(int batch, int n_worlds, int c_stride, int s_stride, double
                      const double *state, const double *prev_state, double robot_radius, int seg_limit,
                      int n_dir, const double *dirs, int n_speed, double dt, void *stream);
 
+/* ---- way-point curves: the initial path between two poses (csrc/curves.h, csrc/curves.hip) ----------------------------
+ *
+ * The reference leaves the curve between two way-points to the third-party gctl package (curve_generator.generate_curve,
+ * neupan/blocks/initial_path.py:337-339), which is not part of it; gctl's sampling is therefore NOT what this is compared
+ * with.  This comment is the specification (tests/curves_ref.py restates it in numpy); it is taken from the literature: the
+ * Dubins words are the normalised closed forms of A. M. Shkel and V. Lumelsky, "Classification of the Dubins set", Robotics
+ * and Autonomous Systems 34 (2001) 179-202.  Reeds-Shepp curves (48 words, several gears) are not generated.
+ * One definition in float64, compiled for the host and for the device (csrc/curves.h); every arithmetic statement below is one
+ * rounded operation in the order written (no contraction), so two device kernels give the same bits and host and device
+ * differ only where libm and the device math library do.
+ *
+ * Inputs: style (NPA_CURVE_LINE, NPA_CURVE_DUBINS), start (x0, y0, th0), goal (x1, y1, th1), interval > 0 and, for Dubins,
+ *   the turning radius rho = min_radius > 0.  dx = x1 - x0, dy = y1 - y0, D = sqrt(dx dx + dy dy), psi = atan2(dy, dx).
+ * Rows: (x, y, theta, gear = +1).  With the curve's length L: L == 0 gives ONE row, the goal pose (x1, y1, th1).  Otherwise
+ *   n = max(ceil(L / interval - 1e-9), 1) (planner.line_curve's rule), rows i = 0 .. n-1 lie at arc length i L / n and row n is
+ *   the goal: n + 1 rows.  A curve of 2^30 steps or more, or one whose length is not finite, is no curve.
+ * Line: L = D; row i < n is (x0 + f dx, y0 + f dy) with f = i / n; theta of EVERY row, row n included, is psi (what the
+ *   reference's _ensure_consistent_angles, initial_path.py:476-497, makes of a segment); th0 and th1 are not used.
+ * Dubins: mod2pi(x) = x - 2 pi floor(x c), c = 0.15915494309189535 (1 / (2 pi)), moved into [0, 2 pi) by one addition or
+ *   subtraction of 2 pi when rounding left it outside.  d = D / rho, alpha = mod2pi(th0 - psi), beta = mod2pi(th1 - psi), sa = sin alpha, sb = sin beta,
+ *   ca = cos alpha, cb = cos beta, cab = ca cb + sa sb.  D == 0 with alpha == beta: L = 0.  Otherwise the six words, in this
+ *   order, each (t, p, q) in radii, each with a direction (ya, xa):
+ *     0 LSL  p2 = 2 + d d - 2 cab + 2 d (sa - sb)    (ya, xa) = (cb - ca, d + sa - sb)     t = mod2pi(u - alpha)     q = mod2pi(beta - u)
+ *     1 LSR  p2 = -2 + d d + 2 cab + 2 d (sa + sb)   (ya, xa) = (-ca - cb, d + sa + sb)    t = mod2pi(u - alpha)     q = mod2pi(-(beta - u))
+ *     2 RSL  p2 = -2 + d d + 2 cab - 2 d (sa + sb)   (ya, xa) = (ca + cb, d - sa - sb)     t = mod2pi(-(u - alpha))  q = mod2pi(beta - u)
+ *     3 RSR  p2 = 2 + d d - 2 cab + 2 d (sb - sa)    (ya, xa) = (ca - cb, d - sa + sb)     t = mod2pi(-(u - alpha))  q = mod2pi(-(beta - u))
+ *            p = sqrt(p2); infeasible when p2 < -1e-12, a p2 in [-1e-12, 0) counts as 0.  LSL, RSR: u = atan2(ya, xa).  LSR, RSL:
+ *            the paper's atan2(ya, xa) - atan2(yb, p), yb = -2 for LSR and +2 for RSL, as ONE atan2 of the quotient of the two
+ *            directions: u = atan2(ya p - xa yb, xa p + ya yb) (the same angle modulo 2 pi, which is all mod2pi keeps)
+ *     4 RLR  a = (6 - d d + 2 cab + 2 d (sa - sb)) / 8   (ya, xa) = (ca - cb, d - sa + sb)   u = atan2(ya, xa)
+ *            p = mod2pi(2 pi - acos a)   t = mod2pi(p / 2 - u + alpha)   q = mod2pi(-(beta - alpha) - t + p)
+ *     5 LRL  a = (6 - d d + 2 cab - 2 d (sa - sb)) / 8   (ya, xa) = (ca - cb, d + sa - sb)   u = atan2(ya, xa)
+ *            p = mod2pi(2 pi - acos a)   t = mod2pi(p / 2 - u - alpha)   q = mod2pi((beta - alpha) - t + p)
+ *            infeasible when a is outside [-1, 1] by more than 1e-12; inside that margin it is clamped
+ *   The word with the smallest t + p + q wins, ties to the lowest index; L = rho (t + p + q).
+ *   A segment of type k (L: +1, S: 0, R: -1) carries a pose (x, y, h) over the length l (in radii) to
+ *     k == 0: (x + rho (l cos h), y + rho (l sin h), h);   else with e = h + k l: (x + rho (k (sin e - sin h)), y - rho (k (cos e - cos h)), e).
+ *   The poses at the start of the three segments follow from the start pose by that rule with l = t, then l = p (the heading is
+ *   not wrapped).  Row i < n: s = (i (t + p + q)) / n; segment 0 when s < t, 1 when s < t + p, else 2; the row is that segment's
+ *   start pose carried over s, s - t or s - (t + p).  Row 0 is therefore the start pose, bit for bit; row n is (x1, y1, th1) as
+ *   given (its heading may differ from the heading the curve arrives with by a multiple of 2 pi).
+ *
+ * npa_curve_rows (HOST, no device): the number of rows, n + 1, or a negative error.
+ * npa_curve_generate (HOST, no device): rows_out [capacity][4] f64 and *n_rows; a curve that does not fit `capacity` is
+ *   NPA_E_ARG and nothing is written.
+ * npa_curve_batch (one launch, one wave per curve, no workspace, no atomics, nothing allocated): B curves of one style and
+ *   radius; start, goal [B][3] f64, interval [B] f64, rows_out [B][capacity][4] f64, n_rows [B] int32, mask [B] int32
+ *   (nullable), all DEVICE.  Every lane evaluates the same six words; lane l writes rows l, l + 64, ...  A curve that needs
+ *   more than `capacity` rows: n_rows[b] = -needed, its rows untouched.  Inputs outside the specification (interval not > 0,
+ *   a pose that is not finite, 2^30 steps or more): n_rows[b] = 0, its rows untouched.  mask[b] == 0: rows and n_rows[b] untouched.
+ * NPA_E_ARG (before anything touches a device): a null required pointer, style outside 0..1, Dubins with min_radius <= 0,
+ *   capacity < 1, batch < 1; the host calls also: interval not > 0, a pose that is not finite. */
+#define NPA_CURVE_LINE 0
+#define NPA_CURVE_DUBINS 1
+int npa_curve_rows(int style, const double *start, const double *goal, double interval, double min_radius);
+int npa_curve_generate(int style, const double *start, const double *goal, double interval, double min_radius,
+                       int capacity, double *rows_out, int32_t *n_rows);
+int npa_curve_batch(int batch, int style, const double *start, const double *goal, const double *interval,
+                    double min_radius, int capacity, const int32_t *mask, double *rows_out, int32_t *n_rows,
+                    void *stream);
+
 /* ---- the bookkeeping of a device-resident closed loop (csrc/cycle.hip) -----------------------------------------------
  *
- * What the host does between the kernels of a control cycle, as three calls: handle-free, stream-ordered, one thread per
- * robot, no workspace, no atomics, nothing allocated, no host synchronisation.  They only select and copy, so a cycle
+ * What the host does between the kernels of a control cycle, as three calls (and a fourth for fleets whose robots have goal
+ * queues): handle-free, stream-ordered, one thread per robot (npa_cycle_retask: one wave), no workspace, no atomics, nothing
+ * allocated, no host synchronisation.  The three only select and copy, so a cycle
  *     npa_cycle_progress -> npa_world_scan -> npa_scan_to_points -> npa_nominal_ref_states -> npa_forward_batch
- *     [-> npa_plan_clearance] -> npa_cycle_act -> npa_world_step -> npa_cycle_commit
- * on one stream over buffers that stay where they are gives the bits of the same cycle paced by the host.
+ *     [-> npa_plan_clearance] -> npa_cycle_act -> npa_world_step -> npa_cycle_commit [-> npa_cycle_retask]
+ * on one stream over buffers that stay where they are gives the bits of the same cycle paced by the host (the fourth computes a
+ * curve: the host-paced cycle takes its rows from npa_curve_batch, the same device function).
  *
  * The curve table holds ALL curves of all robots: path [rows][4] f64 rows (x, y, theta, gear), curve c owns rows
  * curve_off[c] .. curve_off[c] + curve_len[c] - 1, robot b owns the curves robot_first[b] .. robot_first[b + 1] - 1
@@ -625,8 +688,26 @@ int npa_world_behave(int batch, int n_worlds, int c_stride, int s_stride, double
  *   the logs (nullable): log_clearance [cycles][B] f64 row `cycle`, log_states [cycles + 1][B][3] f64 row `cycle + 1` (row 0
  *   is the caller's: the initial poses).
  *
+ * npa_cycle_retask (optional, one launch, one WAVE per robot) runs behind npa_cycle_commit and gives a robot that has arrived
+ *   its next goal -- the reference's reset() followed by update_initial_path_from_goal(state, goal) (neupan/neupan.py:288-294,
+ *   :314-318), without the host.  It needs a table in which robot b owns ONE curve (robot_first[b + 1] - robot_first[b] == 1)
+ *   whose region, the rows from curve_off[robot_first[b]] on, has room for row_capacity[b] rows ([B] int32; the regions must
+ *   not overlap: they are not checked).  goals [B][g_stride][3] f64 (x, y, theta), n_goals [B] int32 (<= g_stride), goal_index
+ *   [B] int32 (in / out; the caller zeroes it), interval [B] f64 (the spacing of the new curve: npa_nominal_ref_states'
+ *   argument), style and min_radius as for npa_curve_batch.
+ *   Robot b re-tasks when arrived[b] != 0, collided[b] == 0 and 0 <= goal_index[b] < n_goals[b].  Then the curve from state[b]
+ *   (the pose after the step) to goals[b][goal_index[b]] is generated by npa_curve_batch's device function (the same bits).  It
+ *   fits (1 <= rows <= row_capacity[b]): the rows are written into the region; curve_len of that curve = rows; cur_off[b] =
+ *   the region's start, cur_len[b] = rows; curve_index[b] = 0; point_index[b] = 0; arrived[b] = 0; cur_vel [B][2][receding]
+ *   f32: the robot's row <- 0 (reset()); goal_index[b] += 1; retask_status[b] = 1.  It does not fit, or its inputs are outside
+ *   the curve specification: retask_status[b] = 2 and nothing else of the robot is written -- it stays arrived and the goal
+ *   is not consumed.  A robot that does not re-task: retask_status[b] = 0, nothing else.  log_goal [cycles][B] int32
+ *   (nullable): row `cycle` receives goal_index after the call.  The planner's own state record (the stop criterion's state,
+ *   min_distance, the QP warm start) is not touched, as the reference does not touch it.
+ *
  * NPA_E_ARG (before anything touches a device): a null required pointer, batch < 1, cycle < 0, ind_range < 1, receding
- *   outside [1, NPA_MAX_T], kinematics outside 0..2. */
+ *   outside [1, NPA_MAX_T], kinematics outside 0..2; npa_cycle_retask also: style outside 0..1, Dubins with min_radius <= 0,
+ *   g_stride < 1. */
 int npa_cycle_progress(int batch, const double *state, const double *path, const int32_t *curve_off,
                        const int32_t *curve_len, const int32_t *robot_first, int loop, double close_threshold,
                        int ind_range, double arrive_threshold, int arrive_index_threshold, int32_t *curve_index,
@@ -639,6 +720,12 @@ int npa_cycle_act(int batch, int receding, int kinematics, int first_cycle, int 
                   float *log_controls, int32_t *log_n_points, void *stream);
 int npa_cycle_commit(int batch, int cycle, const double *state, const double *clearance, int32_t *collided,
                      double *log_states, double *log_clearance, void *stream);
+int npa_cycle_retask(int batch, int receding, int cycle, int style, double min_radius, const double *state,
+                     int32_t *arrived, const int32_t *collided, double *path, const int32_t *curve_off,
+                     int32_t *curve_len, const int32_t *robot_first, const int32_t *row_capacity, const double *goals,
+                     int g_stride, const int32_t *n_goals, int32_t *goal_index, const double *interval,
+                     int32_t *curve_index, int32_t *cur_off, int32_t *cur_len, int32_t *point_index, float *cur_vel,
+                     int32_t *retask_status, int32_t *log_goal, void *stream);
 
 /* ---- training the adjust parameters inside the resident loop (csrc/lon.hip) ------------------------------------------
  *

@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libneupan_amd.so")
 # section 7: the first form of the geometric selection, select_kernel<E, true>) and its knob, NPA_SELECT_V1.
 EXPERIMENTS = os.environ.get("NPA_EXPERIMENTS", "0") not in ("", "0")
 SOURCES = ["dune.hip", "nrmp_qp.hip", "frontend.hip", "dune_labels.hip", "c_api.hip", "create.hip", "pack_image.hip", "serve_group.hip",
-           "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip"]
+           "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip", "curves.hip"]
 # -ffp-contract=fast-honor-pragmas is hipcc's default for device code, stated here so that it is the BUILD's property, not the
 # compiler's: the bit-exact legs (A / B / C, fa against the reference's tensors) are written with __f*_rn intrinsics where the
 # reference rounds every operation, and with explicit fmaf where it does not

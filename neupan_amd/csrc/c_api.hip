@@ -701,6 +701,36 @@ extern "C" int npa_cycle_commit(int batch, int cycle, const double* state, const
   return NPA_OK;
 }
 
+extern "C" hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, double min_radius, const double* state,
+                                              int* arrived, const int* collided, double* path, const int* curve_off,
+                                              int* curve_len, const int* robot_first, const int* row_capacity,
+                                              const double* goals, int g_stride, const int* n_goals, int* goal_index,
+                                              const double* interval, int* curve_index, int* cur_off, int* cur_len,
+                                              int* point_index, float* cur_vel, int* status, int* log_goal, hipStream_t stream);
+
+extern "C" int npa_cycle_retask(int batch, int receding, int cycle, int style, double min_radius, const double* state,
+                                int32_t* arrived, const int32_t* collided, double* path, const int32_t* curve_off,
+                                int32_t* curve_len, const int32_t* robot_first, const int32_t* row_capacity, const double* goals,
+                                int g_stride, const int32_t* n_goals, int32_t* goal_index, const double* interval,
+                                int32_t* curve_index, int32_t* cur_off, int32_t* cur_len, int32_t* point_index, float* cur_vel,
+                                int32_t* retask_status, int32_t* log_goal, void* stream) {
+  const char* what = nullptr;
+  if (batch < 1 || cycle < 0 || !state || !arrived || !collided || !path || !curve_off || !curve_len || !robot_first ||
+      !row_capacity || !goals || !n_goals || !goal_index || !interval || !curve_index || !cur_off || !cur_len || !point_index ||
+      !cur_vel || !retask_status)
+    what = "npa_cycle_retask: bad argument";
+  else if (receding < 1 || receding > NPA_MAX_T) what = "npa_cycle_retask: receding outside [1,NPA_MAX_T]";
+  else if (style != NPA_CURVE_LINE && style != NPA_CURVE_DUBINS) what = "npa_cycle_retask: style outside 0..1";
+  else if (style == NPA_CURVE_DUBINS && (!(min_radius > 0.0) || !std::isfinite(min_radius)))
+    what = "npa_cycle_retask: dubins needs min_radius > 0";
+  else if (g_stride < 1) what = "npa_cycle_retask: g_stride < 1";
+  if (what) return fail(NPA_E_ARG, what);
+  HIP_TRY(npa_launch_cycle_retask(batch, receding, cycle, style, min_radius, state, arrived, collided, path, curve_off, curve_len,
+                                  robot_first, row_capacity, goals, g_stride, n_goals, goal_index, interval, curve_index, cur_off,
+                                  cur_len, point_index, cur_vel, retask_status, log_goal, (hipStream_t)stream));
+  return NPA_OK;
+}
+
 // ---- the packed input record (csrc/ingest.hip) ----
 static int ingest_args_ok(int batch, int receding, int n_stride) {
   return batch >= 1 && receding >= 1 && receding <= NPA_MAX_T && n_stride >= 1;

@@ -2,13 +2,16 @@
 //   cycle_switch_kernel  curve switching and the arrival latch behind progress_kernel   initial_path.py:247-315
 //   cycle_act_kernel     warm start, stop test, action, scripted override, freeze       neupan.py:137, :150-164
 //   cycle_commit_kernel  the collision latch and the cycle's log rows behind the plant step
-// One thread per robot, no workspace, no atomics; handle-free and stream-ordered like frontend.hip.  Every per-robot decision
+//   curve_wave_kernel    an arrived robot's next goal: a new curve into its region of the table       neupan.py:288-294, :314-318
+//                        (and, for npa_curve_batch, plain curves: csrc/curves.hip)
+// One thread per robot (curve_wave_kernel: one wave), no workspace, no atomics; handle-free and stream-ordered like frontend.hip.  Every per-robot decision
 // is a select and every loop bound is a launch argument: the kernels only choose and copy, so a loop built from them gives
 // the bits of the host-paced loop (FleetPlanner.forward + run_closed_loop) whose rules they restate.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/neupan_amd.h"
+#include "curves.h"
 
 namespace {
 
@@ -103,7 +106,101 @@ __global__ __launch_bounds__(CY_THREADS) void cycle_commit_kernel(
   }
 }
 
+// The arguments of curve_wave_kernel, by value as ONE kernel argument (a code object describes every kernel argument in its
+// metadata; 28 of them were 2 KB of the library).  retask == 0 (npa_curve_batch): B plain curves, start / goals [B][3], g_stride 1,
+// one capacity, rows [B][capacity][4], n_rows; the fields behind n_rows are not read.  retask != 0 (npa_cycle_retask): start is
+// the state, rows the curve table, n_rows the retask_status.
+struct CurveWaveArgs {                       // (what a wave reads first comes first: the registers of the rest load late)
+  int retask, batch, T, cycle, style, g_stride, capacity;
+  const int *mask, *collided, *n_goals, *robot_first, *curve_off, *row_capacity;
+  int *goal_index, *arrived, *log_goal;
+  double rho;
+  const double *start, *goals, *interval;
+  double* rows;
+  int *n_rows, *curve_len, *curve_index, *cur_off, *cur_len, *point_index;
+  float* cur_vel;
+};
+
+// One wave per curve, two callers: npa_curve_batch and npa_cycle_retask (the next goal of a robot that has arrived, into its
+// region of the curve table).  ONE kernel, because the curve is some 10 KB of inlined double-precision library code and the
+// product library has a size limit; `retask` is a launch argument, so the branch is the whole wave's.  Everything a re-task's
+// decision reads is loaded before anything is written, and a wave with nothing to do leaves at its first test.
+__global__ __launch_bounds__(npa_curve::kWave) void curve_wave_kernel(CurveWaveArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int gi = 0, off = 0, cap = a.capacity;
+  size_t row0 = (size_t)b * a.capacity;
+  // Lane l owns word l of what the wave writes behind the curve (WORDS below): its address is chosen here, in front of the curve,
+  // so that the nine array arguments are not held in scalar registers across it; the curve's own code needs those.
+  int* word = lane == 0 ? a.n_rows + b : nullptr;
+  float* vel = nullptr;
+  if (a.retask) {
+    gi = a.goal_index[b];
+    const bool go = a.arrived[b] != 0 && a.collided[b] == 0 && gi >= 0 && gi < a.n_goals[b];
+    int* lg = a.log_goal ? a.log_goal + (size_t)a.cycle * a.batch + b : nullptr;
+    if (!go) {
+      if (lane == 0) {
+        a.n_rows[b] = 0;
+        if (lg) *lg = gi;
+      }
+      return;
+    }
+    const int first = a.robot_first[b];
+    off = a.curve_off[first];
+    cap = a.row_capacity[b];
+    row0 = (size_t)off;
+    word = lane == 1 ? lg : word;                         // WORDS: 0 retask_status, 1 the log row, 2 goal_index, 3 arrived,
+    word = lane == 2 ? a.goal_index + b : word;           // 4 point_index, 5 curve_index, 6 cur_off, 7 cur_len, 8 curve_len
+    word = lane == 3 ? a.arrived + b : word;
+    word = lane == 4 ? a.point_index + b : word;
+    word = lane == 5 ? a.curve_index + b : word;
+    word = lane == 6 ? a.cur_off + b : word;
+    word = lane == 7 ? a.cur_len + b : word;
+    word = lane == 8 ? a.curve_len + first : word;
+    vel = lane < 2 * a.T ? a.cur_vel + (size_t)b * 2 * a.T + lane : nullptr;
+  } else if (a.mask && a.mask[b] == 0) {
+    return;
+  }
+  const int needed = npa_curve::curve_wave(a.style, a.start + (size_t)b * 3, a.goals + ((size_t)b * a.g_stride + gi) * 3,
+                                           a.interval[b], a.rho, cap, a.rows + row0 * 4, lane);
+  if (!word && !vel) return;
+  if (!a.retask) {
+    *word = needed > cap ? -needed : needed;              // (lane 0)
+    return;
+  }
+  const bool fits = needed >= 1 && needed <= cap;
+  if (!fits) {                                            // the robot stays arrived, the goal is not consumed
+    if (word && lane < 2) *word = lane == 0 ? 2 : gi;
+    return;
+  }
+  if (vel) *vel = 0.f;                                    // reset(): neupan.py:288-294
+  const int value = lane == 0 ? 1 : (lane <= 2 ? gi + 1 : (lane <= 5 ? 0 : (lane == 6 ? off : needed)));
+  if (word) *word = value;
+}
+
 }  // namespace
+
+extern "C" hipError_t npa_launch_curve_batch(int batch, int style, const double* start, const double* goal, const double* interval,
+                                             double min_radius, int capacity, const int* mask, double* rows_out, int* n_rows,
+                                             hipStream_t stream) {
+  CurveWaveArgs a = {};
+  a.batch = batch; a.T = 1; a.style = style; a.g_stride = 1; a.capacity = capacity; a.rho = min_radius;
+  a.start = start; a.goals = goal; a.interval = interval; a.mask = mask; a.rows = rows_out; a.n_rows = n_rows;
+  hipLaunchKernelGGL(curve_wave_kernel, dim3(batch), dim3(npa_curve::kWave), 0, stream, a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, double min_radius, const double* state,
+                                              int* arrived, const int* collided, double* path, const int* curve_off,
+                                              int* curve_len, const int* robot_first, const int* row_capacity,
+                                              const double* goals, int g_stride, const int* n_goals, int* goal_index,
+                                              const double* interval, int* curve_index, int* cur_off, int* cur_len,
+                                              int* point_index, float* cur_vel, int* status, int* log_goal, hipStream_t stream) {
+  const CurveWaveArgs a = {1, batch, T, cycle, style, g_stride, 0, nullptr, collided, n_goals, robot_first, curve_off, row_capacity,
+                           goal_index, arrived, log_goal, min_radius, state, goals, interval, path, status, curve_len, curve_index,
+                           cur_off, cur_len, point_index, cur_vel};
+  hipLaunchKernelGGL(curve_wave_kernel, dim3(batch), dim3(npa_curve::kWave), 0, stream, a);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t npa_launch_cycle_switch(int batch, int loop, const double* state, const int* curve_arrived,
                                               const int* curve_off, const int* curve_len, const int* robot_first,

@@ -72,6 +72,24 @@ class FleetPlanner:
         self.cur_vel = None                          # zeros on the first cycle (neupan.py:73)
         self.arrived = np.zeros(self.B, dtype=bool)
 
+    def retask(self, b, path):
+        """Robot b's next mission: `path` (rows [P, 4] of x, y, theta, gear, or a list of (4,1) points; ONE curve, no gear split)
+        replaces its curve list, it starts at the path's first point, its arrival latch is cleared and its warm start is zeroed
+        -- the reference's reset() + set of a new initial path (neupan.py:288-303) for one robot of the fleet.  Nothing changes
+        for the other robots (their progress along their curves is kept); the robot's interval is kept too."""
+        curve = np.ascontiguousarray(np.asarray(path, dtype=np.float64).reshape(-1, 4))
+        if curve.shape[0] < 1:
+            raise ValueError("FleetPlanner.retask: an empty path")
+        pidx = self.nb._pidx.cpu().numpy().copy()
+        self.curve_lists[b] = [curve]
+        self.curve_index[b] = 0
+        pidx[b] = 0
+        self._upload(pidx)
+        self.arrived[b] = False
+        if self.cur_vel is not None:
+            self.cur_vel = self.cur_vel.clone()          # (it may be the planner's own output tensor)
+            self.cur_vel[b] = 0
+
     def set_adjust(self, theta):
         """Per-robot adjust parameters: `theta` (B, 7) or (B, 8) float32 on the device, row b = q_s[0..2], p_u, eta, d_max, d_min
         of robot b (a robot in a corridor and one in open space want different d_max and eta) -- PAN.set_scene_adjust; None

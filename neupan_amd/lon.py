@@ -267,7 +267,9 @@ class LonLoop(ResidentLoop):
     in place (`theta`).  train: the columns that are stepped; lr, betas, eps: torch.optim.Adam's; loss_weight, loss_offset,
     stuck_threshold, stuck_patience: the example's 10, 50, 0.01, 5; accumulate: gradients add up over an episode, as they do in
     the example, which clears them once per episode (False: every cycle steps on its own gradient); bounds: {name: (lo, hi)}
-    clamps a column after every step.  The remaining arguments are ResidentLoop's.
+    clamps a column after every step.  The remaining arguments are ResidentLoop's, except its goal queues (goals,
+    path_capacity, curve_style, min_radius): a training episode ends when its robot arrives, by definition, so there is no
+    next goal to give it.
     `t`, the step count of the bias correction, counts cycles since construction and is not reset, as an optimiser object's.
     Attributes besides ResidentLoop's (device tensors, the same objects for the life of the loop): theta, m, v, gacc [B, 8] f32,
     loss [B] f32, active, ended, stuck_count, skipped (steps refused for a non-finite gradient), bad (re-solves whose status

@@ -624,8 +624,49 @@ class _HostCycle:
         return dict(self.logs, arrive=self.arrive, collided=self.collided)
 
 
+class _HostRetask:
+    """The host-paced twin of npa_cycle_retask, behind `_HostCycle.cycle`: it reads the arrival and collision flags, takes the
+    new rows from npa_curve_batch -- the DEVICE generator: libm and the device math library differ in the last bits, and only
+    the same code gives the two loops the same bits -- and hands them to `fleet.retask`.  Attributes as ResidentLoop's:
+    goal_index, retask_status [B] (host int32), log [cycles, B] int32 (device)."""
+
+    def __init__(self, fleet, device, cycles, goals, path_capacity, curve_style, min_radius):
+        q = _goal_queues(goals, fleet, path_capacity, curve_style, min_radius)
+        B = fleet.B
+        self.fleet, self.q, self.B = fleet, q, B
+        self.goals = torch.from_numpy(q["goals"]).to(device)
+        self.interval = torch.from_numpy(_bcast(fleet.intervals, B)).to(device)
+        self.goal_index, self.retask_status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        self.log = torch.zeros((cycles, B), dtype=torch.int32, device=device)
+        self.rows = torch.zeros((B, int(q["capacity"].max()), 4), dtype=torch.float64, device=device)
+        self.n_rows = torch.zeros((B,), dtype=torch.int32, device=device)
+
+    def step(self, loop, cyc):
+        from .curves import generate_batch
+        fleet, q, gi = self.fleet, self.q, self.goal_index
+        go = fleet.arrived & ~loop.collided.cpu().numpy() & (gi < q["n_goals"])
+        self.retask_status[:] = 0
+        if go.any():
+            pick = torch.from_numpy(np.minimum(gi, q["goals"].shape[1] - 1).astype(np.int64)).to(self.goals.device)
+            goal = self.goals[torch.arange(self.B, device=pick.device), pick]
+            rows, n_rows = generate_batch(q["style"], loop.st, goal, self.interval, q["min_radius"], capacity=self.rows.shape[1],
+                                          mask=go.astype(np.int32), out=self.rows, n_rows=self.n_rows)
+            n_h = n_rows.cpu().numpy()
+            loop.arrive = loop.arrive.clone()
+            for b in np.nonzero(go)[0]:
+                n = int(n_h[b])
+                if 1 <= n <= q["capacity"][b]:
+                    fleet.retask(b, rows[b, :n].cpu().numpy())
+                    gi[b] += 1
+                    self.retask_status[b] = 1
+                    loop.arrive[b] = False
+                else:
+                    self.retask_status[b] = 2
+        self.log[cyc] = torch.from_numpy(gi.copy()).to(self.log.device)
+
+
 def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=False, certify=False, peers=False,
-                    max_points=None, actions=None):
+                    max_points=None, actions=None, goals=None, path_capacity=None, curve_style="line", min_radius=None):
     """example/run_exp.py's loop for the B robots of `fleet` (a FleetPlanner whose paths are set) in `world`:
 
         scan (LidarWorld.scan) -> scan_to_point[_velocity]_batch -> fleet.forward -> LidarWorld.step
@@ -641,23 +682,60 @@ def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=Fa
     Returns dict(states [cycles+1, B, 3] f64, actions [cycles, B, 2] f32, arrive [B] bool, stop [cycles, B] bool,
     collided [B] bool, clearance [cycles, B] f64 (the world clearance after each step), controls [cycles, B, 2, T] f32 (the
     plans' opt_u), n_points [cycles, B] int32 (the clouds' sizes); with certify, plan_clearance [B, T+1] of the last cycle),
-    device tensors."""
+    device tensors.
+    `goals` (one list of (x, y, theta) per robot; with path_capacity, curve_style, min_radius as ResidentLoop takes them): a
+    robot that has arrived and has not collided is given the curve from its pose to its next goal at the end of the cycle
+    (`_HostRetask`: the reference's reset() + update_initial_path_from_goal); the result then also has goal [cycles, B] int32
+    (the number of goals consumed after each cycle), goal_index and retask_status [B] int32."""
     loop = _HostCycle(fleet, world, states, cycles, scan, point_velocities, peers, max_points)
+    tasks = None if goals is None else _HostRetask(fleet, world.device, cycles, goals, path_capacity, curve_style, min_radius)
     override = None if actions is None else torch.as_tensor(actions).to(device=world.device, dtype=torch.float32)
     for cyc in range(cycles):
         info, _, _ = loop.cycle(cyc, None if override is None else override[cyc], certify)
+        if tasks is not None:
+            tasks.step(loop, cyc)
     out = loop.result()
+    if tasks is not None:
+        out.update(goal=tasks.log, goal_index=torch.from_numpy(tasks.goal_index).to(world.device),
+                   retask_status=torch.from_numpy(tasks.retask_status).to(world.device))
     if certify and cycles > 0:
         out["plan_clearance"] = info["clearance"]
     return out
 
 
-def curve_table(curve_lists):
+def _goal_queues(goals, fleet, path_capacity, curve_style, min_radius):
+    """The goal queues of a loop as npa_cycle_retask takes them.  goals: one list of (x, y, theta) per robot (an empty list: the
+    robot keeps its one mission).  Returns dict(goals [B, g_stride, 3] f64, n_goals [B] int32, capacity [B] int32 -- robot b's
+    region of the curve table: max(the rows of its initial path, path_capacity) --, style, min_radius)."""
+    from .curves import STYLES, style_code
+    B = fleet.B
+    if len(goals) != B:
+        raise ValueError(f"goals: {len(goals)} queues for {B} robots")
+    for b, curves in enumerate(fleet.curve_lists):
+        if len(curves) != 1:          # (a re-tasked path is one curve, and robot_first[b + 1] is also where the neighbour's curves start)
+            raise ValueError(f"goals: robot {b}'s initial path has {len(curves)} curves (a gear change); a robot that is given "
+                             "goals must start on a single curve")
+    style = style_code(curve_style)
+    rho = float(min_radius or 0.0)
+    if style == STYLES["dubins"] and not rho > 0.0:
+        raise ValueError("goals: curve_style 'dubins' needs min_radius > 0")
+    stride = max(1, max(len(q) for q in goals))
+    table = np.zeros((B, stride, 3), dtype=np.float64)
+    for b, q in enumerate(goals):
+        if len(q):
+            table[b, :len(q)] = np.asarray(q, dtype=np.float64).reshape(len(q), -1)[:, :3]
+    cap = np.array([max(c[0].shape[0], int(path_capacity or 0)) for c in fleet.curve_lists], dtype=np.int32)
+    return dict(goals=table, n_goals=np.array([len(q) for q in goals], dtype=np.int32), capacity=cap, style=style, min_radius=rho)
+
+
+def curve_table(curve_lists, capacity=None):
     """All curves of all robots as one table: `curve_lists[b]` = robot b's curves in driving order, arrays [P, 4] of rows
     x, y, theta, gear (FleetPlanner.curve_lists: what `_split_by_gear` makes of a path).  Returns numpy arrays (path [rows, 4]
     float64: the curves back to back; curve_off [C] and curve_len [C] int32: curve c owns rows curve_off[c] .. curve_off[c] +
     curve_len[c] - 1; robot_first [B + 1] int32: robot b owns curves robot_first[b] .. robot_first[b + 1] - 1) -- the layout
-    npa_cycle_progress reads (include/neupan_amd.h)."""
+    npa_cycle_progress reads (include/neupan_amd.h).  capacity [B] (optional, robots of ONE curve each): robot b's curve owns a
+    region of capacity[b] >= its rows in the table, the rows behind the curve zeros -- the room npa_cycle_retask writes a new
+    curve into."""
     rows, off, ln, first = [], [], [], [0]
     o = 0
     for b, curves in enumerate(curve_lists):
@@ -668,6 +746,11 @@ def curve_table(curve_lists):
             if a.shape[0] < 1:
                 raise ValueError(f"robot {b} has an empty curve")
             rows.append(a); off.append(o); ln.append(a.shape[0]); o += a.shape[0]
+            if capacity is not None:
+                pad = int(capacity[b]) - a.shape[0]
+                if len(curves) != 1 or pad < 0:
+                    raise ValueError(f"robot {b}: a region of {int(capacity[b])} rows for {len(curves)} curves, the first of {a.shape[0]}")
+                rows.append(np.zeros((pad, 4), dtype=np.float64)); o += pad
         first.append(len(off))
     if not rows:
         raise ValueError("no robots")
@@ -684,9 +767,16 @@ class ResidentLoop:
         -> npa_forward_batch_flags [-> npa_plan_clearance]                                                    (_plan_step)
         -> npa_cycle_act (warm start, stop, action, override, freeze)
         [-> npa_world_behave, when the world has agents] -> npa_world_step -> npa_cycle_commit (collision latch, log rows)
-                                                                                                              (_tail_step)
+        [-> npa_cycle_retask, when the loop has goals]                                                        (_tail_step)
     followed by the host's bookkeeping (_finish_step: the planner's last call, `cycles_done`, the audit every 64 cycles).  This is
     the one definition of the resident cycle: `lon.LonLoop` replaces the plan step and adds its own steps around these.
+
+    With `goals` (one list of (x, y, theta) per robot) one more launch ends the tail step: npa_cycle_retask gives a robot that has
+    arrived and has not collided the curve from its pose to its next goal (curve_style 'line' or 'dubins', the latter with
+    min_radius; neupan_amd.curves), written into the robot's own region of the curve table: max(the rows of its initial path,
+    path_capacity) rows.  A curve that does not fit leaves the robot arrived (retask_status 2).  Every robot's initial path must
+    then be a single curve.  Without goals the table and the launches are what they were; attributes goal_index, retask_status
+    [B] int32 (None without goals), and `run` adds logs["goal"] [cycles, B] int32: the goals consumed after each cycle.
 
     The arguments are `run_closed_loop`'s.  `fleet` must be fresh from `set_paths` (its host bookkeeping -- curve_index, arrived,
     cur_vel -- is not used again: this object owns the device copy, and `fleet.forward` must not be mixed in until the next
@@ -703,7 +793,8 @@ class ResidentLoop:
     [B, 2] f32, stop [B] uint8, frozen / arrived / collided [B] int32, clearance [B] f64, points, point_velocities, n_points,
     out (the plan's dict as PAN.forward_batch returns it), plan_clearance (with certify: PAN.plan_clearance's dict)."""
 
-    def __init__(self, fleet, world, states, scan=None, point_velocities=False, certify=False, peers=False, max_points=None):
+    def __init__(self, fleet, world, states, scan=None, point_velocities=False, certify=False, peers=False, max_points=None,
+                 goals=None, path_capacity=None, curve_style="line", min_radius=None):
         if getattr(fleet, "B", 0) < 1:
             raise ValueError("ResidentLoop: the fleet has no paths (set_paths first)")
         if fleet.cur_vel is not None:
@@ -742,7 +833,8 @@ class ResidentLoop:
         zeros = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
         empty = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
         # ---- the curve table and the per-robot path state
-        path, off, ln, first = curve_table(fleet.curve_lists)
+        self._goals = None if goals is None else _goal_queues(goals, fleet, path_capacity, curve_style, min_radius)
+        path, off, ln, first = curve_table(fleet.curve_lists, None if goals is None else self._goals["capacity"])
         self._table = (torch.from_numpy(path).to(dev), i32(off), i32(ln), i32(first))
         self.curve_index = zeros((B,), torch.int32)
         self.cur_off, self.cur_len = i32(off[first[:-1]]), i32(ln[first[:-1]])
@@ -829,6 +921,17 @@ class ResidentLoop:
                       _ptr(self.frozen), float(fleet.dt), KIN[kin], float(L), world.bounds, len(V),
                       V.ctypes.data_as(C.POINTER(C.c_double)), world.peer_base if peers else -1, _ptr(self.clearance))
         self._commit = (_ptr(st), _ptr(self.clearance), _ptr(self.collided))
+        # ---- the next goal of a robot that has arrived, behind the commit (without goals: no launch, no buffer)
+        self._retask, self._log_goal, self.goal_index, self.retask_status = None, None, None, None
+        if goals is not None:
+            q = self._goals
+            self.goal_index, self.retask_status = zeros((B,), torch.int32), zeros((B,), torch.int32)
+            held = (torch.from_numpy(q["goals"]).to(dev), i32(q["n_goals"]), i32(q["capacity"]))
+            self._retask = (q["style"], q["min_radius"], _ptr(st), _ptr(self.arrived), _ptr(self.collided), _ptr(path_d), _ptr(off_d),
+                            _ptr(len_d), _ptr(first_d), _ptr(held[2]), _ptr(held[0]), q["goals"].shape[1], _ptr(held[1]),
+                            _ptr(self.goal_index), _ptr(itv), _ptr(self.curve_index), _ptr(self.cur_off), _ptr(self.cur_len),
+                            _ptr(self.point_index), _ptr(self.cur_vel), _ptr(self.retask_status))
+            self._held = self._held + held
         # ---- the agents' choice, between act and step (a world without agents: no launch, no buffer)
         self._behave, self.prev_states = None, None
         if world.has_agents:
@@ -885,6 +988,11 @@ class ResidentLoop:
         rc = lib.npa_cycle_commit(self.B, row, *self._commit, lh, lr, stream)
         if rc:
             check(rc, "npa_cycle_commit")
+        if self._retask is not None:                     # (the goal log is a run's: `run` sets its address, `cycle` has none)
+            style, rho = self._retask[:2]
+            rc = lib.npa_cycle_retask(self.B, self.T, row, style, rho, *self._retask[2:], self._log_goal, stream)
+            if rc:
+                check(rc, "npa_cycle_retask")
 
     def _finish_step(self):
         """the host's bookkeeping behind a cycle: what the planner reports as its last call, the counters, the audit"""
@@ -941,7 +1049,10 @@ class ResidentLoop:
         return logs, override.unbind(0)
 
     def _result(self, logs):
-        return dict(logs, arrive=self.arrived != 0, collided=self.collided != 0)
+        out = dict(logs, arrive=self.arrived != 0, collided=self.collided != 0)
+        if self._retask is not None:
+            out.update(goal_index=self.goal_index, retask_status=self.retask_status)
+        return out
 
     def run(self, cycles, actions=None):
         """`cycles` cycles; returns the dict run_closed_loop returns (same keys, shapes and dtypes; states[0] = the poses at the
@@ -949,8 +1060,14 @@ class ResidentLoop:
         cycles = int(cycles)
         logs, rows = self._open_run(cycles, actions)
         ptrs = tuple(_ptr(logs[k]) for k in _LOG_ORDER) if cycles > 0 else None
-        for i in range(cycles):
-            self._on_device(rows[i], ptrs, i)
+        if self._retask is not None:
+            logs["goal"] = torch.zeros((cycles, self.B), dtype=torch.int32, device=self.device)
+            self._log_goal = _ptr(logs["goal"]) if cycles > 0 else None
+        try:
+            for i in range(cycles):
+                self._on_device(rows[i], ptrs, i)
+        finally:
+            self._log_goal = None
         self._override = rows                        # (held: the last launches may still read them)
         out = self._result(logs)
         if self.certify and cycles > 0:
