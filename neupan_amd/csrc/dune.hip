@@ -181,7 +181,7 @@ extern "C" hipError_t npa_launch_select_geo(const DevParams& P, const float* wpa
   if (n_use_max < 1) n_use_max = 1;
   const size_t n_pad = ((size_t)n_use_max + SEL2_TRIP - 1) / SEL2_TRIP * SEL2_TRIP;
   const size_t key_area = std::max<size_t>(n_pad * sizeof(unsigned), SEL_CAP * (NPA_MAX_E + 5 + 2) * sizeof(float));
-  const size_t shmem = (11 * 32 + 8 * 32 + 8 + NPA_GEO_BANDS) * sizeof(float) + (2 * SEL_CAP + NPA_MAX_M) * sizeof(int) +
+  const size_t shmem = (11 * 32 + 8 * 32 + 8 + NPA_GEO_BANDS + SEL_LDS_FRAME) * sizeof(float) + (2 * SEL_CAP + NPA_MAX_M) * sizeof(int) +
                        (key_area + 15) / 16 * 16;
   const int blocks = (batch + 7) / 8 * 8 * nsl;
 #define LAUNCHG(EE, BB, KK)                                                                                         \
@@ -237,7 +237,7 @@ extern "C" hipError_t npa_launch_select_geo_group(const DevParams& P, const SelG
   if (n_use_max < 1) n_use_max = 1;
   const size_t n_pad = ((size_t)n_use_max + SEL2_TRIP - 1) / SEL2_TRIP * SEL2_TRIP;
   const size_t key_area = std::max<size_t>(n_pad * sizeof(unsigned), SEL_CAP * (NPA_MAX_E + 5 + 2) * sizeof(float));
-  const size_t shmem = (11 * 32 + 8 * 32 + 8 + NPA_GEO_BANDS) * sizeof(float) + (2 * SEL_CAP + NPA_MAX_M) * sizeof(int) +
+  const size_t shmem = (11 * 32 + 8 * 32 + 8 + NPA_GEO_BANDS + SEL_LDS_FRAME) * sizeof(float) + (2 * SEL_CAP + NPA_MAX_M) * sizeof(int) +
                        (key_area + 15) / 16 * 16;
   const int blocks = (batch + 7) / 8 * 8 * nsl;
 #define LAUNCHG(EE, BB, KK)                                                                                         \

@@ -117,6 +117,16 @@ __device__ __forceinline__ void ln_tanh(f32x16 acc, const float* g, const float*
   }
 }
 
+// max / min / ReLU WITHOUT the canonicalising v_max_f32 x, x, x that fmaxf / fminf get in front of them whenever the compiler cannot
+// prove an operand quiet (an MFMA accumulator, a DPP or lane read, a load): the median of (a, b, +inf) IS max(a, b), one
+// v_med3_f32, and takes its operands as they are.  With one NaN operand v_med3_f32 returns min3, the other operand: what fmaxf
+// returns.  The sites (select_geo_body.inc, the exact encoder's ReLU) and what a NaN does at each: DESIGN.md section 3.1.
+// (the +inf sits in a register behind an empty asm: as a literal the compiler folds the median back into fmaxf, canonicalisation and all)
+__device__ __forceinline__ float inf_reg() { float v = __builtin_inff(); asm("" : "+v"(v)); return v; }
+__device__ __forceinline__ float max_nc(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, inf_reg()); }
+__device__ __forceinline__ float min_nc(float a, float b) { return -__builtin_amdgcn_fmed3f(-a, -b, inf_reg()); }
+__device__ __forceinline__ float relu_acc(float x) { return max_nc(x, 0.f); }
+
 __device__ __forceinline__ f32x16 layer32(const float (&w)[16], const float (&a)[16], f32x16 acc) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[r], a[r], acc, 0, 0, 0);
@@ -355,7 +365,7 @@ __device__ __forceinline__ void encode_tile_stream(float w1, const float* __rest
   {
     f32x16 acc = layer32(wa, a, bias_init<PERM>(vec + V_B2 * 32, hf));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = fmaxf(acc[r], 0.f);
+    for (int r = 0; r < 16; ++r) a[r] = relu_acc(acc[r]);
   }
   __builtin_amdgcn_sched_barrier(0);
   load_layer(wls, 2, lane, wa);
@@ -370,7 +380,7 @@ __device__ __forceinline__ void encode_tile_stream(float w1, const float* __rest
   {
     f32x16 acc = layer32(wa, a, bias_init<PERM>(vec + V_B4 * 32, hf));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = fmaxf(acc[r], 0.f);
+    for (int r = 0; r < 16; ++r) a[r] = relu_acc(acc[r]);
   }
   __builtin_amdgcn_sched_barrier(0);
   {
@@ -455,7 +465,7 @@ __device__ __forceinline__ void encode_tile16_stream(float w1a, float w1b, const
     f32x4 c0 = ld4(vq + V_B2 * 32), c1 = ld4(vq + V_B2 * 32 + 4);
     layer16(wa, a, c0, c1);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { a[r] = fmaxf(c0[r], 0.f); a[4 + r] = fmaxf(c1[r], 0.f); }
+    for (int r = 0; r < 4; ++r) { a[r] = relu_acc(c0[r]); a[4 + r] = relu_acc(c1[r]); }
   }
   __builtin_amdgcn_sched_barrier(0);
   load_layer(wls16, 2, lane, wa);
@@ -472,7 +482,7 @@ __device__ __forceinline__ void encode_tile16_stream(float w1a, float w1b, const
     f32x4 c0 = ld4(vq + V_B4 * 32), c1 = ld4(vq + V_B4 * 32 + 4);
     layer16(wa, a, c0, c1);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { a[r] = fmaxf(c0[r], 0.f); a[4 + r] = fmaxf(c1[r], 0.f); }
+    for (int r = 0; r < 4; ++r) { a[r] = relu_acc(c0[r]); a[4 + r] = relu_acc(c1[r]); }
   }
   __builtin_amdgcn_sched_barrier(0);
   {
@@ -527,7 +537,7 @@ __device__ __forceinline__ void encode_tile_bf16(float w1, const float* __restri
   {
     f32x16 acc = layer32_bf16(wb, 0, lane, a, bias_init(vec + V_B2 * 32, hf));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = fmaxf(acc[r], 0.f);
+    for (int r = 0; r < 16; ++r) a[r] = relu_acc(acc[r]);
   }
   {
     f32x16 acc = layer32_bf16(wb, 1, lane, a, bias_init(vec + V_B3 * 32, hf));
@@ -536,7 +546,7 @@ __device__ __forceinline__ void encode_tile_bf16(float w1, const float* __restri
   {
     f32x16 acc = layer32_bf16(wb, 2, lane, a, bias_init(vec + V_B4 * 32, hf));
 #pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = fmaxf(acc[r], 0.f);
+    for (int r = 0; r < 16; ++r) a[r] = relu_acc(acc[r]);
   }
   {
     f32x16 acc = layer32_bf16(wb, 3, lane, a, bias_init(vec + V_B5 * 32, hf));
@@ -595,9 +605,12 @@ __device__ __forceinline__ int src_index(int n, int n_raw, int n_use) {
 }
 
 // frame of a slice: robot pose at horizon step t, (-R)G^T
-template <int E>
+// RG_LDS (select_geo_body.inc): the frame's image in LDS, frg[6][NPA_MAX_E] = (-R) G^T (2 rows), G^T (2 rows), h, then c, s, tx, ty,
+// tstep -- what the stage loop's point flow and row epilogue read, instead of 5 E + 5 scalars held from here to the emit
+// (F.rg is left unset; the caller's wave barrier in front of the first read orders the store)
+template <int E, bool RG_LDS = false>
 __device__ __forceinline__ void load_frame(const DevParams& P, const float* __restrict__ cur_s,
-                                           const float* __restrict__ trig, int b, int t, SliceFrame& F) {
+                                           const float* __restrict__ trig, int b, int t, SliceFrame& F, float* frg = nullptr) {
   // cos / sin come from the table written together with cur_s (stage_kernel, the QP's write-out, trig_kernel): the
   // fp64 libm evaluation costs ~250 slow VALU instructions, which a wave of dune_kernel would otherwise pay for
   // every work ticket (nearly every ticket of a wave lands in a new slice)
@@ -615,9 +628,22 @@ __device__ __forceinline__ void load_frame(const DevParams& P, const float* __re
   }
   // the frame is wave-uniform: park it in SGPRs, the VGPR budget (128) is tight
   auto uni = [](float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
-  F.c = uni(F.c); F.s = uni(F.s); F.tx = uni(F.tx); F.ty = uni(F.ty); F.tstep = uni(F.tstep);
+  if constexpr (RG_LDS) {
+    if (threadIdx.x == 0) {
 #pragma unroll
-  for (int e = 0; e < E; ++e) { F.rg[0][e] = uni(F.rg[0][e]); F.rg[1][e] = uni(F.rg[1][e]); }
+      for (int e = 0; e < E; ++e) {
+        frg[e] = F.rg[0][e]; frg[NPA_MAX_E + e] = F.rg[1][e];
+        frg[2 * NPA_MAX_E + e] = P.G[e][0]; frg[3 * NPA_MAX_E + e] = P.G[e][1]; frg[4 * NPA_MAX_E + e] = P.h[e];
+      }
+      frg[5 * NPA_MAX_E + 0] = F.c; frg[5 * NPA_MAX_E + 1] = F.s; frg[5 * NPA_MAX_E + 2] = F.tx; frg[5 * NPA_MAX_E + 3] = F.ty;
+      frg[5 * NPA_MAX_E + 4] = F.tstep;
+    }
+  }
+  F.c = uni(F.c); F.s = uni(F.s); F.tx = uni(F.tx); F.ty = uni(F.ty); F.tstep = uni(F.tstep);
+  if constexpr (!RG_LDS) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) { F.rg[0][e] = uni(F.rg[0][e]); F.rg[1][e] = uni(F.rg[1][e]); }
+  }
 }
 
 // one point (two lanes) through point flow + encoder + lam/distance
@@ -650,36 +676,29 @@ __device__ __forceinline__ void point_features(const DevParams& P, const SliceFr
   }
 }
 
-// point_features with the streamed-weight encoder (exact rows; same operation order); BF16: the reduced-precision tier,
-// wls then points at the bf16 fragments (WP_WB16)
-template <int E, bool BF16 = false, bool PERM = false>
-__device__ __forceinline__ void point_features_stream(const DevParams& P, const SliceFrame& F, float w1, const float* __restrict__ wls,
-                                                      const float* vec, const float* w6, const float* b6, const float* px_row,
-                                                      const float* py_row, const float* vx_row, const float* vy_row, int src,
-                                                      int lane, float mu[E], float& gx, float& gy, float& lx, float& ly,
-                                                      float& dist, float& p0x, float& p0y) {
-  gx = px_row[src];
-  gy = py_row[src];
-  if (vx_row) {
-    gx = __fadd_rn(gx, __fmul_rn(F.tstep, __fmul_rn(vx_row[src], P.dt32)));
-    gy = __fadd_rn(gy, __fmul_rn(F.tstep, __fmul_rn(vy_row[src], P.dt32)));
+// element i of the weight pack with the index, constant part included, in a VECTOR register (behind an empty asm): the
+// address is wpack + 4 i as the load forms it.  Written wpack[K + i] with a large constant K, the compiler keeps wpack + 4 K as
+// one more 64-bit scalar per K, computed in front of the loop the load sits in, however rarely the load runs
+__device__ __forceinline__ float wpack_at(const float* __restrict__ wpack, int i) { asm("" : "+v"(i)); return wpack[i]; }
+// point `src` of a scene by INDEX into its two rows -- x at [src], y at [src + n_stride] of ONE base pointer, velocities alike
+// (vel null: a static cloud) -- moved to the slice's time and into the robot frame; pan.py:182, :210, the operations of point_features
+__device__ __forceinline__ void slice_point(const DevParams& P, const SliceFrame& F, const float* __restrict__ pts,
+                                            const float* __restrict__ vel, int n_stride, int src, float& gx, float& gy,
+                                            float& p0x, float& p0y) {
+  int sy = src + n_stride;
+  asm("" : "+v"(sy));                       // (the sum stays an index: folded into the base it is a second row pointer to carry)
+  gx = pts[src];
+  gy = pts[sy];
+  if (vel) {
+    gx = __fadd_rn(gx, __fmul_rn(F.tstep, __fmul_rn(vel[src], P.dt32)));
+    gy = __fadd_rn(gy, __fmul_rn(F.tstep, __fmul_rn(vel[sy], P.dt32)));
   }
-  float dx = __fsub_rn(gx, F.tx), dy = __fsub_rn(gy, F.ty);
+  const float dx = __fsub_rn(gx, F.tx), dy = __fsub_rn(gy, F.ty);
   p0x = fmaf(F.c, dx, __fmul_rn(F.s, dy));
   p0y = fmaf(F.c, dy, -__fmul_rn(F.s, dx));
-  if constexpr (BF16) encode_tile_bf16<E>(w1, wls, vec, w6, b6, p0x, p0y, lane, mu);
-  else encode_tile_stream<E, PERM>(w1, wls, vec, w6, b6, p0x, p0y, lane, mu);
-  lx = 0.f; ly = 0.f; dist = 0.f;
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    lx = fmaf(F.rg[0][e], mu[e], lx);
-    ly = fmaf(F.rg[1][e], mu[e], ly);
-    float tmp = __fsub_rn(fmaf(P.G[e][0], p0x, __fmul_rn(P.G[e][1], p0y)), P.h[e]);
-    dist = fmaf(mu[e], tmp, dist);
-  }
 }
 
-// point_features_stream on a 16-point tile: a point is the four lanes {j, j + 16, j + 32, j + 48}; all four return its row
+// point_features with the streamed-weight encoder on a 16-point tile (exact rows; same operation order): a point is the four lanes {j, j + 16, j + 32, j + 48}; all four return its row
 template <int E>
 __device__ __forceinline__ void point_features_stream16(const DevParams& P, const SliceFrame& F, float w1a, float w1b,
                                                         const float* __restrict__ wls16, const float* vec, const float* w6,
@@ -1138,16 +1157,17 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_
 //  * the violation count is mirrored into pinned host memory (npa_audit_peek: no device synchronisation to poll it).
 __device__ __forceinline__ float dpp_f32_b1(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false)); }
 __device__ __forceinline__ float wave_max_f32(float v) {
-  v = fmaxf(v, dpp_f32_b1(v));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false)));
+  v = max_nc(v, dpp_f32_b1(v));
+  v = max_nc(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false)));
+  v = max_nc(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false)));
+  v = max_nc(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false)));
   auto rl = [&](int l) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), l)); };
-  return fmaxf(fmaxf(rl(0), rl(16)), fmaxf(rl(32), rl(48)));
+  return max_nc(max_nc(rl(0), rl(16)), max_nc(rl(32), rl(48)));
 }
 // geometric key of a robot-frame point: v_sqrt_f32 (1 ulp) -- nominates only.  RECT: the axis-aligned box form.
-template <int E, bool RECT>
-__device__ __forceinline__ float geo_key_t(const DevParams& P, float x, float y) {
+// PP: DevParams as the kernels hold it, or DevParams in the kernel-argument segment (geo_key_karg below): one copy of the arithmetic
+template <int E, bool RECT, class PP>
+__device__ __forceinline__ float geo_key_t(const PP& P, float x, float y) {
   if constexpr (RECT) {
     const float dx = fmaxf(fabsf(x - P.rcx) - P.rhx, 0.f), dy = fmaxf(fabsf(y - P.rcy) - P.rhy, 0.f);
     return __builtin_amdgcn_sqrtf(fmaf(dx, dx, dy * dy));
@@ -1166,8 +1186,8 @@ __device__ __forceinline__ float geo_key_t(const DevParams& P, float x, float y)
     return inside ? 0.f : __builtin_amdgcn_sqrtf(best);
   }
 }
-template <int E>
-__device__ __forceinline__ float geo_key(const DevParams& P, float x, float y) {
+template <int E, class PP>
+__device__ __forceinline__ float geo_key(const PP& P, float x, float y) {
   return P.geo_rect ? geo_key_t<E, true>(P, x, y) : geo_key_t<E, false>(P, x, y);
 }
 
@@ -1241,6 +1261,14 @@ __device__ __forceinline__ unsigned key_pass(const DevParams& P, const SliceFram
   return lmin;
 }
 
+// (select_geo_body.inc, the stage loop)
+#define SEL_OPAQUE_V(x) asm volatile("" : "+v"(x))
+#define SEL_OPAQUE_S(x) do { (x) = __builtin_amdgcn_readfirstlane(x); asm volatile("" : "+s"(x)); } while (0)   // (x is wave-uniform)
+#define SEL_LDS_FRAME (6 * NPA_MAX_E)              // floats of the frame's image in LDS (select_geo_carve.inc; the launchers size it)
+// the stage loop's wave-uniform switches, bits of the scalar `st`
+enum { ST_OVERFLOW = 1, ST_ALL = 2, ST_USE16 = 4, ST_USET = 8, ST_AUD16 = 16, ST_AUDIT_WAVE = 32, ST_HAS_AUDIT = 64, ST_DISTRUST = 128 };
+#define ST_IS(f) ((st & (unsigned)(f)) != 0u)
+#define ST_PUT(f, v) (st = (v) ? (st | (unsigned)(f)) : (st & ~(unsigned)(f)))
 #define SEL2_TRIP 256                            // points per trip of the key pass (4 per lane)
 // -DNPA_SEL_PROF: s_memtime stamps between the phases of a wave, summed over all waves in npa_sel_prof[] (slot 15 counts
 // the waves); tests/tools/select_phase_cycles.py builds that variant next to the product library and reads it back
@@ -1265,16 +1293,66 @@ extern "C" int npa_dbg_sel_prof(unsigned long long* out16, int reset) {
 #define SELP_DECL
 #define SELP(i)
 #endif
+// ---- the kernel-argument segment, read by hand --------------------------------------------------------------------------
+// What a wave needs of its arguments only at the END (the five output pointers, the statistics and audit counters) the compiler
+// loads at the top with everything else and carries through the kernel: about a dozen 64-bit scalars parked in VGPR lanes and
+// fetched back with v_readlane at the emit.  The body therefore takes them out of the argument segment itself, through a base
+// pointer that passed an empty asm (the loads can neither be merged with the preamble's nor hoisted), one phase ahead of their
+// use.  The pointer stays a pointer to the constant address space throughout: the loads are s_load_dword*.
+// SelGeoArgs mirrors the parameter list of select_geo_kernel (arguments sit in the segment in order, each at its natural
+// alignment: the layout of a struct); the group kernel's per-call block is SelGeoCall (pan_common.h) at G.c[blockIdx.y].
+#define NPA_KARG __attribute__((address_space(4)))
+#define NPA_GLOBAL __attribute__((address_space(1)))
+typedef const char NPA_KARG* karg_ptr;
+struct SelGeoArgs {
+  DevParams P; const float* wpack; int n_stride; const float* cur_s; const float* points; const float* vel; const int* n_points;
+  const int* flags; float* mu_sorted; float* lam_sorted; float* pts_sorted; float* dist_sorted; int* count; int scene0, t0, nsl,
+  nscene, debug; unsigned* stats; const float* trig; unsigned* audit; unsigned audit_thresh, audit_seed; float margin_scale;
+};
+struct SelGeoGroupArgs { DevParams P; SelGeoGroup G; int t0, nsl, nscene, debug; unsigned audit_thresh; float margin_scale; };
+struct SelOutPtrs { float* mu; float* lam; float* pts; float* dist; int* count; };      // (consecutive in both layouts)
+static_assert(offsetof(SelGeoArgs, count) - offsetof(SelGeoArgs, mu_sorted) == 32 && offsetof(SelGeoCall, count) - offsetof(SelGeoCall, mu_sorted) == 32,
+              "SelOutPtrs is read as one block");
+// (what the compiler lays out for the two parameter lists on gfx950, read from the kernels' metadata; a parameter added to or
+// moved in a kernel's list without its mirror fails here or at the offsets below)
+static_assert(sizeof(DevParams) == 0x1a8 && offsetof(SelGeoArgs, wpack) == sizeof(DevParams) && offsetof(SelGeoGroupArgs, G) == sizeof(DevParams),
+              "DevParams is the first argument of both kernels");
+static_assert(sizeof(SelGeoCall) == 0x78 && sizeof(SelGeoGroupArgs) == 0x1a8 + 8 * 0x78 + 24 && offsetof(SelGeoGroupArgs, debug) == 0x1a8 + 8 * 0x78 + 12,
+              "SelGeoGroupArgs mirrors select_geo_group_kernel(P, G, t0, nsl, nscene, debug, audit_thresh, margin_scale)");
+static_assert(offsetof(SelGeoArgs, mu_sorted) == 0x1a8 + 0x38 && offsetof(SelGeoArgs, debug) == 0x1a8 + 0x70 && offsetof(SelGeoArgs, stats) == 0x1a8 + 0x78 &&
+              offsetof(SelGeoArgs, audit) == 0x1a8 + 0x88 && sizeof(SelGeoArgs) == 0x1a8 + 0xa0,
+              "SelGeoArgs mirrors the parameter list of select_geo_kernel");
+__device__ __forceinline__ karg_ptr karg_fence(karg_ptr p) { asm volatile("" : "+s"(p)); return p; }
+template <class T>
+__device__ __forceinline__ T karg_load(karg_ptr p, size_t off) { return *reinterpret_cast<const T NPA_KARG*>(p + off); }
+// SEL_KARG(member): the argument `member` of this wave's call, fetched now
+#define SEL_KARG(T_, member) karg_load<T_>(SEL_KARGS_LATE(), SEL_KARG_OFF(member))
+// geo_key with the polygon read from the kernel-argument segment (DevParams is the first argument of both kernels) through a
+// fenced base: inside the stage loop.  Read through `P`, the twenty-odd dwords of the general polygon (pvy ... pil, loop-invariant
+// scalar loads) were fetched in front of the loop and held through it, on a box robot that never takes that branch.
+template <int E>
+__device__ __forceinline__ float geo_key_karg(karg_ptr kbase, float x, float y) {
+  return geo_key<E>(*reinterpret_cast<const DevParams NPA_KARG*>(karg_fence(kbase)), x, y);
+}
+
+// (SelGeoArgs above MUST follow this parameter list, member for member: the body reads some arguments through it)
 template <int E, bool BF16 = false, bool KEYS16 = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(E <= 6 ? 4 : 3, E <= 6 ? 4 : 3))) void select_geo_kernel(
     DevParams P, const float* __restrict__ wpack, int n_stride, const float* __restrict__ cur_s,
     const float* __restrict__ points, const float* __restrict__ vel, const int* __restrict__ n_points,
-    const int* __restrict__ flags, float* __restrict__ mu_sorted, float* __restrict__ lam_sorted,
-    float* __restrict__ pts_sorted, float* __restrict__ dist_sorted, int* __restrict__ count, int scene0, int t0, int nsl,
-    int nscene, int debug, unsigned* __restrict__ stats, const float* __restrict__ trig, unsigned* __restrict__ audit,
+    const int* __restrict__ flags, float* __restrict__ mu_sorted_, float* __restrict__ lam_sorted_,
+    float* __restrict__ pts_sorted_, float* __restrict__ dist_sorted_, int* __restrict__ count_, int scene0, int t0, int nsl,
+    int nscene, int debug, unsigned* __restrict__ stats_, const float* __restrict__ trig, unsigned* __restrict__ audit,
     unsigned audit_thresh, unsigned audit_seed, float margin_scale) {
+  // (the arguments with a trailing underscore are read by SEL_KARG where the body needs them, not here)
+#define SEL_KARG_OFF(member) offsetof(SelGeoArgs, member)
+#define SEL_KBASE_OFF(member) offsetof(SelGeoArgs, member)
+  const karg_ptr sel_kbase = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+#define SEL_KARGS_LATE() karg_fence(sel_kbase)
+#define SEL_KOFF_STORE()
+#define SEL_KOFF() 0
 #include "select_geo_carve.inc"
-  const int lane = threadIdx.x, j = lane & 31, hf = lane >> 5;
+  int lane = threadIdx.x;
   SELP_DECL;
   // workgroup w runs on XCD w % 8 (observed dispatch order; a speed assumption only): scene = 8 * (w / (8 nsl)) + w % 8
   const int w = blockIdx.x, xcd = w & 7, r_ = w >> 3;
@@ -1282,27 +1360,51 @@ __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_
   if (bl >= nscene) return;
   const int t = r_ % nsl + t0, b = bl + scene0;
 #include "select_geo_body.inc"
+#undef SEL_KARG_OFF
+#undef SEL_KBASE_OFF
+#undef SEL_KARGS_LATE
+#undef SEL_KOFF_STORE
+#undef SEL_KOFF
 }
 
 // select_geo_kernel over a GROUP of forward calls (pan_common.h: merged launches): blockIdx.y = the call, blockIdx.x what it
 // is above; the per-call pointers come out of the kernel arguments, everything else is the same statements.
+// (SelGeoGroupArgs above MUST follow this parameter list)
 template <int E, bool BF16 = false, bool KEYS16 = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu_waves_per_eu(E <= 6 ? 4 : 3, E <= 6 ? 4 : 3))) void select_geo_group_kernel(
     DevParams P, SelGeoGroup G, int t0, int nsl, int nscene, int debug, unsigned audit_thresh, float margin_scale) {
-  const SelGeoCall& q = G.c[blockIdx.y];
-  const float* __restrict__ wpack = q.wpack; const float* __restrict__ cur_s = q.cur_s; const float* __restrict__ points = q.points;
-  const float* __restrict__ vel = q.vel; const int* __restrict__ n_points = q.n_points; const int* __restrict__ flags = q.flags;
-  float* __restrict__ mu_sorted = q.mu_sorted; float* __restrict__ lam_sorted = q.lam_sorted; float* __restrict__ pts_sorted = q.pts_sorted;
-  float* __restrict__ dist_sorted = q.dist_sorted; int* __restrict__ count = q.count; unsigned* __restrict__ stats = q.stats;
-  const float* __restrict__ trig = q.trig; unsigned* __restrict__ audit = q.audit;
-  const int n_stride = q.n_stride;
-  unsigned audit_seed = q.audit_seed;
+#define SEL_KARG_OFF(member) offsetof(SelGeoCall, member)
+#define SEL_KBASE_OFF(member) offsetof(SelGeoGroupArgs, member)
+  const karg_ptr sel_kbase = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  const int sel_koff = (int)offsetof(SelGeoGroupArgs, G) + (int)blockIdx.y * (int)sizeof(SelGeoCall);
+  const karg_ptr sel_kargs = sel_kbase + sel_koff;
+  // (behind the preamble the call's block is found again through its OFFSET, parked in the frame's LDS image by the body: the
+  // 64-bit base held to the emit was the one pair the merged kernel had to park more than the single-call one)
+#define SEL_KARGS_LATE() (karg_fence(sel_kbase) + __builtin_amdgcn_readfirstlane(__float_as_int(frg[5 * NPA_MAX_E + 7])))
+#define SEL_KOFF_STORE() do { if (threadIdx.x == 0) frg[5 * NPA_MAX_E + 7] = __int_as_float(sel_koff); } while (0)
+#define SEL_KOFF() sel_koff
+  // (field by field: `G.c[blockIdx.y]` as a whole came in as two 16- and 8-dword loads and was parked as such)
+  const float* __restrict__ wpack = karg_load<const float*>(sel_kargs, SEL_KARG_OFF(wpack));
+  const float* __restrict__ cur_s = karg_load<const float*>(sel_kargs, SEL_KARG_OFF(cur_s));
+  const float* __restrict__ points = karg_load<const float*>(sel_kargs, SEL_KARG_OFF(points));
+  const float* __restrict__ vel = karg_load<const float*>(sel_kargs, SEL_KARG_OFF(vel));
+  const int* __restrict__ n_points = karg_load<const int*>(sel_kargs, SEL_KARG_OFF(n_points));
+  const int* __restrict__ flags = karg_load<const int*>(sel_kargs, SEL_KARG_OFF(flags));
+  const float* __restrict__ trig = karg_load<const float*>(sel_kargs, SEL_KARG_OFF(trig));
+  unsigned* __restrict__ audit = karg_load<unsigned*>(sel_kargs, SEL_KARG_OFF(audit));
+  const int n_stride = karg_load<int>(sel_kargs, SEL_KARG_OFF(n_stride));
+  unsigned audit_seed = karg_load<unsigned>(sel_kargs, SEL_KARG_OFF(audit_seed));
 #include "select_geo_carve.inc"
-  const int lane = threadIdx.x, j = lane & 31, hf = lane >> 5;
+  int lane = threadIdx.x;
   SELP_DECL;
   const int w = blockIdx.x, xcd = w & 7, r_ = w >> 3;
   const int bl = (r_ / nsl) * 8 + xcd;
   if (bl >= nscene) return;
   const int t = r_ % nsl + t0, b = bl;
 #include "select_geo_body.inc"
+#undef SEL_KARG_OFF
+#undef SEL_KBASE_OFF
+#undef SEL_KARGS_LATE
+#undef SEL_KOFF_STORE
+#undef SEL_KOFF
 }

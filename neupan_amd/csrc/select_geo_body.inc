@@ -2,7 +2,7 @@
 // statements: included by select_geo_kernel and select_geo_group_kernel (dune_device.h: workgroup -> (scene, slice) / (call,
 // scene, slice)).  Textual for the same reason as nrmp_qp_body.inc: the kernel's
 // token stream, hence its machine code, stays what the counter records were measured on.  Expects in scope: the kernel's
-// parameters, the carve of select_geo_carve.inc, `lane`, `j`, `hf`, `b`, `t`.
+// parameters, the carve of select_geo_carve.inc, `lane`, `b`, `t`, `sel_kbase` and the SEL_K* macros (dune_device.h: the argument segment).
   const int T = P.T, M = P.M;
   // the exact encoder's tile, chosen PER TRIP on the exact-rows instantiation: 16 points (v_mfma_f32_16x16x4_f32, dune_device.h)
   // when at most 16 are left -- candidate lists carry a median of 14-19 points: half of a 32-point tile was padding --, 32 points
@@ -13,10 +13,17 @@
   if (flags && flags[b * 4 + 0]) return;
   int n_raw = n_points ? n_points[b] : n_stride;
   n_raw = n_raw < 0 ? 0 : (n_raw > n_stride ? n_stride : n_raw);
-  const int n_use = n_raw < P.dune_max_num ? n_raw : P.dune_max_num;
-  const size_t orow = (size_t)b * (T + 1) + t;
+  int n_use = n_raw < P.dune_max_num ? n_raw : P.dune_max_num;
+  // the output row (scenes x slices: far below 2^31), computed on the VECTOR side from a scene number behind an empty asm: the
+  // early exit below and the emit (through LDS) use it; as a scalar it -- and T, b, t with it -- was parked from here to the
+  // early exit's block, which the compiler lays out at the kernel's end
+  int orow_v = b;
+  asm volatile("" : "+v"(orow_v));
+  orow_v = orow_v * (T + 1) + t;
+  int koff_v = SEL_KOFF();                               // (likewise: where this call's arguments start, for the early exit)
+  asm volatile("" : "+v"(koff_v));
   if (n_use <= 0) {
-    if (lane == 0) count[orow] = 0;
+    if (lane == 0) ((int NPA_GLOBAL*)karg_load<int*>(karg_fence(sel_kbase) + __builtin_amdgcn_readfirstlane(koff_v), SEL_KARG_OFF(count)))[orow_v] = 0;
     return;
   }
   // the preamble's loads as ONE batch (written as loops they compiled to a load -> wait -> LDS write per trip: twelve global
@@ -35,14 +42,16 @@
   const float w1 = wpack[WP_W1 + lane];
   const float w1a = TILE16 ? wpack[WP_W116 + lane] : 0.f, w1b = TILE16 ? wpack[WP_W116 + 64 + lane] : 0.f;
   SliceFrame F;
-  load_frame<E>(P, cur_s, trig, b, t, F);
+  load_frame<E, true>(P, cur_s, trig, b, t, F, frg);        // (F.rg: in LDS, read by the row epilogue below)
+  if (lane == 0) frg[5 * NPA_MAX_E + 5] = __int_as_float(orow_v);      // (read back at the emit)
+  SEL_KOFF_STORE();
   const float* px_row = points + (size_t)b * 2 * n_stride;
-  const float* py_row = px_row + n_stride;
   const float* vx_row = vel ? vel + (size_t)b * 2 * n_stride : nullptr;
-  const float* vy_row = vel ? vx_row + n_stride : nullptr;
   const bool has_vel = vel != nullptr, decim = n_use < n_raw;
+  // (the audit block's pointer is used here and in the audit-wave hash below; the counters at the end fetch it again)
+  const bool has_audit = audit != nullptr;             // (ST_HAS_AUDIT / ST_DISTRUST of `st` inside the stage loop)
   // a violation seen by an earlier launch (or an earlier wave of this one): everything is a candidate from here on
-  const bool distrust = audit && __builtin_amdgcn_readfirstlane((int)aud_viol) != 0;
+  const bool distrust = has_audit && __builtin_amdgcn_readfirstlane((int)aud_viol) != 0;
   // a polygon that is not an axis-aligned box: the key pass ranks on the distance to its BOUNDING BOX (a lower bound of g, 8
   // instructions instead of 12 per edge: at 8 edges and 5000 points the pass was most of this kernel), g <= key + S
   const float boxS = (P.geo_rect && E == 4) ? 0.f : __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(wpack[WP_TABH + 4])));
@@ -52,7 +61,8 @@
   // ---- key pass: dkey[n] = bits of g(point n) (0xFFFFFFFF behind the slice's end), lane minimum on the way ----------
   const int n_pad = (n_use + SEL2_TRIP - 1) & ~(SEL2_TRIP - 1);
   unsigned lmin;
-#define KP(R_, V_, D_) lmin = key_pass<E, R_, V_, D_>(P, F, px_row, py_row, vx_row, vy_row, dkey, n_raw, n_use, n_pad, lane)
+#define KP(R_, V_, D_) \
+  lmin = key_pass<E, R_, V_, D_>(P, F, px_row, px_row + n_stride, vx_row, vx_row ? vx_row + n_stride : nullptr, dkey, n_raw, n_use, n_pad, lane)
   if (has_vel) { if (decim) KP(true, true, true); else KP(true, true, false); }
   else { if (decim) KP(true, false, true); else KP(true, false, false); }
 #undef KP
@@ -67,7 +77,7 @@
   WSYNC();
   SELP(1);
 
-  const int msel = n_use < M ? n_use : M;
+  int msel = n_use < M ? n_use : M;
   // msel-th smallest of the 64 lane minima: an upper bound of the msel-th smallest key (each of those lanes holds a key
   // that small; consecutive points sit in different lanes, so a run of near points -- a scan of one obstacle -- does not
   // loosen it).  Fewer than msel lanes with a point (tiny slices): the bound is 0xFFFFFFFF and everything is a candidate.
@@ -87,7 +97,7 @@
     else {
       // the point's g lies in [key, key + S]: the largest margin over the bands of that range (one band for a box)
       float mm = 0.f;
-      for (int bb = npa_geo_band(g), be = npa_geo_band(g + boxS); bb <= be; ++bb) mm = fmaxf(mm, etab[bb]);
+      for (int bb = npa_geo_band(g), be = npa_geo_band(g + boxS); bb <= be; ++bb) mm = max_nc(mm, etab[bb]);
       hi = g + boxS + mm;
     }
   }
@@ -104,7 +114,7 @@
         const float lo_b = __uint_as_float((unsigned)(bnd + (0x3E800000u >> 20)) << 20) - 0.25f;
         const float hi_b = bnd == NPA_GEO_BANDS - 1 ? P.geo_far : __uint_as_float((unsigned)(bnd + 1 + (0x3E800000u >> 20)) << 20) - 0.25f;
         const float reach = U + etab[bnd];
-        if (lo_b < P.geo_far && lo_b <= reach) gs = fmaxf(gs, fminf(hi_b, reach));
+        if (lo_b < P.geo_far && lo_b <= reach) gs = max_nc(gs, min_nc(hi_b, reach));
       }
     }
     gs = wave_max_f32(gs);
@@ -130,7 +140,8 @@
   WSYNC();
   SELP(3);
   int ncand = ntot, fellback = 0;
-  bool overflow = false, all = false;
+  // the wave-uniform switches of the stage loop as BITS of one scalar (as bools each was a 64-bit lane mask, parked and fetched back)
+  unsigned st = (has_audit ? (unsigned)ST_HAS_AUDIT : 0u) | (distrust ? (unsigned)ST_DISTRUST : 0u);
   int total = 0;
   if (ntot <= SEL_CAP && ntot >= msel) {
     if (lane < ntot) sel[lane] = (int)dkey[lane];
@@ -138,17 +149,17 @@
   } else if (ntot < msel) {
     // cannot happen while the threshold covers the nominating lanes' own minima (it does, by construction); if it ever
     // did, exact keys for the whole slice are the answer, not fewer rows than promised
-    overflow = true; fellback = 1; all = true; total = n_use;
+    ST_PUT(ST_OVERFLOW, true); fellback = 1; ST_PUT(ST_ALL, true); total = n_use;
   } else {
     // more candidates than the final ranking holds (a wall at constant distance, a blob inside the robot, a distrusted
     // margin): exact keys for the list -- stored behind it -- or, when it takes more than half the slice, for every point
-    overflow = true;
+    ST_PUT(ST_OVERFLOW, true);
     fellback = 1;
-    all = 2 * ntot > n_use;
-    total = all ? n_use : ntot;
+    ST_PUT(ST_ALL, 2 * ntot > n_use);
+    total = ST_IS(ST_ALL) ? n_use : ntot;
   }
   unsigned* ckey = dkey + ntot;
-  auto cand_index = [&](int q) { return all ? q : (int)dkey[q]; };
+  auto cand_index = [&](int q) { return ST_IS(ST_ALL) ? q : (int)dkey[q]; };
   auto extract = [&]() {                      // the msel smallest (key, index) pairs of dkey[0..n_use) -> sel[0..msel)
     for (int m = 0; m < msel; ++m) {
       unsigned long long best = ~0ull;
@@ -162,13 +173,13 @@
   // which waves run the extra audit tile: a hash of (launch, scene, slice).  The launch number is the host's sequence
   // number plus a device-side count of launches (audit[4], bumped by workgroup 0): a launch replayed from a HIP graph
   // carries a frozen host number, and should still audit other waves and other points each time
-  bool audit_wave = false;
   if (audit && audit_thresh) {
     audit_seed += (unsigned)__builtin_amdgcn_readfirstlane((int)aud_launches);
     if (blockIdx.x == 0 && lane == 0) atomicAdd(audit + 4, 1u);
     unsigned hsh = (audit_seed * 0x9E3779B1u) ^ ((unsigned)b * 0x85EBCA77u) ^ ((unsigned)t * 0xC2B2AE3Du);
     hsh ^= hsh >> 15; hsh *= 0x2C1B3C6Du; hsh ^= hsh >> 12; hsh *= 0x297A2D39u; hsh ^= hsh >> 15;
-    audit_wave = hsh < audit_thresh || audit_thresh == 0xFFFFFFFFu;
+    ST_PUT(ST_AUDIT_WAVE, hsh < audit_thresh || audit_thresh == 0xFFFFFFFFu);
+    if (lane == 0) frg[5 * NPA_MAX_E + 6] = __uint_as_float(audit_seed + (unsigned)t);     // the audit tile's phase (stage 2, behind stage 1's barriers)
   }
   // Stage 0 (overflow only): exact KEYS of the long list, the msel smallest become the candidates.  Stage 1: the final
   // candidates (<= SEL_CAP) with their ROWS parked in LDS, ranked and emitted.  Stage 2 (audit waves): 32 points spread
@@ -182,7 +193,7 @@
   int viol = 0;
   float worst = 0.f;
   // (a list of up to four tiles goes straight to the exact encoder: the filter costs a bf16 pass plus the survivors' exact one)
-  bool use16 = KEYS16 && overflow && !all && !distrust && total > 128;
+  ST_PUT(ST_USE16, KEYS16 && ST_IS(ST_OVERFLOW) && !ST_IS(ST_ALL) && !ST_IS(ST_DISTRUST) && total > 128);
   // TABF (the default instantiation, when the handle carries the table: P.geo_tab): the same filter with the TABLE-corrected
   // geometric key g(p) + f_table(p) (dune_device.h, geo_tab_corr) in place of an encoder pass -- 64 list entries per trip at ~60
   // VALU instructions and two gathers, against 32 per ~16 k-cycle encoder tile; its error is what bilinear interpolation of the
@@ -190,29 +201,32 @@
   // ten-odd points that really compete for rank M, and those alone are encoded exactly.  It also runs on lists that do not
   // overflow but need a second encoder tile (more than 32 candidates).  Survivors are audited like the bf16 tier's.
   constexpr bool TABF = !BF16 && !KEYS16 && (E == 4 || E == 8);      // (the polygon sizes of the benchmark configurations)
-  bool useT = TABF && P.geo_tab != 0 && !distrust && ntot >= msel && (overflow || ntot > 32);
-  if (useT && !overflow) total = ntot;                           // (the list stands in dkey[0 .. ntot); sel[] is rebuilt from the survivors)
-  bool aud16 = false;                                            // stage 1 checks every survivor's |exact - filter key| against m16
+  ST_PUT(ST_USET, TABF && P.geo_tab != 0 && !ST_IS(ST_DISTRUST) && ntot >= msel && (ST_IS(ST_OVERFLOW) || ntot > 32));
+  if (ST_IS(ST_USET) && !ST_IS(ST_OVERFLOW)) total = ntot;       // (the list stands in dkey[0 .. ntot); sel[] is rebuilt from the survivors)
+  ST_PUT(ST_AUD16, false);                                            // stage 1 checks every survivor's |exact - filter key| against m16
   float m16 = 0.f;
   SELP(4);
 #pragma unroll 1
-  for (int stage = (overflow || useT) ? 0 : 1;;) {
+  for (int stage = (ST_IS(ST_OVERFLOW) || ST_IS(ST_USET)) ? 0 : 1;;) {
+    // What the stages derive from the lane number and the slice's sizes (compare masks, clamped counts, the decimation step, the
+    // audit tile's stride: most of it for the rare stages) is loop-invariant, so the compiler computed ALL of it in front of this
+    // loop and parked it in VGPR lanes: ~100 v_writelane per wave, whichever stage ran.  Behind an empty asm the values are
+    // this trip's own: each is derived where it is used.  (Integers only: a pointer through an asm loses its address space.)
+    SEL_OPAQUE_V(lane); SEL_OPAQUE_S(n_use); SEL_OPAQUE_S(n_raw); SEL_OPAQUE_S(msel);
     const int cnt = stage == 0 ? total : (stage == 1 ? ncand : (n_use < 32 ? n_use : 32));
-    if (TABF && stage == 0 && useT) {
-      unsigned* fk = all ? dkey : ckey;
+    if (TABF && stage == 0 && ST_IS(ST_USET)) {
+      unsigned* fk = ST_IS(ST_ALL) ? dkey : ckey;
 #pragma unroll 1
       for (int q0 = 0; q0 < cnt; q0 += 64) {
         const int q = q0 + lane, qc = q < cnt ? q : cnt - 1;
         const int src = src_index(cand_index(qc), n_raw, n_use);
-        float gx = px_row[src], gy = py_row[src];
-        if (vx_row) {
-          gx = __fadd_rn(gx, __fmul_rn(F.tstep, __fmul_rn(vx_row[src], P.dt32)));
-          gy = __fadd_rn(gy, __fmul_rn(F.tstep, __fmul_rn(vy_row[src], P.dt32)));
-        }
-        const float dx = __fsub_rn(gx, F.tx), dy = __fsub_rn(gy, F.ty);
-        const float p0x = fmaf(F.c, dx, __fmul_rn(F.s, dy)), p0y = fmaf(F.c, dy, -__fmul_rn(F.s, dx));
+        SliceFrame Fl;      // (the frame out of LDS, per trip: the key pass's scalars are dead by now, and held across the encoder these are five registers)
+        Fl.c = frg[5 * NPA_MAX_E + 0]; Fl.s = frg[5 * NPA_MAX_E + 1];
+        Fl.tx = frg[5 * NPA_MAX_E + 2]; Fl.ty = frg[5 * NPA_MAX_E + 3]; Fl.tstep = frg[5 * NPA_MAX_E + 4];
+        float gx, gy, p0x, p0y;
+        slice_point(P, Fl, px_row, vx_row, n_stride, src, gx, gy, p0x, p0y);
         // a point outside the calibrated square (or a NaN): no bound on its distance, it survives whatever the others do
-        const float gk = geo_key<E>(P, p0x, p0y);
+        const float gk = geo_key_karg<E>(sel_kbase, p0x, p0y);
         const unsigned kc = gk < P.geo_far ? ordered_key(gk + geo_tab_corr(wpack, p0x, p0y)) : NPA_TAB_KEY_FAR;
         if (q < cnt) fk[q] = kc;                                 // (all: entry q is point q, its geometric key is done with)
       }
@@ -228,63 +242,68 @@
       else if (stage == 1) idx = sel[qc];
       else {                                  // audit tile: 32 points n_use / 32 apart, the phase moves with the launch
         const int step = n_use >> 5;
-        idx = step > 0 ? qc * step + (int)((audit_seed + (unsigned)t) % (unsigned)step) : qc;
+        idx = step > 0 ? qc * step + (int)(__float_as_uint(frg[5 * NPA_MAX_E + 6]) % (unsigned)step) : qc;
       }
-      float mu[E], gx, gy, lx, ly, dist, p0x, p0y;
+      // the point flow, the encoder and the row epilogue of point_features_stream / _stream16 (dune_device.h), operation for
+      // operation -- spelled out here because the point is fetched by INDEX from the scene's two rows (slice_point) and the
+      // frame's rows come out of LDS: four row pointers and 2 E frame scalars less to carry through this loop
+      float mu[E], gx, gy, lx = 0.f, ly = 0.f, dist = 0.f, p0x, p0y;
+      SliceFrame Fl;      // (the frame out of LDS, per trip: the key pass's scalars are dead by now, and held across the encoder these are five registers)
+      Fl.c = frg[5 * NPA_MAX_E + 0]; Fl.s = frg[5 * NPA_MAX_E + 1];
+      Fl.tx = frg[5 * NPA_MAX_E + 2]; Fl.ty = frg[5 * NPA_MAX_E + 3]; Fl.tstep = frg[5 * NPA_MAX_E + 4];
+      slice_point(P, Fl, px_row, vx_row, n_stride, src_index(idx, n_raw, n_use), gx, gy, p0x, p0y);
       if constexpr (KEYS16) {
-        if (stage == 0 && use16)
-          point_features_stream<E, true>(P, F, w1, wpack + WP_WB16, vec, w6, b6, px_row, py_row, vx_row, vy_row,
-                                         src_index(idx, n_raw, n_use), lane, mu, gx, gy, lx, ly, dist, p0x, p0y);
-        else
-          point_features_stream<E, false>(P, F, w1, wls, vec, w6, b6, px_row, py_row, vx_row, vy_row,
-                                          src_index(idx, n_raw, n_use), lane, mu, gx, gy, lx, ly, dist, p0x, p0y);
+        if (stage == 0 && ST_IS(ST_USE16)) encode_tile_bf16<E>(w1, wpack + WP_WB16, vec, w6, b6, p0x, p0y, lane, mu);
+        else encode_tile_stream<E, false>(w1, wls, vec, w6, b6, p0x, p0y, lane, mu);
       } else if constexpr (TILE16) {
-        if (narrow)
-          point_features_stream16<E>(P, F, w1a, w1b, wls16, vec, w6, b6, px_row, py_row, vx_row, vy_row,
-                                     src_index(idx, n_raw, n_use), lane, mu, gx, gy, lx, ly, dist, p0x, p0y);
-        else
-          point_features_stream<E, false, true>(P, F, w1, wls, vec, w6, b6, px_row, py_row, vx_row, vy_row,
-                                                src_index(idx, n_raw, n_use), lane, mu, gx, gy, lx, ly, dist, p0x, p0y);
-      } else
-      point_features_stream<E, BF16>(P, F, w1, wls, vec, w6, b6, px_row, py_row, vx_row, vy_row,
-                               src_index(idx, n_raw, n_use), lane, mu, gx, gy, lx, ly, dist, p0x, p0y);
+        if (narrow) encode_tile16_stream<E>(w1a, w1b, wls16, vec, w6, b6, p0x, p0y, lane, mu);
+        else encode_tile_stream<E, true>(w1, wls, vec, w6, b6, p0x, p0y, lane, mu);
+      } else if constexpr (BF16) encode_tile_bf16<E>(w1, wls, vec, w6, b6, p0x, p0y, lane, mu);
+      else encode_tile_stream<E, false>(w1, wls, vec, w6, b6, p0x, p0y, lane, mu);
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        lx = fmaf(frg[e], mu[e], lx);                                    // (uniform LDS addresses: broadcast reads)
+        ly = fmaf(frg[NPA_MAX_E + e], mu[e], ly);
+        const float tmp = __fsub_rn(fmaf(frg[2 * NPA_MAX_E + e], p0x, __fmul_rn(frg[3 * NPA_MAX_E + e], p0y)), frg[4 * NPA_MAX_E + e]);
+        dist = fmaf(mu[e], tmp, dist);
+      }
       if constexpr (KEYS16 || TABF) {
-        if (stage == 1 && aud16) {
+        if (stage == 1 && ST_IS(ST_AUD16)) {
           // the bound the survivors rest on, checked on every one of them: |exact - filter key| <= m16
           const unsigned k16 = s16[qc];
           const float d16 = __uint_as_float((k16 & 0x80000000u) ? (k16 & 0x7FFFFFFFu) : ~k16);
-          const float ex = fabsf(dist - d16) - (TABF ? wpack[WP_KTAB + npa_geo_band(d16)] * margin_scale : m16);
+          const float ex = fabsf(dist - d16) - (TABF ? wpack_at(wpack, WP_KTAB + npa_geo_band(d16)) * margin_scale : m16);
           const bool bad = own && q < cnt && ex > 0.f;
           viol += bad ? 1 : 0;
-          worst = bad ? fmaxf(worst, ex) : worst;
+          worst = bad ? max_nc(worst, ex) : worst;
         }
       }
-      if (stage != 0 && audit) {
+      if (stage != 0 && ST_IS(ST_HAS_AUDIT)) {
         // the bound the candidates rest on, checked on every exactly encoded point: |exact - g| <= margin[band(g)]
-        const float g = geo_key<E>(P, p0x, p0y);
+        const float g = geo_key_karg<E>(sel_kbase, p0x, p0y);
         const float ex = fabsf(dist - g) - etab[npa_geo_band(g)];
         const bool bad = own && q < cnt && g < P.geo_far && ex > 0.f;          // (NaN distance: ex is NaN, not counted here;
         viol += bad ? 1 : 0;                                                       //  a NaN row is a broken checkpoint, not a key matter)
-        worst = bad ? fmaxf(worst, ex) : worst;
+        worst = bad ? max_nc(worst, ex) : worst;
         if constexpr (TABF) {
           // The table filter EXCLUDES on its key: a wrong table margin drops a true member on the excluded side, where the audit of
           // the survivors (aud16 above) never looks.  The audit waves therefore check |exact - (g + f_table)| <= m_table[band(key)]
           // on every point they encode exactly -- their candidates and the 32 points of stage 2 spread over the slice, mostly
           // NON-candidates and non-survivors -- and count a failure like one of the geometric margin: the handle distrusts both.
-          if (audit_wave && P.geo_tab != 0) {
+          if (ST_IS(ST_AUDIT_WAVE) && karg_load<int>(karg_fence(sel_kbase), offsetof(DevParams, geo_tab)) != 0) {
             const float tk = g + geo_tab_corr(wpack, p0x, p0y);
-            const float mt = wpack[WP_KTAB + npa_geo_band(tk)] * margin_scale;
+            const float mt = wpack_at(wpack, WP_KTAB + npa_geo_band(tk)) * margin_scale;
             const float ext = fabsf(dist - tk) - mt;
             const bool badt = own && q < cnt && g < P.geo_far && mt < 3.0e38f && ext > 0.f;
             viol += badt ? 1 : 0;
-            worst = badt ? fmaxf(worst, ext) : worst;
+            worst = badt ? max_nc(worst, ext) : worst;
           }
         }
       }
       if (own && q < cnt) {
         const unsigned k = ordered_key(dist);
         if (stage == 0) {
-          if (all) dkey[idx] = k;
+          if (ST_IS(ST_ALL)) dkey[idx] = k;
           else ckey[q] = k;
         } else if (stage == 1) {
           float* r = rows + q * ROW_W;
@@ -299,9 +318,16 @@
     if (stage == 0) SELP(5); else if (stage == 1) SELP(6); else SELP(7);     // exact keys of a long list / the candidates' rows / audit tile
     if (stage == 2) break;
     if (stage == 1) {
+      const size_t orow = (size_t)__float_as_int(frg[5 * NPA_MAX_E + 5]);
+      const int Me = karg_load<int>(karg_fence(sel_kbase), offsetof(DevParams, M));      // (M, fetched for the emit: not carried to it)
       // lane q speaks for candidate q: rank on the exact (distance, index) key, emit; rows >= msel replicate row 0
       const bool mine = lane < ncand;
       const unsigned long long kx = mine ? (((unsigned long long)rkey[2 * lane + 1] << 32) | rkey[2 * lane]) : ~0ull;
+      // the five output pointers leave the argument segment here: their round trip runs behind the rank loop, and they are
+      // live from here to the emit only (fetched at the emit itself, the lone wave waited for them: DESIGN.md 3.1)
+      const karg_ptr ko = SEL_KARGS_LATE() + SEL_KARG_OFF(mu_sorted);
+      const SelOutPtrs O = {karg_load<float*>(ko, 0), karg_load<float*>(ko, 8), karg_load<float*>(ko, 16), karg_load<float*>(ko, 24),
+                            karg_load<int*>(ko, 32)};
       int rank = 0;
       // (four candidates per trip: a lane behind the list holds ~0, which is smaller than nothing -- no remainder handling, a
       // quarter of the loop's scalar instructions)
@@ -312,8 +338,10 @@
       }
       if (mine && rank < msel) {
         const float* r = rows + lane * ROW_W;
+        float NPA_GLOBAL* mu_sorted = (float NPA_GLOBAL*)O.mu; float NPA_GLOBAL* lam_sorted = (float NPA_GLOBAL*)O.lam;
+        float NPA_GLOBAL* pts_sorted = (float NPA_GLOBAL*)O.pts; float NPA_GLOBAL* dist_sorted = (float NPA_GLOBAL*)O.dist;
         auto put = [&](int q) {
-          const size_t o = orow * M + q;
+          const size_t o = orow * Me + q;
 #pragma unroll
           for (int e = 0; e < E; ++e) mu_sorted[o * E + e] = r[e];
           lam_sorted[o * 2 + 0] = r[E]; lam_sorted[o * 2 + 1] = r[E + 1];
@@ -322,21 +350,36 @@
         };
         put(rank);
         if (rank == 0)                          // the nearest row also fills rows >= msel: the padding rule of nrmp.py:258-259
-          for (int q = msel; q < M; ++q) put(q);
+#pragma unroll 1                                // (unrolled by two, its trip counts were eight scalars hoisted in front of the stage loop)
+          for (int q = msel; q < Me; ++q) put(q);
       }
-      if (lane == 0) count[orow] = debug ? (msel | ((ntot < 255 ? ntot : 255) << 8) | (fellback << 16)) : msel;
+      if (lane == 0) {
+        int word = msel;
+        // (the debug flag and what the debug word is made of: read / derived here, behind a fence -- as loop invariants the
+        // flag's compare mask and the shifted count were parked across the stage loop)
+        if (karg_load<int>(karg_fence(sel_kbase), SEL_KBASE_OFF(debug))) {
+          int nt = ntot;
+          asm volatile("" : "+s"(nt));
+          word |= ((nt < 255 ? nt : 255) << 8) | (fellback << 16);
+        }
+        ((int NPA_GLOBAL*)O.count)[orow] = word;
+      }
       SELP(8);
-      if (!audit_wave) break;
+      if (!ST_IS(ST_AUDIT_WAVE)) break;
       stage = 2;
       continue;
     }
-    const bool filt = (KEYS16 && use16) || (TABF && useT);
-    if (stats && lane == 0 && !(TABF && useT)) atomicAdd(stats, (unsigned)((total + 31) / 32));     // (in 32-point tiles: the key policy's unit)
-    if (all && !filt) {
+    SEL_OPAQUE_S(st);                                           // (stage 0 only: the switches tested afresh, not as masks kept from the loop's top)
+    const bool filt = (KEYS16 && ST_IS(ST_USE16)) || (TABF && ST_IS(ST_USET));
+    if (lane == 0 && !(TABF && ST_IS(ST_USET))) {                                                              // (in 32-point tiles: the key policy's unit)
+      unsigned* stats = SEL_KARG(unsigned*, stats);
+      if (stats) atomicAdd(stats, (unsigned)((total + 31) / 32));
+    }
+    if (ST_IS(ST_ALL) && !filt) {
       extract();
     } else if (filt) {
       // kth = the msel-th smallest filter (key, index) pair, found WITHOUT retiring entries (the list is filtered below)
-      const unsigned* fk = all ? dkey : ckey;
+      const unsigned* fk = ST_IS(ST_ALL) ? dkey : ckey;
       // (ordered_key back to the float: distances of points inside the polygon are negative, and they are the nearest ones)
       auto key_float = [](unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); };
       // TABF: the margin of the table key is a function of the band of the KEY (WP_KTAB[band(key)]: the network has creases, and
@@ -346,8 +389,8 @@
       // geometric window's g*).  Lane l holds the margins of bands l and 64 + l.
       float kt0 = 0.f, kt1 = 0.f, Ub = -3.0e38f;
       if constexpr (TABF) {
-        kt0 = wpack[WP_KTAB + lane] * margin_scale;
-        kt1 = wpack[WP_KTAB + 64 + (lane < NPA_GEO_BANDS - 64 ? lane : NPA_GEO_BANDS - 65)] * margin_scale;
+        kt0 = wpack_at(wpack, WP_KTAB + lane) * margin_scale;
+        kt1 = wpack_at(wpack, WP_KTAB + 64 + (lane < NPA_GEO_BANDS - 64 ? lane : NPA_GEO_BANDS - 65)) * margin_scale;
       }
       unsigned long long prev = 0ull;
       for (int m2 = 0; m2 < msel; ++m2) {
@@ -362,7 +405,7 @@
           const int bm = __builtin_amdgcn_readfirstlane(npa_geo_band(km));
           const float mb = __uint_as_float(bm < 64 ? __builtin_amdgcn_readlane(__float_as_uint(kt0), bm & 63)
                                                    : __builtin_amdgcn_readlane(__float_as_uint(kt1), bm & 63));
-          Ub = fmaxf(Ub, km + mb);                                 // (a far / NaN key among them: inf or NaN, refused below)
+          Ub = max_nc(Ub, km + mb);                                 // (a far / NaN key among them: inf or NaN, refused below)
           if (!(km == km)) Ub = __builtin_inff();
         }
       }
@@ -385,7 +428,7 @@
             const float lo_b = bnd == 0 ? -3.0e38f : __uint_as_float((unsigned)(bnd + (0x3E800000u >> 20)) << 20) - 0.25f;
             const float hi_b = bnd == NPA_GEO_BANDS - 1 ? 3.0e38f : __uint_as_float((unsigned)(bnd + 1 + (0x3E800000u >> 20)) << 20) - 0.25f;
             const float reach = Ub + mb;
-            if (lo_b <= reach) gs = fmaxf(gs, fminf(hi_b, reach));
+            if (lo_b <= reach) gs = max_nc(gs, min_nc(hi_b, reach));
           }
         }
         gs = wave_max_f32(gs);
@@ -410,7 +453,7 @@
         bound_ok = dk == dk && fabsf(dk) < 3.0e38f && m16 < 0.25f;
         thr16 = ordered_key(dk + 2.0f * m16);
       }
-      use16 = false; useT = false;                               // (whatever follows, stage 0 does not run the filter again)
+      ST_PUT(ST_USE16, false); ST_PUT(ST_USET, false);                               // (whatever follows, stage 0 does not run the filter again)
       bool decided = false;
       if (bound_ok) {
         // survivors: filter key at or below the threshold.  Their indices are compacted IN PLACE over the list (position <= source,
@@ -433,8 +476,8 @@
         decided = true;
         if (nsurv <= SEL_CAP && nsurv >= msel) {                 // the survivors fit the final ranking: straight to the exact rows
           fellback = 3;                                          // (debug statistics: the filter decided this slice)
-          aud16 = true;                                          // (stage 1 audits |exact - filter key| of every survivor)
-          all = false;
+          ST_PUT(ST_AUD16, true);                                          // (stage 1 audits |exact - filter key| of every survivor)
+          ST_PUT(ST_ALL, false);
           ncand = nsurv;
           stage = 1;
           SELP(9);
@@ -442,12 +485,12 @@
         }
         if (nsurv >= msel) {                                     // a shorter list for the exact keys (every true member is in it)
           fellback = 2;
-          if (!all) total = nsurv;
-          else if (2 * nsurv <= n_use) { all = false; total = nsurv; ckey = dkey + nsurv; }
+          if (!ST_IS(ST_ALL)) total = nsurv;
+          else if (2 * nsurv <= n_use) { ST_PUT(ST_ALL, false); total = nsurv; ckey = dkey + nsurv; }
           else total = n_use;                                    // (still most of the slice: exact keys for every point, in place)
-        } else if (all) total = n_use;
+        } else if (ST_IS(ST_ALL)) total = n_use;
       }
-      if (!decided && !overflow) {                               // (a list that fitted anyway and an uncalibrated band: as without the filter)
+      if (!decided && !ST_IS(ST_OVERFLOW)) {                               // (a list that fitted anyway and an uncalibrated band: as without the filter)
         if (lane < ntot) sel[lane] = (int)dkey[lane];
         WSYNC();
         ncand = ntot;
@@ -477,21 +520,25 @@
     stage = 1;
     SELP(9);
   }
-  if (audit) {
+  if (ST_IS(ST_HAS_AUDIT)) {
     const unsigned long long vb = __ballot(viol > 0);
     if (vb != 0ull) {                          // rare: the counters are touched only then (and by audit waves)
+      unsigned* audit_g = SEL_KARG(unsigned*, audit);
       int v = viol;
       float wv = worst;
-      for (int o = 32; o > 0; o >>= 1) { v += __shfl_xor(v, o, 64); wv = fmaxf(wv, __shfl_xor(wv, o, 64)); }
+      for (int o = 32; o > 0; o >>= 1) { v += __shfl_xor(v, o, 64); wv = max_nc(wv, __shfl_xor(wv, o, 64)); }
       if (lane == 0) {
-        atomicAdd(audit + 2, (unsigned)v); atomicMax(audit + 3, __float_as_uint(wv));
+        atomicAdd(audit_g + 2, (unsigned)v); atomicMax(audit_g + 3, __float_as_uint(wv));
         // mirror for the host: words 6, 7 of the block hold a pointer to a pinned, host-mapped counter (or null).  The owner
         // polls it without synchronising the device (npa_audit_peek); only this rare path ever writes across the bus
-        unsigned* hp = *reinterpret_cast<unsigned* const*>(audit + 6);
+        unsigned* hp = *reinterpret_cast<unsigned* const*>(audit_g + 6);
         if (hp) __hip_atomic_fetch_add(hp, (unsigned)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
-    if (audit_wave && lane == 0) { atomicAdd(audit + 0, 1u); atomicAdd(audit + 1, (unsigned)(n_use < 32 ? n_use : 32)); }
+    if (ST_IS(ST_AUDIT_WAVE) && lane == 0) {
+      unsigned* audit_g = SEL_KARG(unsigned*, audit);
+      atomicAdd(audit_g + 0, 1u); atomicAdd(audit_g + 1, (unsigned)(n_use < 32 ? n_use : 32));
+    }
   }
   SELP(10);
 #ifdef NPA_SEL_PROF
