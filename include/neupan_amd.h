@@ -507,6 +507,37 @@ int npa_world_scan(int batch, int n_worlds, int c_stride, int s_stride, const do
                    const int32_t *n_circles, const int32_t *n_segments, const npa_scan_params *params,
                    const int32_t *n_beams, int beam_stride, const int32_t *skip,
                    double *ranges, double *beam_vel, int32_t *hit, void *stream);
+
+/* npa_world_scan_noisy (one launch): npa_world_scan with Gaussian bearing and range noise, drawn on the device by the
+ *   counter-based generator of npa_world_behave.  IR-SIM's lidar2d has the switches noise / std / angle_std; its code was
+ *   not available to compare with, so this specification is the project's own.
+ *   Generator.  mix is the splitmix64 finaliser of npa_world_behave; all integer arithmetic is 64-bit wrap-around:
+ *       z = mix(mix(mix(mix(seed + scene) + beam) + draw) + k),   U(seed, scene, beam, draw, k) = (z >> 11) * 2^-53
+ *       g(k0) = sqrt(-2 ln(1 - U(.., k0))) * cos(2 pi U(.., k0 + 1))     (float64; 1 - U is in (0, 1], so |g| < 8.6)
+ *       g_a = g(0),  g_r = g(2)
+ *   The integer part is exact.  ln and cos may differ in the last bits between the host's libm and the device library
+ *   (the device evaluates cospi(2 U)); whatever must be bit-equal between two runs is computed by this one kernel.
+ *   Beam i of scene b uses scene = scene_base + b, beam = i and the call's `draw`.  It is cast along
+ *       ang' = ang + angle_std * g_a          (one multiply, one add, no contraction; ang is npa_world_scan's, bit for bit)
+ *   and the cast is npa_world_scan's: same forms, same tie rule, same culling, same skip.  hit and beam_vel are that cast's.
+ *   A beam that hit (hit >= 0):  ranges = min(max(t + std * g_r, 0) + 0, range_max);  a miss: ranges = range_max exactly,
+ *   without noise (a noisy miss never becomes a phantom point).  The range is reported at the NOMINAL beam i:
+ *   npa_scan_to_points keeps using the nominal angle -- that is what bearing noise means.
+ *   With std == 0 and angle_std == 0 the three outputs are npa_world_scan's bit for bit.  A scene's result does not depend
+ *   on the batch (given scene_base), on n_beams of other scenes, or on the chunking.
+ *   Not IR-SIM's: the generator (IR-SIM draws from numpy's global stream), the clamp to [0, range_max], misses without noise.
+ * NPA_E_ARG (before anything touches a device): everything npa_world_scan refuses; std or angle_std negative or not
+ *   finite; draw < 0; scene_base < 0 (or scene_base + batch beyond an int).
+ *
+ * npa_scan_noise_draws (HOST, no device): out [n][2] f64 = (g_a, g_r) of the beams first_beam .. first_beam + n - 1 of
+ *   `scene` and `draw`.  NPA_E_ARG: scene, draw, first_beam or n negative, a null out. */
+int npa_world_scan_noisy(int batch, int n_worlds, int c_stride, int s_stride, const double *circles, const double *segments,
+                         const int32_t *n_circles, const int32_t *n_segments, const npa_scan_params *params,
+                         const int32_t *n_beams, int beam_stride, const int32_t *skip,
+                         double *ranges, double *beam_vel, int32_t *hit,
+                         double std, double angle_std, uint64_t seed, int scene_base, int draw, void *stream);
+int npa_scan_noise_draws(uint64_t seed, int scene, int draw, int first_beam, int n, double *out);
+
 int npa_world_step(int batch, int n_worlds, int c_stride, int s_stride, double *circles, double *segments,
                    const int32_t *n_circles, const int32_t *n_segments, double *state, const float *action,
                    const int32_t *frozen, double dt, int kinematics, double wheelbase, const double *bounds,

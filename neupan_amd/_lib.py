@@ -87,6 +87,9 @@ SYMBOLS = {
     "npa_plan_clearance": (_I, [_P, _I, _I, _P, _P, _P, _P, C.c_float, _P, _P, _P, _P, _P]),
     "npa_world_list_capacity": (_I, []),
     "npa_world_scan": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "npa_world_scan_noisy": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, C.c_double, C.c_double, C.c_uint64, _I,
+                                  _I, _P]),
+    "npa_scan_noise_draws": (_I, [C.c_uint64, _I, _I, _I, _I, C.POINTER(C.c_double)]),
     "npa_world_step": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.c_double, _I, C.c_double, C.POINTER(C.c_double), _I,
                             C.POINTER(C.c_double), _I, _P, _P]),
     "npa_behave_list_capacity": (_I, []),

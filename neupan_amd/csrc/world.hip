@@ -1,7 +1,8 @@
 // A lidar world on the device (gfx950 only): what the reference gets from its simulator in example/run_exp.py --
 // env.get_lidar_scan() and env.step(action) -- for B robots at once, handle-free and stream-ordered like frontend.hip.
 //   world_scan_kernel       ray-casts every beam of every robot against the circles and segments of its world; the outputs are
-//                           the ranges / beam velocities npa_scan_to_points takes (neupan.py:173-281 is the consumer)
+//                           the ranges / beam velocities npa_scan_to_points takes (neupan.py:173-281 is the consumer);
+//                           <true>: with Gaussian bearing and range noise (scan_noise.h), npa_world_scan_noisy
 //   world_move_kernel       plant step (motion_predict_model, initial_path.py:388-444, in the float32 / float64 mix nominal_kernel
 //                           uses), translation of the moving primitives, the robots' own edges written as moving segments
 //   world_clearance_kernel  exact signed distance of every robot's polygon to the nearest primitive of its world
@@ -15,6 +16,7 @@
 #include <cmath>
 
 #include "handle.h"
+#include "scan_noise.h"
 
 namespace {
 
@@ -39,16 +41,26 @@ __device__ __forceinline__ int compact_slot(bool keep, int lane, int wv, int* wa
   return off + before;
 }
 
+// the noisy scan's by-value scalars: the levels, and what selects the draws (scene = scene_base + blockIdx.y)
+struct ScanNoise {
+  double std, angle_std;
+  unsigned long long seed;
+  int scene_base, draw;
+};
+
 // One workgroup per (scene, tile of WS_THREADS beams).  Per chunk of WS_CAP primitives: phase 1, thread = primitive, culls
 // against the sensor's reach and compacts the survivors, in index order and already reduced to what a beam needs of them,
 // into LDS; phase 2, thread = beam, every lane walks the same list (broadcast reads).  Circles first, then segments: the walk
 // is in primitive-index order and a lane's best changes only on t < best, so ties stay with the lowest index.  Every loop is
 // wave-uniform; what depends on the lane is a select.
+// NOISE (npa_world_scan_noisy): the beam is cast along ang + angle_std g_a and a hit's range becomes t + std g_r, clamped to
+// [0, range_max]; the draws are per lane and straight-line (scan_noise.h).  The plain instantiation compiles none of it.
+template <bool NOISE>
 __global__ __launch_bounds__(WS_THREADS) void world_scan_kernel(
     int n_worlds, int c_stride, int s_stride, const double* __restrict__ circles, const double* __restrict__ segments,
     const int* __restrict__ n_circles, const int* __restrict__ n_segments, const npa_scan_params* __restrict__ params,
     const int* __restrict__ n_beams, int beam_stride, const int* __restrict__ skip, double* __restrict__ ranges,
-    double* __restrict__ beam_vel, int* __restrict__ hit) {
+    double* __restrict__ beam_vel, int* __restrict__ hit, ScanNoise Z) {
   __shared__ double l0[WS_CAP], l1[WS_CAP], l2[WS_CAP], l3[WS_CAP], l4[WS_CAP];
   __shared__ int lidx[WS_CAP];
   __shared__ int wave_tot[WS_THREADS / 64];
@@ -74,7 +86,14 @@ __global__ __launch_bounds__(WS_THREADS) void world_scan_kernel(
   const bool live = i < n;
   const int ii = live ? i : n - 1;
   const double step = n > 1 ? (P.angle_max - P.angle_min) / (double)(n - 1) : 0.0;
-  const double ang = (n > 1 && ii == n - 1) ? P.angle_max : (double)ii * step + P.angle_min;
+  double ang = (n > 1 && ii == n - 1) ? P.angle_max : (double)ii * step + P.angle_min;
+  double g_r = 0.0;
+  if constexpr (NOISE) {
+    double g_a;
+    npa_noise::draws(Z.seed, Z.scene_base + b, ii, Z.draw, g_a, g_r);
+    const double turn = Z.angle_std * g_a;
+    ang = Z.angle_std != 0.0 ? ang + turn : ang;               // (angle_std == 0: the angle's own bits, a zero's sign included)
+  }
   const double lx = cos(ang), ly = sin(ang);
   const double tx = sc * lx + (-ss) * ly, ty = ss * lx + sc * ly;
   const double dx = rc * tx + (-rsn) * ty, dy = rsn * tx + rc * ty;
@@ -156,6 +175,11 @@ __global__ __launch_bounds__(WS_THREADS) void world_scan_kernel(
     __syncthreads();
   }
 
+  if constexpr (NOISE) {                                       // a miss stays range_max: no phantom point
+    const double v = best + Z.std * g_r;
+    const double p = (v > 0.0 ? v : 0.0) + 0.0;                // (+ 0: no negative zero)
+    best = bi >= 0 ? (p < rmax ? p : rmax) : rmax;
+  }
   if (live) {
     ranges[(size_t)b * beam_stride + i] = best;
     if (hit) hit[(size_t)b * beam_stride + i] = bi;
@@ -367,10 +391,42 @@ extern "C" int npa_world_scan(int batch, int n_worlds, int c_stride, int s_strid
     return fail(NPA_E_ARG, "npa_world_scan: bad argument");
   if (n_worlds != 1 && n_worlds != batch) return fail(NPA_E_ARG, "npa_world_scan: n_worlds must be 1 or batch");
   if (batch > 65535) return fail(NPA_E_ARG, "npa_world_scan: batch above 65535");
-  hipLaunchKernelGGL(world_scan_kernel, dim3((beam_stride + WS_THREADS - 1) / WS_THREADS, batch), dim3(WS_THREADS), 0,
+  hipLaunchKernelGGL(world_scan_kernel<false>, dim3((beam_stride + WS_THREADS - 1) / WS_THREADS, batch), dim3(WS_THREADS), 0,
                      (hipStream_t)stream, n_worlds, c_stride, s_stride, circles, segments, n_circles, n_segments, params,
-                     n_beams, beam_stride, skip, ranges, beam_vel, hit);
+                     n_beams, beam_stride, skip, ranges, beam_vel, hit, ScanNoise{});
   HIP_TRY(hipGetLastError());
+  return NPA_OK;
+}
+
+static bool noise_level_ok(double x) { return x >= 0.0 && std::isfinite(x); }
+
+extern "C" int npa_world_scan_noisy(int batch, int n_worlds, int c_stride, int s_stride, const double* circles,
+                                    const double* segments, const int32_t* n_circles, const int32_t* n_segments,
+                                    const npa_scan_params* params, const int32_t* n_beams, int beam_stride,
+                                    const int32_t* skip, double* ranges, double* beam_vel, int32_t* hit, double std,
+                                    double angle_std, uint64_t seed, int scene_base, int draw, void* stream) {
+  if (batch <= 0 || beam_stride <= 0 || c_stride < 0 || s_stride < 0 || !params || !ranges || !n_circles || !n_segments ||
+      (c_stride > 0 && !circles) || (s_stride > 0 && !segments))
+    return fail(NPA_E_ARG, "npa_world_scan_noisy: bad argument");
+  if (n_worlds != 1 && n_worlds != batch) return fail(NPA_E_ARG, "npa_world_scan_noisy: n_worlds must be 1 or batch");
+  if (batch > 65535) return fail(NPA_E_ARG, "npa_world_scan_noisy: batch above 65535");
+  if (!noise_level_ok(std) || !noise_level_ok(angle_std))
+    return fail(NPA_E_ARG, "npa_world_scan_noisy: std and angle_std must be finite and >= 0");
+  if (draw < 0 || scene_base < 0 || scene_base > 0x7fffffff - batch)
+    return fail(NPA_E_ARG, "npa_world_scan_noisy: draw and scene_base must be >= 0 (and scene_base + batch an int)");
+  ScanNoise Z;
+  Z.std = std; Z.angle_std = angle_std; Z.seed = seed; Z.scene_base = scene_base; Z.draw = draw;
+  hipLaunchKernelGGL(world_scan_kernel<true>, dim3((beam_stride + WS_THREADS - 1) / WS_THREADS, batch), dim3(WS_THREADS), 0,
+                     (hipStream_t)stream, n_worlds, c_stride, s_stride, circles, segments, n_circles, n_segments, params,
+                     n_beams, beam_stride, skip, ranges, beam_vel, hit, Z);
+  HIP_TRY(hipGetLastError());
+  return NPA_OK;
+}
+
+extern "C" int npa_scan_noise_draws(uint64_t seed, int scene, int draw, int first_beam, int n, double* out) {
+  if (scene < 0 || draw < 0 || first_beam < 0 || n < 0 || !out || first_beam > 0x7fffffff - n)
+    return fail(NPA_E_ARG, "npa_scan_noise_draws: bad argument");
+  for (int k = 0; k < n; ++k) npa_noise::draws(seed, scene, first_beam + k, draw, out[2 * k], out[2 * k + 1]);
   return NPA_OK;
 }
 

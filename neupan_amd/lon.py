@@ -459,7 +459,9 @@ class LonLoop(ResidentLoop):
     def reset(self):
         """Start every robot over -- poses, path state, latches, warm start, stuck counters, the accumulated gradients, the
         planner's state record, the world -- without touching theta, m, v or t (nor, with groups, group_theta, group_m, group_v; the
-        groups' accumulated gradients are cleared too).  copy_ / zero_ / fill_ only."""
+        groups' accumulated gradients are cleared too).  copy_ / zero_ / fill_ only.  With lidar noise (`scan["noise"]`) the
+        draw count is not rewound: every episode sees other noise, and `train_closed_loop` reproduces episode e of n cycles with
+        draw0 + e n."""
         st0, c0, s0, off0, len0 = self._saved
         self.states.copy_(st0)
         self.last_xy.copy_(st0[:, :2])
@@ -488,7 +490,7 @@ def train_closed_loop(fleet, world, states, cycles, theta, opt_state=None, train
 
     `theta`: the (B, 8) float32 device block (`adjust_block`), stepped in place; `opt_state`: what `adam_state` made (m, v, t,
     skipped, bad), carried from episode to episode and updated in place (default: a fresh one).  The other arguments are
-    LonLoop's and run_closed_loop's.  The host reads the device several times per cycle (fleet.forward's bookkeeping, the
+    LonLoop's and run_closed_loop's (`scan["noise"]` included: cycle cyc is draw draw0 + cyc).  The host reads the device several times per cycle (fleet.forward's bookkeeping, the
     gradient chain's flags).  Returns the dict LonLoop.episode returns.
     With `groups` (LonLoop's argument) the tail is lon_reduce -> lon_adam on the G group rows -> lon_scatter: `opt_state` comes
     from `adam_state(G, dev)` (the loop adds "dropped" [G] and "robot_bad" [B] to it; its "bad" is not used), every group

@@ -15,9 +15,13 @@ simulator plays (example/run_exp.py: env.get_lidar_scan() -> scan_to_point -> ne
 There is no CPU fallback: scan and step are the HIP kernels of csrc/world.hip behind the C ABI (include/neupan_amd.h).
 The loops call `behave` between the action and the step when the world has agents; a world without agents issues exactly the
 launches it issued before there were agents.
-What IR-SIM does and this does not: sensor noise, obstacle behaviours other than rvo, obstacle kinematics and heading (every
-agent is a holonomic disc or a translating polygon), rendering.  IR-SIM's rvo implementation was not available to compare with:
-the behaviour is the one include/neupan_amd.h specifies from the paper.
+Lidar noise: `LidarWorld.scan(noise=...)` and the loops' `scan` dict (`noise=dict(std, angle_std, seed, draw0)`) add Gaussian
+range and bearing noise drawn on the device (npa_world_scan_noisy; the specification is include/neupan_amd.h's, not IR-SIM's
+code: its generator is numpy's global stream); `scan_from_yaml` reads a robot's `lidar2d` block.  Without noise the loops
+issue exactly the launches they issued before.
+What IR-SIM does and this does not: lidar dropouts, per-robot noise levels, pose and odometry noise, obstacle behaviours other
+than rvo, obstacle kinematics and heading (every agent is a holonomic disc or a translating polygon), rendering.  IR-SIM's rvo
+implementation was not available to compare with: the behaviour is the one include/neupan_amd.h specifies from the paper.
 """
 from __future__ import annotations
 
@@ -120,6 +124,32 @@ def _scan_block(st, angle_min, angle_max, range_min, range_max, scan_offset, dev
     par[:, 4:7] = st
     par[:, 7:10] = torch.from_numpy(np.broadcast_to(np.asarray(scan_offset, dtype=np.float64), (B, 3)).copy()).to(device)
     return par
+
+
+NOISE = dict(std=0.0, angle_std=0.0, seed=0, draw0=0)
+
+
+def _noise_fields(noise, keys=("std", "angle_std", "seed", "draw0")):
+    """a `noise` argument over its defaults, checked: dict(std, angle_std, seed, draw0), or None when there is no noise to add
+    (None, or both levels zero).  std [m] and angle_std [rad] must be finite and >= 0, seed and draw0 integers, draw0 >= 0."""
+    if noise is None:
+        return None
+    if not isinstance(noise, dict):
+        raise TypeError("noise must be None or a dict(std, angle_std, seed, draw0)")
+    unknown = set(noise) - set(keys)
+    if unknown:
+        raise TypeError(f"unknown noise parameters {sorted(unknown)} (known: {list(keys)})")
+    out = dict(NOISE)
+    for k in ("std", "angle_std"):
+        v = float(noise.get(k, 0.0))
+        if not (v >= 0.0 and v != float("inf")):
+            raise ValueError(f"noise: {k} must be finite and >= 0, not {v}")
+        out[k] = v
+    out["seed"] = int(noise.get("seed", 0)) & _M64
+    out["draw0"] = int(noise.get("draw0", 0))
+    if out["draw0"] < 0:
+        raise ValueError("noise: draw0 must be >= 0")
+    return out if (out["std"] > 0.0 or out["angle_std"] > 0.0) else None
 
 
 class LidarWorld:
@@ -429,14 +459,22 @@ class LidarWorld:
                 raise ValueError(f"{what} must be contiguous")
         return R
 
-    def scan(self, states, n_beams, angle_min, angle_max, range_min, range_max, scan_offset=(0.0, 0.0, 0.0), out=None):
+    def scan(self, states, n_beams, angle_min, angle_max, range_min, range_max, scan_offset=(0.0, 0.0, 0.0), out=None, noise=None,
+             draw=0, scene_base=0):
         """Ray-cast the lidars of B robots.  states [B, 3] (host or device); n_beams an int, or [B] ints (ragged: columns at or
         beyond n_beams[b] are not written; they keep what `out` = (ranges, beam_vel, hit) held, zeros without it).  `out` may
         be wider than the scan, also with an int n_beams: its width is the row stride; a mismatch in shape, dtype, device or
         contiguity is a ValueError.
         Returns (ranges [B, R] f64, beam_vel [B, 2, R] f64, hit [B, R] int32) device tensors: the first two are what
-        scan_to_point_batch / scan_to_point_velocity_batch take.  No host synchronisation."""
+        scan_to_point_batch / scan_to_point_velocity_batch take.  No host synchronisation.
+        noise = dict(std=, angle_std=, seed=0): Gaussian range [m] and bearing [rad] noise (npa_world_scan_noisy: a hit's range
+        is t + std g_r clamped to [0, range_max] along the beam turned by angle_std g_a and reported at the nominal beam; a
+        miss stays range_max); `draw` numbers the scan (the same draw gives the same noise) and robot b is scene
+        scene_base + b of the generator.  None, or both levels zero: npa_world_scan as before."""
         lib, dev = _lib.load(), self.device
+        nz = _noise_fields(noise, ("std", "angle_std", "seed"))
+        if int(draw) < 0 or int(scene_base) < 0:
+            raise ValueError("draw and scene_base must be >= 0")
         st = self._states(states)
         B = st.shape[0]
         if self.W not in (1, B):
@@ -459,9 +497,14 @@ class LidarWorld:
             ranges, vel, hit = out
         c, s, nc, ns = self._upload()
         skip = self.skip if (self.skip is not None and self.skip.shape[0] == B) else None
+        args = (B, self.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par), _ptr(nb), R, _ptr(skip),
+                _ptr(ranges), _ptr(vel), _ptr(hit))
         with torch.cuda.device(dev):
-            check(lib.npa_world_scan(B, self.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par), _ptr(nb),
-                                     R, _ptr(skip), _ptr(ranges), _ptr(vel), _ptr(hit), _stream(dev)), "npa_world_scan")
+            if nz is None:
+                check(lib.npa_world_scan(*args, _stream(dev)), "npa_world_scan")
+            else:
+                check(lib.npa_world_scan_noisy(*args, nz["std"], nz["angle_std"], nz["seed"], int(scene_base), int(draw), _stream(dev)),
+                      "npa_world_scan_noisy")
         return ranges, vel, hit
 
     # ------------------------------------------------------------------ step
@@ -543,15 +586,46 @@ def robot_radius(robot):
 
 
 _SCAN_DEFAULTS = dict(n_beams=100, angle_min=-pi, angle_max=pi, range_min=0.0, range_max=10.0, scan_offset=(0.0, 0.0, 0.0),
-                      angle_range=(-pi, pi), down_sample=1)
+                      angle_range=(-pi, pi), down_sample=1, noise=None)
 _LIMITS = ("angle_min", "angle_max", "range_min", "range_max")
 _LOG_ORDER = ("actions", "stop", "controls", "n_points", "states", "clearance")      # as npa_cycle_act, then npa_cycle_commit take them
 
 
 def _scan_fields(scan):
     """the loops' `scan` argument over the defaults: 100 beams over (-pi, pi), 0 .. 10 m (the example environments' sensor), no
-    offset, every beam kept"""
-    return dict(_SCAN_DEFAULTS, **(scan or {}))
+    offset, every beam kept, no noise.  `noise` (None | dict(std, angle_std, seed=0, draw0=0)) comes back checked
+    (`_noise_fields`): None when there is no noise to add"""
+    sp = dict(_SCAN_DEFAULTS, **(scan or {}))
+    sp["noise"] = _noise_fields(sp["noise"])
+    return sp
+
+
+def scan_from_yaml(env_yaml, robot=0):
+    """The loops' `scan` dict from the first `lidar2d` of robot number `robot`'s `sensors:` list in an IR-SIM environment file:
+    n_beams = number, range_min, range_max, angle_min / angle_max = -+ angle_range / 2 (angle_range of the cloud the same),
+    scan_offset = `offset` if present, and noise: `noise: False` (or absent) gives noise=None, else dict(std, angle_std, seed=0,
+    draw0=0) from `std` / `angle_std`.  The defaults of the fields a file leaves out (number 100, range 0 .. 10 m, angle_range
+    pi, std 0.2, angle_std 0.02) are written from memory of IR-SIM, which was not available to check against."""
+    import yaml
+    with open(env_yaml) as f:
+        doc = yaml.safe_load(f)
+    robots = doc.get("robot") or []
+    robots = [robots] if isinstance(robots, dict) else list(robots)
+    if not 0 <= int(robot) < len(robots):
+        raise ValueError(f"scan_from_yaml: robot {robot} of {len(robots)}")
+    lidar = next((x for x in (robots[int(robot)].get("sensors") or []) if (x.get("type") or x.get("name")) == "lidar2d"), None)
+    if lidar is None:
+        raise ValueError(f"scan_from_yaml: robot {robot} has no lidar2d sensor")
+    half = 0.5 * float(lidar.get("angle_range", pi))
+    off = [float(x) for x in (lidar.get("offset") or (0.0, 0.0, 0.0))]
+    off = tuple(off + [0.0] * (3 - len(off)))[:3]
+    noise = None
+    if lidar.get("noise", False):
+        noise = dict(std=float(lidar.get("std", 0.2)), angle_std=float(lidar.get("angle_std", 0.02)), seed=0, draw0=0)
+    sp = dict(n_beams=int(lidar.get("number", 100)), angle_min=-half, angle_max=half, range_min=float(lidar.get("range_min", 0.0)),
+              range_max=float(lidar.get("range_max", 10.0)), scan_offset=off, angle_range=(-half, half), down_sample=1, noise=noise)
+    _scan_fields(sp)                               # (checked here: a bad file fails at the read, not in a loop)
+    return sp
 
 
 def _run_logs(cycles, B, T, device):
@@ -585,6 +659,7 @@ class _HostCycle:
         self.collided = torch.zeros((B,), dtype=torch.bool, device=dev)
         self.arrive = torch.zeros((B,), dtype=torch.bool, device=dev)
         self._beams, self._limits, self._offset = sp["n_beams"], tuple(sp[k] for k in _LIMITS), sp["scan_offset"]
+        self._noise = sp["noise"]                               # (cycle cyc is draw draw0 + cyc of the generator, robot b scene b)
         self._to_points = dict(scan_offset=sp["scan_offset"], angle_range=sp["angle_range"], down_sample=sp["down_sample"],
                                max_points=max_points, device=dev)
         self.prev, self.radius = (torch.empty_like(self.st), robot_radius(fleet.robot)) if world.has_agents else (None, 0.0)
@@ -596,7 +671,12 @@ class _HostCycle:
         at the top and handed to it as a host array."""
         fleet, world, st, logs = self.fleet, self.world, self.st, self.logs
         st_h = st.cpu().numpy()                                 # (the cycle's one read of the poses: forward needs them on the host)
-        ranges, bvel, _ = world.scan(st, self._beams, *self._limits, self._offset)
+        nz = self._noise
+        if nz is None:
+            ranges, bvel, _ = world.scan(st, self._beams, *self._limits, self._offset)
+        else:
+            ranges, bvel, _ = world.scan(st, self._beams, *self._limits, self._offset, noise=dict(std=nz["std"], angle_std=nz["angle_std"],
+                                                                                                 seed=nz["seed"]), draw=nz["draw0"] + cyc)
         if self.point_velocities:
             pts, pvel, npts = scan_to_point_velocity_batch(st_h, ranges, *self._limits, velocities=bvel, **self._to_points)
         else:
@@ -672,7 +752,10 @@ def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=Fa
         scan (LidarWorld.scan) -> scan_to_point[_velocity]_batch -> fleet.forward -> LidarWorld.step
 
     `scan`: dict(n_beams, angle_min, angle_max, range_min, range_max[, scan_offset, angle_range, down_sample]) -- the fields of
-    the reference's lidar message; default 100 beams over (-pi, pi), 0 .. 10 m (the example environments' sensor).
+    the reference's lidar message; default 100 beams over (-pi, pi), 0 .. 10 m (the example environments' sensor).  Its `noise`
+    (None | dict(std, angle_std, seed=0, draw0=0)) adds lidar noise (`LidarWorld.scan`): cycle cyc is draw draw0 + cyc, robot b
+    scene b, so ResidentLoop and this loop see the same noise bit for bit, and draw0 = n continues a run of n cycles.
+    `scan_from_yaml` makes the dict from an environment file.
     point_velocities=True feeds the hit primitives' velocities (scan_to_point_velocity, neupan.py:224-281); certify=True asks
     `forward` for the plan's exact clearance; peers=True makes the robots see each other (one shared world).  A robot is frozen
     once it has arrived or once its world clearance is <= 0 (IR-SIM's collision_mode: stop).  `actions` [cycles, B, 2]
@@ -777,6 +860,9 @@ class ResidentLoop:
     path_capacity) rows.  A curve that does not fit leaves the robot arrived (retask_status 2).  Every robot's initial path must
     then be a single curve.  Without goals the table and the launches are what they were; attributes goal_index, retask_status
     [B] int32 (None without goals), and `run` adds logs["goal"] [cycles, B] int32: the goals consumed after each cycle.
+
+    With `scan["noise"]` the scan slot holds npa_world_scan_noisy with draw = draw0 + cycles_done, a host scalar at issue time;
+    the count runs on over runs (and over `LonLoop.reset`: episodes see different noise).  Without it the launch is npa_world_scan.
 
     The arguments are `run_closed_loop`'s.  `fleet` must be fresh from `set_paths` (its host bookkeeping -- curve_index, arrived,
     cur_vel -- is not used again: this object owns the device copy, and `fleet.forward` must not be mixed in until the next
@@ -899,14 +985,22 @@ class ResidentLoop:
         self.action, self.stop = zeros((B, 2), torch.float32), zeros((B,), torch.uint8)
         self.frozen, self.clearance = zeros((B,), torch.int32), empty((B,), torch.float64)
         path_d, off_d, len_d, first_d = self._table
+        # the scan slot: with noise, npa_world_scan_noisy over the same arguments; its draw number is a host scalar read at
+        # issue time (`_scan_noisy`), like the log row -- no buffer, no synchronisation
+        self._noise = sp["noise"]
+        scan_args = (B, world.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par_w), _ptr(nb), R, _ptr(skip),
+                     _ptr(self.ranges), _ptr(self.beam_vel), _ptr(self.hit))
+        if self._noise is None:
+            scan_slot = ("npa_world_scan", lib.npa_world_scan, scan_args)
+        else:
+            nz = self._noise
+            scan_slot = ("npa_world_scan_noisy", self._scan_noisy, scan_args + (nz["std"], nz["angle_std"], nz["seed"], 0))
         self._front = (
             ("npa_cycle_progress", lib.npa_cycle_progress,
              (B, _ptr(st), _ptr(path_d), _ptr(off_d), _ptr(len_d), _ptr(first_d), 1 if fleet.loop else 0, fleet.close_threshold,
               fleet.ind_range, fleet.arrive_threshold, fleet.arrive_index_threshold, _ptr(self.curve_index), _ptr(self.cur_off),
               _ptr(self.cur_len), _ptr(self.point_index), _ptr(self._curve_arrived), _ptr(self.arrived), _ptr(par_w), _ptr(par_s))),
-            ("npa_world_scan", lib.npa_world_scan,
-             (B, world.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par_w), _ptr(nb), R, _ptr(skip),
-              _ptr(self.ranges), _ptr(self.beam_vel), _ptr(self.hit))),
+            scan_slot,
             ("npa_scan_to_points", lib.npa_scan_to_points,
              (B, R, _ptr(self.ranges), _ptr(self.beam_vel) if point_velocities else None, None, _ptr(par_s),
               1 if point_velocities else 0, N, _ptr(self.points), _ptr(self.point_velocities), _ptr(self.n_points))),
@@ -942,6 +1036,11 @@ class ResidentLoop:
         fleet.cur_vel = self.cur_vel                 # (the fleet has planned from here on: a second loop needs set_paths)
 
     # ------------------------------------------------------------------ one cycle, in four steps
+    def _scan_noisy(self, *args):
+        """the noisy scan of the cycle being issued: draw draw0 + cycles_done (scene_base 0: robot b is scene b), so a second
+        run continues the sequence and `LonLoop.reset` does not rewind it; args: the slot's, then the stream"""
+        return self._lib.npa_world_scan_noisy(*args[:-1], self._noise["draw0"] + self.cycles_done, args[-1])
+
     def _front_step(self):
         """the workspace check, then the launches in front of the plan; returns the cycle's stream"""
         pan = self.fleet.pan
