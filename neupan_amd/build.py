@@ -1,6 +1,6 @@
-"""Build libneupan_amd.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libneupan_amd.so and libneupan_amd_train.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-    python -m neupan_amd.build            # also invoked by __graft_entry__.build()
+    python -m neupan_amd.build            # both libraries; also invoked by __graft_entry__.build()
 """
 from __future__ import annotations
 
@@ -89,5 +89,47 @@ def build(force=False, verbose=True):
     return LIB
 
 
+# The training library (include/neupan_amd_train.h): a library of its own, because libneupan_amd.so is held below 2 MiB
+# (tests/test_abi.py) and has no room for another kernel.  Same flags, same compiler refusal, same stripped link.
+TRAIN_SOURCES = ["dune_train.hip"]
+TRAIN_LIB = os.path.join(HERE, "libneupan_amd_train.so")
+TRAIN_OBJ = os.path.join(HERE, "_obj")      # (not csrc/: needs_build() takes every file there for a source of the main library)
+
+
+def needs_build_train():
+    if not os.path.exists(TRAIN_LIB):
+        return True
+    t = os.path.getmtime(TRAIN_LIB)
+    deps = [os.path.join(CSRC, f) for f in TRAIN_SOURCES] + [os.path.join(HERE, "..", "include", f)
+                                                             for f in ("neupan_amd_train.h", "neupan_amd.h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_train(force=False, verbose=True):
+    if not force and not needs_build_train():
+        return TRAIN_LIB
+    ver = hipcc_version()
+    if not ver.startswith(VALIDATED_HIPCC):
+        msg = f"neupan_amd.build: hipcc {ver} is not the validated {VALIDATED_HIPCC} (DESIGN.md section 1)"
+        if os.environ.get("NPA_ALLOW_UNVALIDATED") != "1":
+            raise UnvalidatedCompiler(msg + ": set NPA_ALLOW_UNVALIDATED=1 to build anyway, then run the -m gpu suite")
+        print(msg + ": building because NPA_ALLOW_UNVALIDATED=1 -- run the -m gpu suite before trusting it", file=sys.stderr)
+    objs = []
+    os.makedirs(TRAIN_OBJ, exist_ok=True)
+    for src in TRAIN_SOURCES:
+        obj = os.path.join(TRAIN_OBJ, src.replace(".hip", ".o"))
+        cmd = [hipcc_path(), *FLAGS, f'-DNPA_HIPCC_VERSION="{ver}"', "-c", os.path.join(CSRC, src), "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        objs.append(obj)
+    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--strip-all", *objs, "-o", TRAIN_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return TRAIN_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
+    build_train(force="--force" in sys.argv)
