@@ -1,6 +1,7 @@
-"""Build libneupan_amd.so and libneupan_amd_train.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
+"""Build libneupan_amd.so, libneupan_amd_train.so and libneupan_amd_grid.so in-tree with hipcc for gfx950 (cross-compiles
+without a GPU).
 
-    python -m neupan_amd.build            # both libraries; also invoked by __graft_entry__.build()
+    python -m neupan_amd.build            # the three libraries; also invoked by __graft_entry__.build()
 """
 from __future__ import annotations
 
@@ -130,6 +131,48 @@ def build_train(force=False, verbose=True):
     return TRAIN_LIB
 
 
+# The occupancy-grid library (include/neupan_amd_grid.h): a library of its own for the same reason.  Same flags, same compiler
+# refusal, same stripped link; scan_beam.h and scan_noise.h are the headers it shares with world.hip of the main library.
+GRID_SOURCES = ["grid.hip"]
+GRID_LIB = os.path.join(HERE, "libneupan_amd_grid.so")
+GRID_HEADERS = ["scan_beam.h", "scan_noise.h"]
+
+
+def needs_build_grid():
+    if not os.path.exists(GRID_LIB):
+        return True
+    t = os.path.getmtime(GRID_LIB)
+    deps = [os.path.join(CSRC, f) for f in GRID_SOURCES + GRID_HEADERS] + [os.path.join(HERE, "..", "include", f)
+                                                                            for f in ("neupan_amd_grid.h", "neupan_amd.h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def build_grid(force=False, verbose=True):
+    if not force and not needs_build_grid():
+        return GRID_LIB
+    ver = hipcc_version()
+    if not ver.startswith(VALIDATED_HIPCC):
+        msg = f"neupan_amd.build: hipcc {ver} is not the validated {VALIDATED_HIPCC} (DESIGN.md section 1)"
+        if os.environ.get("NPA_ALLOW_UNVALIDATED") != "1":
+            raise UnvalidatedCompiler(msg + ": set NPA_ALLOW_UNVALIDATED=1 to build anyway, then run the -m gpu suite")
+        print(msg + ": building because NPA_ALLOW_UNVALIDATED=1 -- run the -m gpu suite before trusting it", file=sys.stderr)
+    objs = []
+    os.makedirs(TRAIN_OBJ, exist_ok=True)
+    for src in GRID_SOURCES:
+        obj = os.path.join(TRAIN_OBJ, src.replace(".hip", ".o"))
+        cmd = [hipcc_path(), *FLAGS, f'-DNPA_HIPCC_VERSION="{ver}"', "-c", os.path.join(CSRC, src), "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+        objs.append(obj)
+    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--strip-all", *objs, "-o", GRID_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return GRID_LIB
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_train(force="--force" in sys.argv)
+    build_grid(force="--force" in sys.argv)

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "handle.h"
+#include "scan_beam.h"
 #include "scan_noise.h"
 
 namespace {
@@ -78,15 +79,13 @@ __global__ __launch_bounds__(WS_THREADS) void world_scan_kernel(
   const double* sw = segments + (size_t)w * s_stride * 6;
 
   // sensor pose = state o offset, and the beam's direction, composed as scan_kernel composes a point
-  const double sc = cos(P.offset[2]), ss = sin(P.offset[2]);
-  const double rc = cos(P.state[2]), rsn = sin(P.state[2]);
-  const double ox = (rc * P.offset[0] + (-rsn) * P.offset[1]) + P.state[0];
-  const double oy = (rsn * P.offset[0] + rc * P.offset[1]) + P.state[1];
+  // (scan_beam.h: the occupancy-grid scan of libneupan_amd_grid.so starts and points its beams with the same code)
+  const npa_beam::Sensor S = npa_beam::sensor(P);
+  const double ox = S.ox, oy = S.oy;
   const int i = (int)blockIdx.x * WS_THREADS + tid;
   const bool live = i < n;
   const int ii = live ? i : n - 1;
-  const double step = n > 1 ? (P.angle_max - P.angle_min) / (double)(n - 1) : 0.0;
-  double ang = (n > 1 && ii == n - 1) ? P.angle_max : (double)ii * step + P.angle_min;
+  double ang = npa_beam::angle(P, n, ii);
   double g_r = 0.0;
   if constexpr (NOISE) {
     double g_a;
@@ -94,9 +93,8 @@ __global__ __launch_bounds__(WS_THREADS) void world_scan_kernel(
     const double turn = Z.angle_std * g_a;
     ang = Z.angle_std != 0.0 ? ang + turn : ang;               // (angle_std == 0: the angle's own bits, a zero's sign included)
   }
-  const double lx = cos(ang), ly = sin(ang);
-  const double tx = sc * lx + (-ss) * ly, ty = ss * lx + sc * ly;
-  const double dx = rc * tx + (-rsn) * ty, dy = rsn * tx + rc * ty;
+  double dx, dy;
+  npa_beam::direction(S, ang, dx, dy);
   const double rmax = P.range_max;
   const double reach2 = (rmax * rmax) * WS_CULL_SLACK;
 

@@ -19,6 +19,9 @@ QP and takes an Adam step; the episode ends on arrive, stop or stuck.  Here:
       + for k = K-1 .. first: npa_nrmp_backward(snapshot k, gs, gu, gd) -> npa_lon_chain(k)
       + npa_lon_adam(t)
 
+  (a world with an occupancy grid, `LidarWorld.set_map`: npa_grid_scan behind the scan and npa_grid_clearance in front of the
+  commit, inherited with the front and the tail)
+
   With `groups` a parameter row is shared by a group of robots and trained from the rollouts of all of them -- the reference's
   one tuned set, at scale.  The tail of the cycle is then
 

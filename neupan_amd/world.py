@@ -19,6 +19,11 @@ Lidar noise: `LidarWorld.scan(noise=...)` and the loops' `scan` dict (`noise=dic
 range and bearing noise drawn on the device (npa_world_scan_noisy; the specification is include/neupan_amd.h's, not IR-SIM's
 code: its generator is numpy's global stream); `scan_from_yaml` reads a robot's `lidar2d` block.  Without noise the loops
 issue exactly the launches they issued before.
+Occupancy grids: `LidarWorld.set_map(GridMap, reach)` puts a map (neupan_amd.gridmap; include/neupan_amd_grid.h) behind the
+primitives: every scan is followed by npa_grid_scan, which merges the map's ranges into it (hit = -2 where the map is nearer),
+every step that measures a clearance by npa_grid_clearance, exact up to `reach`; the loops do the same.  A world without a map
+issues exactly the launches it issued before.  The RVO agents and the moving circles do not see the map, and
+`PAN.plan_clearance` / certify judge a plan against the cloud, as before.
 What IR-SIM does and this does not: lidar dropouts, per-robot noise levels, pose and odometry noise, obstacle behaviours other
 than rvo, obstacle kinematics and heading (every agent is a holonomic disc or a translating polygon), rendering.  IR-SIM's rvo
 implementation was not available to compare with: the behaviour is the one include/neupan_amd.h specifies from the paper.
@@ -32,7 +37,7 @@ from math import cos, pi, sin
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _lib_grid
 from ._lib import KIN, NeupanAmdError, NpaBehaveParams, check
 from .frontend import _SCAN_DTYPE, _bcast, _ptr, _scan_params, _stream, scan_to_point_batch, scan_to_point_velocity_batch
 
@@ -179,6 +184,7 @@ class LidarWorld:
         self._na = np.zeros(W, dtype=np.int32)
         self._adev, self._held_by_loop = None, False
         self.behaviour = dict(BEHAVIOUR)
+        self._grid, self._grid_reach = None, 1.0       # the occupancy grid behind the primitives (set_map), none by default
 
     # ------------------------------------------------------------------ building
     def add_polygon(self, vertices, velocity=(0.0, 0.0)):
@@ -196,6 +202,39 @@ class LidarWorld:
             self._ns[w] = n + len(seg)
         self._s = s
         return first
+
+    def set_map(self, grid, reach=1.0):
+        """Put an occupancy grid (neupan_amd.gridmap.GridMap) behind the primitives of the (every) world, or remove it (None).
+        Scans then see its occupied cells (hit = -2, velocity 0) and the clearance of `step` and of the loops counts them,
+        exactly where it is <= `reach` [m]: cells farther than that from a robot are not looked at.  The map is static and
+        shared by every world; agents and moving circles do not see it.  A loop made before this call keeps the map it was
+        made with."""
+        if grid is None:
+            self._grid = None
+            return
+        from .gridmap import GridMap
+        if not isinstance(grid, GridMap):
+            raise TypeError("set_map: a GridMap or None")
+        cells = grid.cells
+        if not (isinstance(cells, torch.Tensor) and cells.dtype == torch.uint8 and cells.dim() == 2 and cells.is_contiguous()
+                and cells.numel() > 0):
+            raise ValueError("set_map: the map's cells must be a contiguous uint8 tensor [ny, nx]")
+        if cells.device.type != self.device.type or (self.device.index is not None and cells.device.index != self.device.index):
+            raise ValueError(f"set_map: the map is on {cells.device}, the world on {self.device}")
+        reach = float(reach)
+        if not (reach > 0.0 and reach != float("inf")):
+            raise ValueError(f"set_map: reach must be positive and finite, not {reach}")
+        self._grid, self._grid_reach = grid, reach
+
+    @property
+    def grid(self):
+        """the occupancy grid (`set_map`), or None"""
+        return self._grid
+
+    def _grid_args(self):
+        """the map as npa_grid_scan and npa_grid_clearance take it: cells, nx, ny, x0, y0, res"""
+        g = self._grid
+        return (_ptr(g.cells), int(g.cells.shape[1]), int(g.cells.shape[0]), g.origin[0], g.origin[1], g.resolution)
 
     def add_agents(self, first, count=1, v_max=1.0, goal_threshold=0.1, wander=False, goals=None, **behaviour):
         """Make primitives of every world agents: they choose their velocity in every `behave` call (npa_world_behave).
@@ -470,7 +509,9 @@ class LidarWorld:
         noise = dict(std=, angle_std=, seed=0): Gaussian range [m] and bearing [rad] noise (npa_world_scan_noisy: a hit's range
         is t + std g_r clamped to [0, range_max] along the beam turned by angle_std g_a and reported at the nominal beam; a
         miss stays range_max); `draw` numbers the scan (the same draw gives the same noise) and robot b is scene
-        scene_base + b of the generator.  None, or both levels zero: npa_world_scan as before."""
+        scene_base + b of the generator.  None, or both levels zero: npa_world_scan as before.
+        With a map (`set_map`) npa_grid_scan follows on the same stream, with the same noise arguments: where the map is nearer
+        than every primitive the range is the map's, hit -2 and the velocity 0."""
         lib, dev = _lib.load(), self.device
         nz = _noise_fields(noise, ("std", "angle_std", "seed"))
         if int(draw) < 0 or int(scene_base) < 0:
@@ -505,6 +546,11 @@ class LidarWorld:
             else:
                 check(lib.npa_world_scan_noisy(*args, nz["std"], nz["angle_std"], nz["seed"], int(scene_base), int(draw), _stream(dev)),
                       "npa_world_scan_noisy")
+            if self._grid is not None:
+                z = nz or NOISE
+                _lib_grid.check(_lib_grid.load().npa_grid_scan(*self._grid_args(), B, _ptr(par), _ptr(nb), R, _ptr(ranges), _ptr(vel),
+                                                               _ptr(hit), z["std"], z["angle_std"], z["seed"], int(scene_base),
+                                                               int(draw), _stream(dev)), "npa_grid_scan")
         return ranges, vel, hit
 
     # ------------------------------------------------------------------ step
@@ -542,6 +588,9 @@ class LidarWorld:
                                      _ptr(frozen), float(dt), KIN[kinematics], float(wheelbase or 0.0), self.bounds,
                                      0 if V is None else len(V), vp, self.peer_base if peers else -1, _ptr(clr), _stream(dev)),
                   "npa_world_step")
+            if clr is not None and self._grid is not None:
+                _lib_grid.check(_lib_grid.load().npa_grid_clearance(*self._grid_args(), B, _ptr(st), len(V), vp, self._grid_reach,
+                                                                    _ptr(clr), _stream(dev)), "npa_grid_clearance")
         return clr
 
     def step(self, states, actions, dt, kinematics, wheelbase=0.0, frozen=None, robot_vertices=None, peers=False):
@@ -549,7 +598,8 @@ class LidarWorld:
         is advanced IN PLACE when it is a float64 device tensor [B, 3] (else a device copy is); `frozen` [B]: robots that stay.
         robot_vertices [E, 2] (robot frame, counter-clockwise) gives the second result, the exact signed distance of every
         robot's polygon to the nearest primitive after the move (<= 0: collided), else None; peers=True additionally writes
-        the robots' edges into the tail `set_peers` made.  Returns (states, clearance).  No host synchronisation."""
+        the robots' edges into the tail `set_peers` made.  With a map (`set_map`) the clearance also counts its occupied cells
+        (npa_grid_clearance behind npa_world_step).  Returns (states, clearance).  No host synchronisation."""
         if kinematics not in KIN:
             raise ValueError("kinematics must be one of diff, acker, omni")
         dev = self.device
@@ -851,6 +901,9 @@ class ResidentLoop:
         -> npa_cycle_act (warm start, stop, action, override, freeze)
         [-> npa_world_behave, when the world has agents] -> npa_world_step -> npa_cycle_commit (collision latch, log rows)
         [-> npa_cycle_retask, when the loop has goals]                                                        (_tail_step)
+    and, when the world has a map (`LidarWorld.set_map`), npa_grid_scan behind the scan and npa_grid_clearance between
+    npa_world_step and npa_cycle_commit (include/neupan_amd_grid.h): the map the world has when the loop is made, held for the
+    loop's lifetime; without a map neither is issued,
     followed by the host's bookkeeping (_finish_step: the planner's last call, `cycles_done`, the audit every 64 cycles).  This is
     the one definition of the resident cycle: `lon.LonLoop` replaces the plan step and adds its own steps around these.
 
@@ -995,12 +1048,27 @@ class ResidentLoop:
         else:
             nz = self._noise
             scan_slot = ("npa_world_scan_noisy", self._scan_noisy, scan_args + (nz["std"], nz["angle_std"], nz["seed"], 0))
+        # the map's slot behind it (a world without a map: no slot, no launch, no buffer), and its clearance for the tail step
+        grid_slot, self._grid_clear = (), None
+        if world.grid is not None:
+            glib, gmap = _lib_grid.load(), world._grid_args()
+            self._glib = glib
+            grid_args = gmap + (B, _ptr(par_w), _ptr(nb), R, _ptr(self.ranges), _ptr(self.beam_vel), _ptr(self.hit))
+            if self._noise is None:
+                grid_slot = (("npa_grid_scan", self._grid_scan, grid_args + (0.0, 0.0, 0, 0, 0)),)
+            else:
+                nz = self._noise
+                grid_slot = (("npa_grid_scan", self._grid_scan_noisy, grid_args + (nz["std"], nz["angle_std"], nz["seed"], 0)),)
+            self._grid_clear = gmap + (B, _ptr(st), len(V), V.ctypes.data_as(C.POINTER(C.c_double)), world._grid_reach,
+                                       _ptr(self.clearance))
+            self._held_map = world.grid.cells
         self._front = (
             ("npa_cycle_progress", lib.npa_cycle_progress,
              (B, _ptr(st), _ptr(path_d), _ptr(off_d), _ptr(len_d), _ptr(first_d), 1 if fleet.loop else 0, fleet.close_threshold,
               fleet.ind_range, fleet.arrive_threshold, fleet.arrive_index_threshold, _ptr(self.curve_index), _ptr(self.cur_off),
               _ptr(self.cur_len), _ptr(self.point_index), _ptr(self._curve_arrived), _ptr(self.arrived), _ptr(par_w), _ptr(par_s))),
             scan_slot,
+            *grid_slot,
             ("npa_scan_to_points", lib.npa_scan_to_points,
              (B, R, _ptr(self.ranges), _ptr(self.beam_vel) if point_velocities else None, None, _ptr(par_s),
               1 if point_velocities else 0, N, _ptr(self.points), _ptr(self.point_velocities), _ptr(self.n_points))),
@@ -1040,6 +1108,17 @@ class ResidentLoop:
         """the noisy scan of the cycle being issued: draw draw0 + cycles_done (scene_base 0: robot b is scene b), so a second
         run continues the sequence and `LonLoop.reset` does not rewind it; args: the slot's, then the stream"""
         return self._lib.npa_world_scan_noisy(*args[:-1], self._noise["draw0"] + self.cycles_done, args[-1])
+
+    def _grid_scan(self, *args):
+        """the map's slot: a failure is reported with this library's own message (`_front_step` reads the main library's)"""
+        rc = self._glib.npa_grid_scan(*args)
+        if rc:
+            _lib_grid.check(rc, "npa_grid_scan")
+        return rc
+
+    def _grid_scan_noisy(self, *args):
+        """the map's slot behind a noisy scan: the same draw number, read at issue time as `_scan_noisy` reads it"""
+        return self._grid_scan(*args[:-1], self._noise["draw0"] + self.cycles_done, args[-1])
 
     def _front_step(self):
         """the workspace check, then the launches in front of the plan; returns the cycle's stream"""
@@ -1084,6 +1163,10 @@ class ResidentLoop:
         rc = lib.npa_world_step(*self._step, stream)
         if rc:
             check(rc, "npa_world_step")
+        if self._grid_clear is not None:                 # the map's cells into the clearance, in front of the collision latch
+            rc = self._glib.npa_grid_clearance(*self._grid_clear, stream)
+            if rc:
+                _lib_grid.check(rc, "npa_grid_clearance")
         rc = lib.npa_cycle_commit(self.B, row, *self._commit, lh, lr, stream)
         if rc:
             check(rc, "npa_cycle_commit")
