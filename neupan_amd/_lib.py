@@ -1,4 +1,5 @@
-"""ctypes binding of libneupan_amd.so (C ABI: include/neupan_amd.h).
+"""ctypes binding of libneupan_amd.so (C ABI: include/neupan_amd.h), and `Binding`, the one loader of every row of
+build.LIBRARIES (_lib_train.py and _lib_grid.py are a symbol table and a Binding each).
 
 The HIP library is the product path.  There is NO CPU fallback: if the shared library is
 missing (or cannot be loaded) every entry point raises -- build it with
@@ -8,11 +9,13 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import shutil
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from . import build
+
 # (NPA_LIB_PATH: a variant build of the same library -- the experiments build, a profiling build -- for tools and tests; there is
 # no fallback of any kind: whichever path is named must exist and export every symbol of include/neupan_amd.h)
-LIB_PATH = os.environ.get("NPA_LIB_PATH") or os.path.join(HERE, "libneupan_amd.so")
+LIB_PATH = os.environ.get("NPA_LIB_PATH") or build.LIB
 
 NPA_MAX_T, NPA_MAX_M, NPA_MAX_E = 21, 32, 8
 KIN = {"diff": 0, "acker": 1, "omni": 2}
@@ -115,35 +118,48 @@ SYMBOLS = {
     "npa_version": (C.c_char_p, []),
 }
 
-_lib = None
-
-
 class NeupanAmdError(RuntimeError):
     pass
 
 
-def load():
-    """Load the HIP library; raise loudly if it is absent (no fallback path exists)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    # torch must be imported first: its wheel bundles the HIP runtime (libamdhip64) that owns
-    # the device context and the streams we are handed; loading ours after it makes the
-    # dynamic linker bind this library to that same runtime instead of a second copy.
-    import torch  # noqa: F401
-    if not os.path.exists(LIB_PATH):
-        raise NeupanAmdError(
-            f"{LIB_PATH} not found: the HIP extension is not built. Run `python -m neupan_amd.build` "
-            "(needs hipcc; cross-compiles for gfx950). neupan_amd has no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)          # AttributeError if the export is missing
-        fn.restype, fn.argtypes = res, args
-    _lib = lib
-    return lib
+class Binding:
+    """One row of build.LIBRARIES behind ctypes: `load()` opens the library once and gives every name of `symbols` its
+    prototype (a missing export is an AttributeError there), `check(status, what)` raises with the library's own last-error
+    string, the export `last_error`.  on_demand: build the row first when it is stale and a compiler is at hand (the main
+    library never builds on load).  missing: what to say behind "<path> not found"; path: a callable where the path can change
+    after import, else the row's output."""
+
+    def __init__(self, row, symbols, last_error, missing, on_demand=True, path=None):
+        self.row, self.symbols, self.last_error, self.missing, self.on_demand = row, symbols, last_error, missing, on_demand
+        self.path = path or (lambda: build.LIBRARIES[row].lib)
+        self.lib = None
+
+    def load(self):
+        if self.lib is not None:
+            return self.lib
+        # torch must be imported first: its wheel bundles the HIP runtime (libamdhip64) that owns
+        # the device context and the streams we are handed; loading ours after it makes the
+        # dynamic linker bind this library to that same runtime instead of a second copy.
+        import torch  # noqa: F401
+        path = self.path()
+        if self.on_demand and build.needs_build(self.row) and (shutil.which("hipcc") or os.path.exists(build.hipcc_path())):
+            build.build_library(self.row, verbose=False)
+        if not os.path.exists(path):
+            raise NeupanAmdError(f"{path} not found{self.missing}")
+        lib = C.CDLL(path)
+        for name, (res, args) in self.symbols.items():
+            fn = getattr(lib, name)          # AttributeError if the export is missing
+            fn.restype, fn.argtypes = res, args
+        self.lib = lib
+        return lib
+
+    def check(self, status, what):
+        if status != 0:
+            msg = getattr(self.load(), self.last_error)()
+            raise NeupanAmdError(f"{what} failed with status {status}: {msg.decode() if msg else ''}")
 
 
-def check(status, what):
-    if status != 0:
-        msg = load().npa_last_error()
-        raise NeupanAmdError(f"{what} failed with status {status}: {msg.decode() if msg else ''}")
+# load(): the HIP library, raising loudly if it is absent (no fallback path exists)
+_main = Binding("main", SYMBOLS, "npa_last_error", ": the HIP extension is not built. Run `python -m neupan_amd.build` (needs hipcc; "
+                "cross-compiles for gfx950). neupan_amd has no CPU fallback.", on_demand=False, path=lambda: LIB_PATH)
+load, check = _main.load, _main.check

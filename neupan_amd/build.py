@@ -1,23 +1,27 @@
-"""Build libneupan_amd.so, libneupan_amd_train.so and libneupan_amd_grid.so in-tree with hipcc for gfx950 (cross-compiles
-without a GPU).
+"""Build the project's shared libraries in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
-    python -m neupan_amd.build            # the three libraries; also invoked by __graft_entry__.build()
+    python -m neupan_amd.build [--force]  # every row of LIBRARIES; also invoked by __graft_entry__.build()
+
+`LIBRARIES` is the one table: a row names a library's output, its translation units in link order, the public headers and the
+csrc files those units include.  `needs_build(name)` and `build_library(name)` read nothing else; the objects of every row go
+to neupan_amd/_obj/.  Why there are three libraries and how to add a fourth: DESIGN.md, "Libraries".
 """
 from __future__ import annotations
 
+import functools
 import os
 import shutil
 import subprocess
 import sys
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-LIB = os.path.join(HERE, "libneupan_amd.so")
+INCLUDE = os.path.join(HERE, "..", "include")
+OBJ = os.path.join(HERE, "_obj")
 # The product build.  NPA_EXPERIMENTS=1 in the environment adds the one experiment on record that is still compiled (DESIGN.md
 # section 7: the first form of the geometric selection, select_kernel<E, true>) and its knob, NPA_SELECT_V1.
 EXPERIMENTS = os.environ.get("NPA_EXPERIMENTS", "0") not in ("", "0")
-SOURCES = ["dune.hip", "nrmp_qp.hip", "frontend.hip", "dune_labels.hip", "c_api.hip", "create.hip", "pack_image.hip", "serve_group.hip",
-           "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip", "curves.hip"]
 # -ffp-contract=fast-honor-pragmas is hipcc's default for device code, stated here so that it is the BUILD's property, not the
 # compiler's: the bit-exact legs (A / B / C, fa against the reference's tensors) are written with __f*_rn intrinsics where the
 # reference rounds every operation, and with explicit fmaf where it does not
@@ -25,16 +29,49 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", 
          "-Wno-unused-result", "-Wno-unused-value"] + (["-DNPA_EXPERIMENTS"] if EXPERIMENTS else [])
 
 
+class Library(NamedTuple):
+    """A row of LIBRARIES.  lib: the output; sources: the .hip files of csrc/ in link order; headers: files of include/, first
+    the one whose exports the library implements, then those it pulls in; includes: every csrc file a source reaches through
+    #include "..." (tests/test_build.py walks the includes and fails on a file that is not listed)."""
+    lib: str
+    sources: list
+    headers: tuple
+    includes: tuple = ()
+
+    def files(self):
+        """every file the output depends on"""
+        return [os.path.join(CSRC, f) for f in (*self.sources, *self.includes)] + [os.path.join(INCLUDE, f) for f in self.headers]
+
+
+LIBRARIES = {
+    # held below 2 MiB (tests/test_build.py): what has no room here gets a row of its own
+    "main": Library(os.path.join(HERE, "libneupan_amd.so"),
+                    ["dune.hip", "nrmp_qp.hip", "frontend.hip", "dune_labels.hip", "c_api.hip", "create.hip", "pack_image.hip",
+                     "serve_group.hip", "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip", "curves.hip"],
+                    ("neupan_amd.h",),
+                    ("handle.h", "pan_common.h", "pack_image.h", "curves.h", "scan_beam.h", "scan_noise.h", "dune_device.h",
+                     "select_geo_carve.inc", "select_geo_body.inc", "nrmp_qp_device.h", "nrmp_qp_body.inc")),
+    # the fused DUNE training step
+    "train": Library(os.path.join(HERE, "libneupan_amd_train.so"), ["dune_train.hip"], ("neupan_amd_train.h", "neupan_amd.h")),
+    # the occupancy-grid obstacle of the device world; the beam and noise headers are the ones it shares with world.hip
+    "grid": Library(os.path.join(HERE, "libneupan_amd_grid.so"), ["grid.hip"], ("neupan_amd_grid.h", "neupan_amd.h"),
+                    ("scan_beam.h", "scan_noise.h")),
+}
+LIB, TRAIN_LIB, GRID_LIB = (LIBRARIES[k].lib for k in ("main", "train", "grid"))
+SOURCES, TRAIN_SOURCES, GRID_SOURCES = (LIBRARIES[k].sources for k in ("main", "train", "grid"))
+
+
 def hipcc_path():
     return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-def needs_build():
-    if not os.path.exists(LIB):
+def needs_build(name):
+    """the row's output is missing, or older than one of the row's files"""
+    row = LIBRARIES[name]
+    if not os.path.exists(row.lib):
         return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "neupan_amd.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+    t = os.path.getmtime(row.lib)
+    return any(os.path.getmtime(f) > t for f in row.files())
 
 
 # The kernels were validated (bitwise determinism of the reduced-precision key path included -- an earlier form of its
@@ -60,9 +97,11 @@ def hipcc_version():
     return "unknown"
 
 
-def build(force=False, verbose=True):
-    if not force and not needs_build():
-        return LIB
+def build_library(name, force=False, verbose=True):
+    """Compile the row's units side by side and link them, stripped, in the row's order; returns the output's path."""
+    row = LIBRARIES[name]
+    if not force and not needs_build(name):
+        return row.lib
     ver = hipcc_version()
     if not ver.startswith(VALIDATED_HIPCC):
         msg = (f"neupan_amd.build: hipcc {ver} is not the validated {VALIDATED_HIPCC} (two miscompile symptoms were seen with "
@@ -71,9 +110,10 @@ def build(force=False, verbose=True):
             raise UnvalidatedCompiler(msg + ": set NPA_ALLOW_UNVALIDATED=1 to build anyway, then run the -m gpu suite")
         print(msg + ": building because NPA_ALLOW_UNVALIDATED=1 -- run the -m gpu determinism tests before trusting it",
               file=sys.stderr)
+    os.makedirs(OBJ, exist_ok=True)
     objs, procs = [], []
-    for src in SOURCES:                      # (the translation units are independent: compiled side by side)
-        obj = os.path.join(CSRC, src.replace(".hip", ".o"))
+    for src in row.sources:                  # (the translation units are independent: compiled side by side)
+        obj = os.path.join(OBJ, src.replace(".hip", ".o"))
         cmd = [hipcc_path(), *FLAGS, f'-DNPA_HIPCC_VERSION="{ver}"', "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -83,96 +123,16 @@ def build(force=False, verbose=True):
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
     # (linked stripped: the static symbol table is a fiftieth of the file and nothing reads it -- the exports are .dynsym's)
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--strip-all", *objs, "-o", LIB]
+    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--strip-all", *objs, "-o", row.lib]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
-    return LIB
+    return row.lib
 
 
-# The training library (include/neupan_amd_train.h): a library of its own, because libneupan_amd.so is held below 2 MiB
-# (tests/test_abi.py) and has no room for another kernel.  Same flags, same compiler refusal, same stripped link.
-TRAIN_SOURCES = ["dune_train.hip"]
-TRAIN_LIB = os.path.join(HERE, "libneupan_amd_train.so")
-TRAIN_OBJ = os.path.join(HERE, "_obj")      # (not csrc/: needs_build() takes every file there for a source of the main library)
-
-
-def needs_build_train():
-    if not os.path.exists(TRAIN_LIB):
-        return True
-    t = os.path.getmtime(TRAIN_LIB)
-    deps = [os.path.join(CSRC, f) for f in TRAIN_SOURCES] + [os.path.join(HERE, "..", "include", f)
-                                                             for f in ("neupan_amd_train.h", "neupan_amd.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def build_train(force=False, verbose=True):
-    if not force and not needs_build_train():
-        return TRAIN_LIB
-    ver = hipcc_version()
-    if not ver.startswith(VALIDATED_HIPCC):
-        msg = f"neupan_amd.build: hipcc {ver} is not the validated {VALIDATED_HIPCC} (DESIGN.md section 1)"
-        if os.environ.get("NPA_ALLOW_UNVALIDATED") != "1":
-            raise UnvalidatedCompiler(msg + ": set NPA_ALLOW_UNVALIDATED=1 to build anyway, then run the -m gpu suite")
-        print(msg + ": building because NPA_ALLOW_UNVALIDATED=1 -- run the -m gpu suite before trusting it", file=sys.stderr)
-    objs = []
-    os.makedirs(TRAIN_OBJ, exist_ok=True)
-    for src in TRAIN_SOURCES:
-        obj = os.path.join(TRAIN_OBJ, src.replace(".hip", ".o"))
-        cmd = [hipcc_path(), *FLAGS, f'-DNPA_HIPCC_VERSION="{ver}"', "-c", os.path.join(CSRC, src), "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-        objs.append(obj)
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--strip-all", *objs, "-o", TRAIN_LIB]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return TRAIN_LIB
-
-
-# The occupancy-grid library (include/neupan_amd_grid.h): a library of its own for the same reason.  Same flags, same compiler
-# refusal, same stripped link; scan_beam.h and scan_noise.h are the headers it shares with world.hip of the main library.
-GRID_SOURCES = ["grid.hip"]
-GRID_LIB = os.path.join(HERE, "libneupan_amd_grid.so")
-GRID_HEADERS = ["scan_beam.h", "scan_noise.h"]
-
-
-def needs_build_grid():
-    if not os.path.exists(GRID_LIB):
-        return True
-    t = os.path.getmtime(GRID_LIB)
-    deps = [os.path.join(CSRC, f) for f in GRID_SOURCES + GRID_HEADERS] + [os.path.join(HERE, "..", "include", f)
-                                                                            for f in ("neupan_amd_grid.h", "neupan_amd.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def build_grid(force=False, verbose=True):
-    if not force and not needs_build_grid():
-        return GRID_LIB
-    ver = hipcc_version()
-    if not ver.startswith(VALIDATED_HIPCC):
-        msg = f"neupan_amd.build: hipcc {ver} is not the validated {VALIDATED_HIPCC} (DESIGN.md section 1)"
-        if os.environ.get("NPA_ALLOW_UNVALIDATED") != "1":
-            raise UnvalidatedCompiler(msg + ": set NPA_ALLOW_UNVALIDATED=1 to build anyway, then run the -m gpu suite")
-        print(msg + ": building because NPA_ALLOW_UNVALIDATED=1 -- run the -m gpu suite before trusting it", file=sys.stderr)
-    objs = []
-    os.makedirs(TRAIN_OBJ, exist_ok=True)
-    for src in GRID_SOURCES:
-        obj = os.path.join(TRAIN_OBJ, src.replace(".hip", ".o"))
-        cmd = [hipcc_path(), *FLAGS, f'-DNPA_HIPCC_VERSION="{ver}"', "-c", os.path.join(CSRC, src), "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-        objs.append(obj)
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--strip-all", *objs, "-o", GRID_LIB]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return GRID_LIB
+build, build_train, build_grid = (functools.partial(build_library, k) for k in ("main", "train", "grid"))
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
-    build_train(force="--force" in sys.argv)
-    build_grid(force="--force" in sys.argv)
+    for name in LIBRARIES:
+        build_library(name, force="--force" in sys.argv)

@@ -131,6 +131,10 @@ def _scan_block(st, angle_min, angle_max, range_min, range_max, scan_offset, dev
     return par
 
 
+def _vertices_ptr(V):
+    return None if V is None else V.ctypes.data_as(C.POINTER(C.c_double))
+
+
 NOISE = dict(std=0.0, angle_std=0.0, seed=0, draw0=0)
 
 
@@ -235,6 +239,32 @@ class LidarWorld:
         """the map as npa_grid_scan and npa_grid_clearance take it: cells, nx, ny, x0, y0, res"""
         g = self._grid
         return (_ptr(g.cells), int(g.cells.shape[1]), int(g.cells.shape[0]), g.origin[0], g.origin[1], g.resolution)
+
+    # The arguments of the four world launches, each spelled once: `scan`, `_step` and ResidentLoop.__init__ all take them from
+    # here, so the loops cannot come to disagree about a launch.  Every tuple ends where the launch's own tail begins (the
+    # noise fields and the stream).
+    def _scan_args(self, B, par, nb, R, ranges, vel, hit):
+        """npa_world_scan's (and npa_world_scan_noisy's) arguments up to hit"""
+        c, s, nc, ns = self._upload()
+        skip = self.skip if (self.skip is not None and self.skip.shape[0] == B) else None
+        return (B, self.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par), _ptr(nb), R, _ptr(skip),
+                _ptr(ranges), _ptr(vel), _ptr(hit))
+
+    def _grid_scan_args(self, B, par, nb, R, ranges, vel, hit):
+        """npa_grid_scan's arguments up to hit"""
+        return self._grid_args() + (B, _ptr(par), _ptr(nb), R, _ptr(ranges), _ptr(vel), _ptr(hit))
+
+    def _step_args(self, st, act, frozen, dt, kinematics, wheelbase, V, peers, clr):
+        """npa_world_step's arguments up to the clearance; V: the robot's vertices [E, 2] (a contiguous float64 array the caller
+        keeps alive) or None"""
+        c, s, nc, ns = self._upload()
+        return (st.shape[0], self.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(st), _ptr(act), _ptr(frozen),
+                float(dt), KIN[kinematics], float(wheelbase or 0.0), self.bounds, 0 if V is None else len(V), _vertices_ptr(V),
+                self.peer_base if peers else -1, _ptr(clr))
+
+    def _grid_clearance_args(self, st, V, clr):
+        """npa_grid_clearance's arguments up to the clearance"""
+        return self._grid_args() + (st.shape[0], _ptr(st), len(V), _vertices_ptr(V), self._grid_reach, _ptr(clr))
 
     def add_agents(self, first, count=1, v_max=1.0, goal_threshold=0.1, wander=False, goals=None, **behaviour):
         """Make primitives of every world agents: they choose their velocity in every `behave` call (npa_world_behave).
@@ -536,10 +566,7 @@ class LidarWorld:
             hit = torch.zeros((B, R), dtype=torch.int32, device=dev)
         else:
             ranges, vel, hit = out
-        c, s, nc, ns = self._upload()
-        skip = self.skip if (self.skip is not None and self.skip.shape[0] == B) else None
-        args = (B, self.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par), _ptr(nb), R, _ptr(skip),
-                _ptr(ranges), _ptr(vel), _ptr(hit))
+        args = self._scan_args(B, par, nb, R, ranges, vel, hit)
         with torch.cuda.device(dev):
             if nz is None:
                 check(lib.npa_world_scan(*args, _stream(dev)), "npa_world_scan")
@@ -548,9 +575,9 @@ class LidarWorld:
                       "npa_world_scan_noisy")
             if self._grid is not None:
                 z = nz or NOISE
-                _lib_grid.check(_lib_grid.load().npa_grid_scan(*self._grid_args(), B, _ptr(par), _ptr(nb), R, _ptr(ranges), _ptr(vel),
-                                                               _ptr(hit), z["std"], z["angle_std"], z["seed"], int(scene_base),
-                                                               int(draw), _stream(dev)), "npa_grid_scan")
+                _lib_grid.check(_lib_grid.load().npa_grid_scan(*self._grid_scan_args(B, par, nb, R, ranges, vel, hit), z["std"],
+                                                               z["angle_std"], z["seed"], int(scene_base), int(draw), _stream(dev)),
+                                "npa_grid_scan")
         return ranges, vel, hit
 
     # ------------------------------------------------------------------ step
@@ -579,18 +606,13 @@ class LidarWorld:
 
     def _step(self, st, act, dt, kinematics, wheelbase, frozen, V, peers, want_clearance):
         lib, dev = _lib.load(), self.device
-        B = st.shape[0]
-        c, s, nc, ns = self._upload()
-        clr = torch.empty((B,), dtype=torch.float64, device=dev) if want_clearance else None
-        vp = None if V is None else V.ctypes.data_as(C.POINTER(C.c_double))
+        clr = torch.empty((st.shape[0],), dtype=torch.float64, device=dev) if want_clearance else None
         with torch.cuda.device(dev):
-            check(lib.npa_world_step(B, self.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(st), _ptr(act),
-                                     _ptr(frozen), float(dt), KIN[kinematics], float(wheelbase or 0.0), self.bounds,
-                                     0 if V is None else len(V), vp, self.peer_base if peers else -1, _ptr(clr), _stream(dev)),
+            check(lib.npa_world_step(*self._step_args(st, act, frozen, dt, kinematics, wheelbase, V, peers, clr), _stream(dev)),
                   "npa_world_step")
             if clr is not None and self._grid is not None:
-                _lib_grid.check(_lib_grid.load().npa_grid_clearance(*self._grid_args(), B, _ptr(st), len(V), vp, self._grid_reach,
-                                                                    _ptr(clr), _stream(dev)), "npa_grid_clearance")
+                _lib_grid.check(_lib_grid.load().npa_grid_clearance(*self._grid_clearance_args(st, V, clr), _stream(dev)),
+                                "npa_grid_clearance")
         return clr
 
     def step(self, states, actions, dt, kinematics, wheelbase=0.0, frozen=None, robot_vertices=None, peers=False):
@@ -998,8 +1020,6 @@ class ResidentLoop:
         self.points = zeros((B, 2, N), torch.float32)
         self.point_velocities = zeros((B, 2, N), torch.float32) if point_velocities else None
         self.n_points = zeros((B,), torch.int32)
-        c, s, nc, ns = world._upload()
-        skip = world.skip if (world.skip is not None and world.skip.shape[0] == B) else None
         # ---- nominal / reference
         nbt = fleet.nb
         self.cur_vel = zeros((B, 2, T), torch.float32)              # (zeros on the first cycle: neupan.py:73)
@@ -1023,7 +1043,7 @@ class ResidentLoop:
         self._plan = (pan._h, B, N if use_pts else 1, _ptr(nom_s), _ptr(nom_u), _ptr(ref_s), _ptr(ref_us), _ptr(p_pts), _ptr(p_vel),
                       _ptr(p_np), _ptr(out["opt_s"]), _ptr(out["opt_u"]), _ptr(out["opt_d"]), _ptr(out["min_distance"]),
                       _ptr(out["iters"]), _ptr(out["nrmp_points"]), _ptr(ws), ws.numel(), _ptr(state), state.numel())
-        self._held = (ws, state, c, s, nc, ns, skip, nb, spd, itv, V)
+        self._held = (ws, state, *world._upload(), world.skip, nb, spd, itv, V)
         self._held_ptrs = (ws.data_ptr(), state.data_ptr())
         self.plan_clearance = None
         self._certify = None
@@ -1038,50 +1058,47 @@ class ResidentLoop:
         self.action, self.stop = zeros((B, 2), torch.float32), zeros((B,), torch.uint8)
         self.frozen, self.clearance = zeros((B,), torch.int32), empty((B,), torch.float64)
         path_d, off_d, len_d, first_d = self._table
+        # A slot of the front step is (name, fn, args, check): `check` is the library's own, so a failure is reported with the
+        # message of the library that failed.
         # the scan slot: with noise, npa_world_scan_noisy over the same arguments; its draw number is a host scalar read at
         # issue time (`_scan_noisy`), like the log row -- no buffer, no synchronisation
-        self._noise = sp["noise"]
-        scan_args = (B, world.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(par_w), _ptr(nb), R, _ptr(skip),
-                     _ptr(self.ranges), _ptr(self.beam_vel), _ptr(self.hit))
-        if self._noise is None:
-            scan_slot = ("npa_world_scan", lib.npa_world_scan, scan_args)
+        self._noise = nz = sp["noise"]
+        scan_out = (par_w, nb, R, self.ranges, self.beam_vel, self.hit)
+        scan_args = world._scan_args(B, *scan_out)
+        if nz is None:
+            scan_slot = ("npa_world_scan", lib.npa_world_scan, scan_args, check)
         else:
-            nz = self._noise
-            scan_slot = ("npa_world_scan_noisy", self._scan_noisy, scan_args + (nz["std"], nz["angle_std"], nz["seed"], 0))
+            scan_slot = ("npa_world_scan_noisy", self._scan_noisy, scan_args + (nz["std"], nz["angle_std"], nz["seed"], 0), check)
         # the map's slot behind it (a world without a map: no slot, no launch, no buffer), and its clearance for the tail step
         grid_slot, self._grid_clear = (), None
         if world.grid is not None:
-            glib, gmap = _lib_grid.load(), world._grid_args()
-            self._glib = glib
-            grid_args = gmap + (B, _ptr(par_w), _ptr(nb), R, _ptr(self.ranges), _ptr(self.beam_vel), _ptr(self.hit))
-            if self._noise is None:
-                grid_slot = (("npa_grid_scan", self._grid_scan, grid_args + (0.0, 0.0, 0, 0, 0)),)
+            self._glib = glib = _lib_grid.load()
+            grid_args = world._grid_scan_args(B, *scan_out)
+            if nz is None:
+                grid_slot = (("npa_grid_scan", glib.npa_grid_scan, grid_args + (0.0, 0.0, 0, 0, 0), _lib_grid.check),)
             else:
-                nz = self._noise
-                grid_slot = (("npa_grid_scan", self._grid_scan_noisy, grid_args + (nz["std"], nz["angle_std"], nz["seed"], 0)),)
-            self._grid_clear = gmap + (B, _ptr(st), len(V), V.ctypes.data_as(C.POINTER(C.c_double)), world._grid_reach,
-                                       _ptr(self.clearance))
+                grid_slot = (("npa_grid_scan", self._grid_scan_noisy, grid_args + (nz["std"], nz["angle_std"], nz["seed"], 0),
+                              _lib_grid.check),)
+            self._grid_clear = world._grid_clearance_args(st, V, self.clearance)
             self._held_map = world.grid.cells
         self._front = (
             ("npa_cycle_progress", lib.npa_cycle_progress,
              (B, _ptr(st), _ptr(path_d), _ptr(off_d), _ptr(len_d), _ptr(first_d), 1 if fleet.loop else 0, fleet.close_threshold,
               fleet.ind_range, fleet.arrive_threshold, fleet.arrive_index_threshold, _ptr(self.curve_index), _ptr(self.cur_off),
-              _ptr(self.cur_len), _ptr(self.point_index), _ptr(self._curve_arrived), _ptr(self.arrived), _ptr(par_w), _ptr(par_s))),
+              _ptr(self.cur_len), _ptr(self.point_index), _ptr(self._curve_arrived), _ptr(self.arrived), _ptr(par_w), _ptr(par_s)), check),
             scan_slot,
             *grid_slot,
             ("npa_scan_to_points", lib.npa_scan_to_points,
              (B, R, _ptr(self.ranges), _ptr(self.beam_vel) if point_velocities else None, None, _ptr(par_s),
-              1 if point_velocities else 0, N, _ptr(self.points), _ptr(self.point_velocities), _ptr(self.n_points))),
+              1 if point_velocities else 0, N, _ptr(self.points), _ptr(self.point_velocities), _ptr(self.n_points)), check),
             ("npa_nominal_ref_states", lib.npa_nominal_ref_states,
              (B, T, KIN[kin], fleet.dt, nbt.L, _ptr(st), _ptr(self.cur_vel), _ptr(spd), _ptr(path_d), _ptr(self.cur_off),
-              _ptr(self.cur_len), _ptr(self.point_index), _ptr(itv), _ptr(nom_s), _ptr(nom_u), _ptr(ref_s), _ptr(ref_us))))
+              _ptr(self.cur_len), _ptr(self.point_index), _ptr(itv), _ptr(nom_s), _ptr(nom_u), _ptr(ref_s), _ptr(ref_us)), check))
         self._act = (_ptr(out["opt_u"]), _ptr(out["min_distance"]), float(fleet.collision_threshold), _ptr(self.arrived),
                      _ptr(self.collided))
         self._act_out = (_ptr(self.n_points), _ptr(self.cur_vel), _ptr(self.action), _ptr(self.stop), _ptr(self.frozen))
         self._kin = KIN[kin]
-        self._step = (B, world.W, c.shape[1], s.shape[1], _ptr(c), _ptr(s), _ptr(nc), _ptr(ns), _ptr(st), _ptr(self.action),
-                      _ptr(self.frozen), float(fleet.dt), KIN[kin], float(L), world.bounds, len(V),
-                      V.ctypes.data_as(C.POINTER(C.c_double)), world.peer_base if peers else -1, _ptr(self.clearance))
+        self._step = world._step_args(st, self.action, self.frozen, fleet.dt, kin, L, V, peers, self.clearance)
         self._commit = (_ptr(st), _ptr(self.clearance), _ptr(self.collided))
         # ---- the next goal of a robot that has arrived, behind the commit (without goals: no launch, no buffer)
         self._retask, self._log_goal, self.goal_index, self.retask_status = None, None, None, None
@@ -1109,16 +1126,9 @@ class ResidentLoop:
         run continues the sequence and `LonLoop.reset` does not rewind it; args: the slot's, then the stream"""
         return self._lib.npa_world_scan_noisy(*args[:-1], self._noise["draw0"] + self.cycles_done, args[-1])
 
-    def _grid_scan(self, *args):
-        """the map's slot: a failure is reported with this library's own message (`_front_step` reads the main library's)"""
-        rc = self._glib.npa_grid_scan(*args)
-        if rc:
-            _lib_grid.check(rc, "npa_grid_scan")
-        return rc
-
     def _grid_scan_noisy(self, *args):
         """the map's slot behind a noisy scan: the same draw number, read at issue time as `_scan_noisy` reads it"""
-        return self._grid_scan(*args[:-1], self._noise["draw0"] + self.cycles_done, args[-1])
+        return self._glib.npa_grid_scan(*args[:-1], self._noise["draw0"] + self.cycles_done, args[-1])
 
     def _front_step(self):
         """the workspace check, then the launches in front of the plan; returns the cycle's stream"""
@@ -1128,10 +1138,10 @@ class ResidentLoop:
             raise NeupanAmdError(f"{type(self).__name__}: the planner's workspace was re-made since the loop was prepared (another "
                                  "batch size planned on the same PAN): make the loop again")
         stream = C.c_void_p(torch.cuda.current_stream(self._idx).cuda_stream)     # (_on_device made _idx the current device)
-        for name, fn, args in self._front:
+        for name, fn, args, failed in self._front:
             rc = fn(*args, stream)
             if rc:
-                check(rc, name)
+                failed(rc, name)
         return stream
 
     def _plan_step(self, stream):

@@ -1,6 +1,7 @@
 """CPU tests of the drop-in boundary: the shared library builds/loads here (hipcc cross-compiles
-without a GPU) and exports every symbol include/neupan_amd.h declares; struct layouts agree;
-the host-side mirror refuses to run without a GPU instead of falling back."""
+without a GPU); struct layouts agree; the host-side mirror refuses to run without a GPU instead of falling back; the
+machine code of every library is free of the two hazards the compiler does not see.  (What each library declares, binds
+and exports, and how it is built: tests/test_build.py.)"""
 import ctypes as C
 import os
 import re
@@ -18,22 +19,6 @@ def lib():
     build.build(force=False, verbose=False)
     from neupan_amd import _lib
     return _lib.load()
-
-
-def declared_symbols():
-    txt = open(os.path.join(ROOT, "include", "neupan_amd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(npa_[a-z_]+)\s*\(", txt)))
-
-
-def test_header_symbols_are_exported_and_bound(lib):
-    from neupan_amd import _lib
-    names = declared_symbols()
-    assert len(names) >= 12
-    for n in names:
-        assert hasattr(lib, n), f"{n} declared in include/neupan_amd.h but not exported"
-        assert n in _lib.SYMBOLS, f"{n} has no ctypes prototype in neupan_amd/_lib.py"
-    assert b"gfx950" in lib.npa_version()
 
 
 def test_config_struct_layout_matches_header():
@@ -240,7 +225,6 @@ def test_hot_kernels_have_no_spills_and_no_scratch():
     from conftest import experiments_built
     if not experiments_built():
         assert not any("aset" in n or "select_kernelILi4ELb1" in n for n in res), "experiment kernels in the product build"
-        assert os.path.getsize(kr.LIB) < 2 * 1024 * 1024, os.path.getsize(kr.LIB)
 
 
 def test_product_qp_instantiations_are_the_ones_the_launchers_name():
@@ -271,7 +255,8 @@ def test_no_kernel_has_instructions_that_only_run_with_exec_zero():
     EXEC -- they execute with EXEC == 0, do nothing, and the restores behind the region bring back stale values
     (tests/tools/hw/README.md, profiles/r05_spilled_build_fault.txt).  Whether a build has such instructions is a static
     property of its machine code (tests/tools/kernel_resources.exec_zero_dead: a must-analysis of EXEC == 0 over the control
-    flow): the product library must have none, in ANY kernel.  (The analysis is also unit-tested on a hand-written block.)"""
+    flow): the product must have none, in ANY kernel of ANY library of build.LIBRARIES.  (The analysis is also unit-tested on a
+    hand-written block.)"""
     sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
     import kernel_resources as kr
     # the analysis itself: a divergent loop, then a copy and a spill store in front of the EXEC restore -- and a clean variant
@@ -300,8 +285,10 @@ def test_no_kernel_has_instructions_that_only_run_with_exec_zero():
     assert kr.exec_zero_dead(block(["s_or_b64 exec, exec, s[6:7]", "v_mov_b32_e32 v142, v136"])) == []
     if not kr.tools_available():
         pytest.skip("ROCm LLVM tools not installed")
-    lost = kr.lost_instructions()
-    assert lost == {}, {k: v[:4] for k, v in lost.items()}
+    from neupan_amd import build as b
+    for name in b.LIBRARIES:
+        lost = kr.lost_instructions(b.build_library(name, verbose=False))
+        assert lost == {}, (name, {k: v[:4] for k, v in lost.items()})
 
 
 def test_hand_written_dpp_instructions_have_their_wait_states():
@@ -309,7 +296,7 @@ def test_hand_written_dpp_instructions_have_their_wait_states():
     statements of nrmp_qp_device.h) -- the compiler schedules around such a statement but does not know its hazards: a VGPR written
     by a vector instruction may not be read through DPP within 2 wait states, one written by the statement not by v_readlane
     within 1.  The statements carry their own s_nop; what the register allocator puts around them is checked here on the MACHINE
-    CODE of the built library (tests/tools/kernel_resources.dpp_hazards; the instruction itself is checked on the device:
+    CODE of every built library (tests/tools/kernel_resources.dpp_hazards; only the main library has such statements; the instruction itself is checked on the device:
     tests/tools/hw/dpp_f64_check.hip, bitwise fma in all 64 lanes for every row_newbcast lane)."""
     sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
     import kernel_resources as kr
@@ -322,29 +309,9 @@ def test_hand_written_dpp_instructions_have_their_wait_states():
     assert kr.dpp_hazards(mk([dpp, ("s_nop", "0"), ("v_readlane_b32", "s3, v9, 4")])) == []
     if not kr.tools_available():
         pytest.skip("ROCm LLVM tools not installed")
-    rep = kr.dpp_hazard_report()
-    assert len(rep) >= 2, list(rep)                     # the stand-alone and the group instantiation of T = 10
-    assert all(v == [] for v in rep.values()), {k: v[:4] for k, v in rep.items() if v}
-
-
-def test_build_refuses_an_unvalidated_compiler(monkeypatch):
-    """neupan_amd.build fails (not warns) on a hipcc other than the validated one unless NPA_ALLOW_UNVALIDATED=1."""
     from neupan_amd import build as b
-    calls = []
-    monkeypatch.setattr(b, "hipcc_version", lambda: "9.9.99999-test")
-    monkeypatch.setattr(b.subprocess, "check_call", lambda cmd, *a, **k: calls.append(cmd))
-
-    class FakeProc:                                   # (the translation units are compiled side by side: Popen + wait)
-        def __init__(self, cmd, *a, **k):
-            calls.append(cmd)
-
-        def wait(self):
-            return 0
-    monkeypatch.setattr(b.subprocess, "Popen", FakeProc)
-    monkeypatch.delenv("NPA_ALLOW_UNVALIDATED", raising=False)
-    with pytest.raises(b.UnvalidatedCompiler):
-        b.build(force=True, verbose=False)
-    assert not calls
-    monkeypatch.setenv("NPA_ALLOW_UNVALIDATED", "1")
-    b.build(force=True, verbose=False)
-    assert len(calls) == len(b.SOURCES) + 1          # every source compiled, one link
+    for name in b.LIBRARIES:
+        rep = kr.dpp_hazard_report(b.build_library(name, verbose=False))
+        if name == "main":
+            assert len(rep) >= 2, list(rep)             # the stand-alone and the group instantiation of T = 10
+        assert all(v == [] for v in rep.values()), (name, {k: v[:4] for k, v in rep.items() if v})

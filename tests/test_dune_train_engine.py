@@ -1,7 +1,7 @@
 """The fused DUNE training step, the parts that need no GPU: the float64 restatement (tests/dune_train_ref.py) against
 float64 torch autograd of `dune_losses`; the ABI of libneupan_amd_train.so (include/neupan_amd_train.h), its refusals and
-its kernel's resources; the parameter pack; the `engine=` argument of DuneTrain.start; and that the main library is
-where it was."""
+its kernel's resources; the parameter pack; the `engine=` argument of DuneTrain.start.  (The library's build contract:
+tests/test_build.py.)"""
 import ctypes as C
 import inspect
 import os
@@ -75,15 +75,11 @@ def test_restatement_adam_matches_torch():
         assert np.abs(p - tp.detach().numpy()).max() <= 1e-14
 
 
-def test_symbols_declared_exported_and_bound(lib):
-    from neupan_amd import _lib, _lib_train
+def test_prototypes_have_the_argument_counts_of_the_header():
+    """(that the names are the header's, bound and exported: tests/test_build.py)"""
+    from neupan_amd import _lib_train
     hdr = _header()
-    names = sorted(set(re.findall(r"\b(npa_[a-z_]+)\s*\(", hdr)))
-    assert names == ["npa_dune_train_last_error", "npa_dune_train_param_count", "npa_dune_train_steps"]
-    assert sorted(_lib_train.SYMBOLS) == names
-    assert not set(names) & set(_lib.SYMBOLS)                  # a table of its own
-    for n in names:
-        assert hasattr(lib, n), n
+    for n in _lib_train.SYMBOLS:
         args = re.search(rf"\b{n}\s*\(([^)]*)\)", hdr).group(1).strip()
         count = 0 if args == "void" else args.count(",") + 1
         assert count == len(_lib_train.SYMBOLS[n][1]), (n, count)
@@ -159,31 +155,6 @@ def test_engine_argument():
     with pytest.raises(ValueError, match="ObsPointNet"):        # the right class, the wrong width
         DuneTrain(ObsPointNet(2, 5), z["G"], z["h"], tempfile.mkdtemp(), device="cpu").start(data_size=100, epoch=0, engine="hip")
     assert not os.path.exists(os.path.join(tr.checkpoint_path, "results.txt"))      # refused before anything is written
-
-
-def test_main_library_untouched_and_build_train_refuses_like_build(monkeypatch):
-    from neupan_amd import build as b
-    assert b.SOURCES == ["dune.hip", "nrmp_qp.hip", "frontend.hip", "dune_labels.hip", "c_api.hip", "create.hip", "pack_image.hip",
-                         "serve_group.hip", "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip",
-                         "curves.hip"]
-    assert b.TRAIN_SOURCES == ["dune_train.hip"] and os.path.basename(b.TRAIN_LIB) == "libneupan_amd_train.so"
-    b.build(force=False, verbose=False)
-    from conftest import experiments_built
-    if not experiments_built():
-        assert os.path.getsize(b.LIB) < 2 * 1024 * 1024
-    from neupan_amd import _lib
-    assert b"0.5.2" in _lib.load().npa_version()
-    calls = []
-    monkeypatch.setattr(b, "hipcc_version", lambda: "9.9.99999-test")
-    monkeypatch.setattr(b.subprocess, "check_call", lambda cmd, *a, **k: calls.append(cmd))
-    monkeypatch.delenv("NPA_ALLOW_UNVALIDATED", raising=False)
-    with pytest.raises(b.UnvalidatedCompiler):
-        b.build_train(force=True, verbose=False)
-    assert not calls
-    monkeypatch.setenv("NPA_ALLOW_UNVALIDATED", "1")
-    b.build_train(force=True, verbose=False)
-    assert len(calls) == len(b.TRAIN_SOURCES) + 1 and "-Wl,--strip-all" in calls[-1]
-    assert all(f in calls[0] for f in b.FLAGS)
 
 
 def test_training_kernel_has_no_scratch_and_no_spills(lib):

@@ -54,7 +54,7 @@ def test_resident_loop_equals_the_host_paced_loop_in_a_map(noise):
     start((fa, fb), paths())
     ref = run_closed_loop(fa, world(), POSES, cycles, scan=scan_of(100, noise), actions=actions)
     loop = ResidentLoop(fb, world(), POSES, scan=scan_of(100, noise))
-    names = [name for name, _, _ in loop._front]
+    names = [slot[0] for slot in loop._front]
     assert names[1] == ("npa_world_scan" if noise is None else "npa_world_scan_noisy") and names[2] == "npa_grid_scan"
     got = loop.run(cycles, actions=actions)
     assert_same(got, ref, RUN_KEYS)
@@ -86,7 +86,7 @@ def test_lon_loop_equals_the_host_paced_training_in_a_map():
     theta0 = lr.THETA0[:B]
     start((fb,), paths())
     loop = LonLoop(fb, world(), POSES, theta0, scan=scan_of(100))
-    assert [name for name, _, _ in loop._front][2] == "npa_grid_scan" and loop._grid_clear is not None
+    assert [slot[0] for slot in loop._front][2] == "npa_grid_scan" and loop._grid_clear is not None
     theta_h, opt = adjust_block(theta0, B, "cuda"), adam_state(B, "cuda")
     start((fa,), paths())
     ref = train_closed_loop(fa, world(), POSES, cycles, theta_h, opt, scan=scan_of(100), actions=actions)
@@ -113,6 +113,6 @@ def test_a_world_whose_map_was_removed_runs_the_loop_it_ran_before():
     assert w.grid is None
     loop = ResidentLoop(fb, w, poses, scan=scan_of(100))
     for lp in (plain, loop):
-        assert [name for name, _, _ in lp._front] == ["npa_cycle_progress", "npa_world_scan", "npa_scan_to_points", "npa_nominal_ref_states"]
+        assert [slot[0] for slot in lp._front] == ["npa_cycle_progress", "npa_world_scan", "npa_scan_to_points", "npa_nominal_ref_states"]
         assert lp._grid_clear is None
     assert_same(loop.run(4), plain.run(4), RUN_KEYS)

@@ -225,15 +225,15 @@ def test_resident_loop_equals_the_host_paced_loop_with_noise():
     start((fa, fb), paths)
     ref = run_closed_loop(fa, LidarWorld(c, s), poses, 6, scan=scan_of(100, nz))
     loop = ResidentLoop(fb, LidarWorld(c, s), poses, scan=scan_of(100, nz))
-    assert [name for name, _, _ in loop._front][1] == "npa_world_scan_noisy"
+    assert [slot[0] for slot in loop._front][1] == "npa_world_scan_noisy"
     got = loop.run(6)
     assert_same(got, ref, RUN_KEYS)
     assert loop.cycles_done == 6
     # the noise is seen: the noise-free run differs, and its loop issues the plain launch
     start((fa,), paths)
     quiet_loop = ResidentLoop(fa, LidarWorld(c, s), poses, scan=scan_of(100))
-    assert [name for name, _, _ in quiet_loop._front][1] == "npa_world_scan"
-    assert "npa_world_scan_noisy" not in [name for name, _, _ in quiet_loop._front]
+    assert [slot[0] for slot in quiet_loop._front][1] == "npa_world_scan"
+    assert "npa_world_scan_noisy" not in [slot[0] for slot in quiet_loop._front]
     quiet = quiet_loop.run(6)
     assert not torch.equal(quiet["n_points"], got["n_points"]) or not torch.equal(quiet["states"], got["states"])
     # a second run continues the draws: its first cycle scans with draw 6, as a host-paced run from the same poses with draw0 = 6
@@ -263,7 +263,7 @@ def test_lon_loop_equals_the_host_paced_training_with_noise():
     theta0 = lr.THETA0[:B]
     start((fb,), paths)
     loop = LonLoop(fb, LidarWorld(circles), poses, theta0, scan=scan_of(64, nz))
-    assert [name for name, _, _ in loop._front][1] == "npa_world_scan_noisy"
+    assert [slot[0] for slot in loop._front][1] == "npa_world_scan_noisy"
     theta_h, opt = adjust_block(theta0, B, "cuda"), adam_state(B, "cuda")
     start((fa,), paths)
     ref = train_closed_loop(fa, LidarWorld(circles), poses, 4, theta_h, opt, scan=scan_of(64, nz))

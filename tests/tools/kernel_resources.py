@@ -27,19 +27,7 @@ def kernel_resources(lib=LIB):
     """{demangled-ish kernel name: dict(vgpr, agpr, sgpr, vgpr_spill, sgpr_spill, scratch, lds, name)} for every kernel."""
     out = {}
     with tempfile.TemporaryDirectory() as d:
-        fat = os.path.join(d, "fat.bin")
-        subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", lib, os.path.join(d, "x")],
-                              stderr=subprocess.DEVNULL)
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-        for i, s in enumerate(starts):
-            part = os.path.join(d, f"b{i}.bin")
-            open(part, "wb").write(blob[s:starts[i + 1] if i + 1 < len(starts) else len(blob)])
-            co = os.path.join(d, f"b{i}.co")
-            r = subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={part}",
-                                "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], stderr=subprocess.PIPE)
-            if r.returncode != 0 or not os.path.exists(co) or os.path.getsize(co) == 0:
-                continue
+        for co in _code_objects(lib, d):
             notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], stdout=subprocess.PIPE, text=True).stdout
             cur = None
             for line in notes.splitlines():

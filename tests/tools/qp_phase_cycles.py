@@ -17,14 +17,14 @@ def prof_lib(mode):
 
 def build_prof(mode):
     lib = prof_lib(mode)
-    if os.path.exists(lib) and all(os.path.getmtime(lib) > os.path.getmtime(os.path.join(nb.CSRC, f)) for f in os.listdir(nb.CSRC) if not f.endswith(".o")):
+    if os.path.exists(lib) and all(os.path.getmtime(lib) > os.path.getmtime(f) for f in nb.LIBRARIES["main"].files()):
         return
     objs = []
     for src in nb.SOURCES:
         if src != "nrmp_qp.hip":                     # the other objects of the product build
-            objs.append(os.path.join(nb.CSRC, src.replace(".hip", ".o")))
+            objs.append(os.path.join(nb.OBJ, src.replace(".hip", ".o")))
             continue
-        o = os.path.join(nb.CSRC, "nrmp_qp.prof%d.o" % mode)
+        o = os.path.join(nb.OBJ, "nrmp_qp.prof%d.o" % mode)
         subprocess.check_call([nb.hipcc_path(), *nb.FLAGS, "-DNPA_QP_PROF=%d" % mode, f'-DNPA_HIPCC_VERSION="{nb.hipcc_version()}"',
                                "-c", os.path.join(nb.CSRC, src), "-o", o], stderr=subprocess.DEVNULL)
         objs.append(o)

@@ -18,14 +18,14 @@ NAMES = ["preamble (vectors to LDS, frame, margins)", "key pass (every point of 
 
 
 def build_prof():
-    if os.path.exists(LIB) and all(os.path.getmtime(LIB) > os.path.getmtime(os.path.join(nb.CSRC, f)) for f in os.listdir(nb.CSRC) if not f.endswith(".o")):
+    if os.path.exists(LIB) and all(os.path.getmtime(LIB) > os.path.getmtime(f) for f in nb.LIBRARIES["main"].files()):
         return
     objs = []
     for src in nb.SOURCES:
         if src != "dune.hip":
-            objs.append(os.path.join(nb.CSRC, src.replace(".hip", ".o")))
+            objs.append(os.path.join(nb.OBJ, src.replace(".hip", ".o")))
             continue
-        o = os.path.join(nb.CSRC, "dune.selprof.o")
+        o = os.path.join(nb.OBJ, "dune.selprof.o")
         subprocess.check_call([nb.hipcc_path(), *nb.FLAGS, "-DNPA_SEL_PROF=1", f'-DNPA_HIPCC_VERSION="{nb.hipcc_version()}"',
                                "-c", os.path.join(nb.CSRC, src), "-o", o], stderr=subprocess.DEVNULL)
         objs.append(o)
