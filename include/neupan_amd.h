@@ -680,6 +680,58 @@ int npa_curve_batch(int batch, int style, const double *start, const double *goa
                     double min_radius, int capacity, const int32_t *mask, double *rows_out, int32_t *n_rows,
                     void *stream);
 
+/* ---- goal fields: the cost-to-goal of every cell of an occupancy map (csrc/cycle.hip, csrc/curves.hip) -----------------
+ *
+ * The curves above know no walls.  An initial path through a map follows the cost-to-goal field of its goal downhill
+ * (neupan_amd/route.py, in PyTorch); the field itself, one shortest-path relaxation over every cell of the map and shared by
+ * every robot that drives to that goal, is this call.  The reference has nothing of the kind; this comment is the
+ * specification (tests/route_ref.py restates it as a heap Dijkstra on Python integers).
+ *
+ * Inputs: blocked [ny][nx] uint8, DEVICE, cell (i, j) at blocked[j nx + i], non-zero = not traversable.  Everything OUTSIDE
+ *   the array is blocked (npa_grid_scan, include/neupan_amd_grid.h, treats the outside as free: a beam may leave the map, a
+ *   route may not).  fields [n_fields][ny][nx] uint32, DEVICE, in and out.  changed [n_fields] uint32, DEVICE.
+ * Moves: the four axis steps at cost 5, the four diagonal steps at cost 7 (7 / 5 = 1.4 for sqrt 2).  A diagonal step from c
+ *   to c + (dx, dy) exists only if c + (dx, 0) and c + (0, dy) are both free: nothing squeezes between two blocked cells that
+ *   touch at a corner.  (The rule names the same two cells in both directions, so dist below is symmetric.)
+ * Result: with dist(s, c) the cost of the cheapest move sequence from s to c over free cells, the converged field is
+ *     d(c) = min over the free cells s with init(s) < NPA_ROUTE_UNREACHED of (init(s) + dist(s, c)),
+ *   NPA_ROUTE_UNREACHED where no such s reaches c.  The caller seeds: 0 in the goal cells, NPA_ROUTE_UNREACHED in every other
+ *   free cell; several seeds and seeds above 0 are allowed, a free cell's seed is at most NPA_ROUTE_UNREACHED.  The entries of
+ *   blocked cells are neither read nor written.  Integer and exact: with at most 2^26 cells a reached value is below 7 2^26
+ *   (seeds are the caller's to keep below 2^32 - 7 2^26), so v + 7 cannot wrap; the kernel adds only to values below
+ *   NPA_ROUTE_UNREACHED.
+ * One sweep is one launch: grid (ceil(nx / 16), ceil(ny / 16), n_fields), 256 threads, under 2 KB of LDS, no workspace, no
+ *   atomics.  A workgroup loads its 16 x 16 tile of one field and a one-cell halo into LDS -- blocked cells and cells outside
+ *   the array as NPA_ROUTE_BLOCKED --, relaxes the tile there for at most 16 rounds (a round: every thread takes the minimum of
+ *   its cell and its eight neighbours plus their move costs; barriers keep a round's reads in front of its writes) and leaves
+ *   early after a round in which no cell fell.  A thread whose cell ended lower than it began stores it to `fields` and stores
+ *   the sweep's mark, sweep_base + s + 1 for sweep s = 0 .. sweeps - 1 of this call, to changed[f].
+ * Why the result is exact, and the same bits in every run, without atomics or a barrier across workgroups:
+ *   (1) a cell of `fields` is written by its own thread alone, and only with a lower value;
+ *   (2) every value ever held is a seed plus the cost of a real move sequence from it (induction over the writes), so no value
+ *       is below d;
+ *   (3) a halo cell read while its own tile stores it yields the old or the new aligned 32-bit word, never a mixture: by (2)
+ *       either is sound;
+ *   (4) a sweep in which no cell fell stored nothing, so every workgroup of it read values nothing wrote meanwhile and found
+ *       no cell to lower in its tile (its last round changed nothing): the field is a fixed point of the relaxation;
+ *   (5) a fixed point f >= d equals d: along a cheapest move sequence from the minimising seed s to c, f(s) <= init(s), and
+ *       f(next) <= f(this) + cost at every move, so f(c) <= d(c).
+ *   Hence the converged field is unique -- whatever the timing, whatever `sweeps` per call.  Only the NUMBER of sweeps it took
+ *   may differ between runs.  After k sweeps every cell whose cheapest sequence has at most k moves is final (a sweep
+ *   relaxes every cell at least once against values at least as low as the previous sweep left), so nx ny + 1 sweeps always
+ *   suffice, and every loop of the kernel has a constant bound.
+ * The call issues `sweeps` launches on `stream` and does not synchronise.  The fields are converged iff, after the call,
+ *   changed[f] < sweep_base + sweeps for every f: the last sweep lowered nothing.  The caller zeroes `changed` once, reads it
+ *   after each call and passes the sweeps issued so far as the next sweep_base.
+ * NPA_E_ARG (before anything touches a device): blocked, fields or changed null; nx or ny < 1; n_fields outside 1 .. 65535
+ *   (a launch's z extent); sweeps < 1; sweep_base + sweeps beyond uint32.  NPA_E_UNSUPPORTED: nx ny > NPA_ROUTE_MAX_CELLS, or
+ *   ny > 16 * 65535 (a launch's y extent). */
+#define NPA_ROUTE_BLOCKED   0xFFFFFFFFu
+#define NPA_ROUTE_UNREACHED 0xFFFFFFFEu
+#define NPA_ROUTE_MAX_CELLS (1 << 26)
+int npa_route_relax(const uint8_t *blocked, int nx, int ny, int n_fields, uint32_t *fields, int sweeps,
+                    uint32_t sweep_base, uint32_t *changed, void *stream);
+
 /* ---- the bookkeeping of a device-resident closed loop (csrc/cycle.hip) -----------------------------------------------
  *
  * What the host does between the kernels of a control cycle, as three calls (and a fourth for fleets whose robots have goal

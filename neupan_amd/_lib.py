@@ -106,6 +106,7 @@ SYMBOLS = {
     "npa_curve_rows": (_I, [_I, _P, _P, C.c_double, C.c_double]),
     "npa_curve_generate": (_I, [_I, _P, _P, C.c_double, C.c_double, _I, _P, _P]),
     "npa_curve_batch": (_I, [_I, _I, _P, _P, _P, C.c_double, _I, _P, _P, _P, _P]),
+    "npa_route_relax": (_I, [_P, _I, _I, _I, _P, _I, C.c_uint32, _P, _P]),
     "npa_lon_loss": (_I, [_I, _I, _I] + [_P] * 7 + [C.c_float, C.c_double, _I, C.c_float, C.c_float] + [_P] * 11 + [_P]),
     "npa_lon_chain": (_I, [_I, _I, _I] + [_P] * 8 + [_P]),
     "npa_lon_adam": (_I, [_I, _I, _I] + [_P] * 6 + [C.c_float] * 7 + [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),

@@ -2,6 +2,8 @@
 //   npa_curve_rows, npa_curve_generate   the host's evaluation of curves.h: no kernel, no HIP runtime call (like pack_image.hip)
 //   npa_curve_batch                      B curves on the device, one wave per curve: the launch of curve_wave_kernel (cycle.hip),
 //                                        the kernel npa_cycle_retask runs -- one copy of the curve's device code in the library
+//   npa_route_relax                      the goal fields of a map (the header's "goal fields" block): the checks and the launches
+//                                        of route_sweep_kernel (cycle.hip)
 // The curve itself is curves.h, compiled for both sides.
 #include "curves.h"
 
@@ -12,6 +14,9 @@
 extern "C" hipError_t npa_launch_curve_batch(int batch, int style, const double* start, const double* goal, const double* interval,
                                              double min_radius, int capacity, const int* mask, double* rows_out, int* n_rows,
                                              hipStream_t stream);
+
+extern "C" hipError_t npa_launch_route_relax(const uint8_t* blocked, int nx, int ny, int n_fields, uint32_t* fields, int sweeps,
+                                             uint32_t sweep_base, uint32_t* changed, hipStream_t stream);
 
 namespace {
 
@@ -69,5 +74,24 @@ extern "C" int npa_curve_batch(int batch, int style, const double* start, const 
   if (what) return fail(NPA_E_ARG, what);
   HIP_TRY(npa_launch_curve_batch(batch, style, start, goal, interval, min_radius, capacity, mask, rows_out, n_rows,
                                  (hipStream_t)stream));
+  return NPA_OK;
+}
+
+// The goal fields of include/neupan_amd.h's "goal fields" block: `sweeps` launches of route_sweep_kernel (cycle.hip), no
+// synchronisation.  It lives in this unit beside the other export that only checks and launches.
+extern "C" int npa_route_relax(const uint8_t* blocked, int nx, int ny, int n_fields, uint32_t* fields, int sweeps,
+                               uint32_t sweep_base, uint32_t* changed, void* stream) {
+  const char* what = nullptr;                                    // (one message object, as npa_curve_batch)
+  int code = NPA_E_ARG;
+  if (!blocked || !fields || !changed) what = "npa_route_relax: a null pointer";
+  else if (nx < 1 || ny < 1) what = "npa_route_relax: nx, ny must be >= 1";
+  else if (n_fields < 1 || n_fields > 65535) what = "npa_route_relax: n_fields outside 1..65535";
+  else if (sweeps < 1 || (uint64_t)sweep_base + (uint64_t)sweeps > 0xFFFFFFFFull) what = "npa_route_relax: sweeps < 1 or sweep_base + sweeps beyond uint32";
+  else if ((int64_t)nx * ny > NPA_ROUTE_MAX_CELLS || ny > 16 * 65535) {
+    what = "npa_route_relax: more than NPA_ROUTE_MAX_CELLS cells, or more than 16 * 65535 rows";
+    code = NPA_E_UNSUPPORTED;
+  }
+  if (what) return fail(code, what);
+  HIP_TRY(npa_launch_route_relax(blocked, nx, ny, n_fields, fields, sweeps, sweep_base, changed, (hipStream_t)stream));
   return NPA_OK;
 }

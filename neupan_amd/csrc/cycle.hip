@@ -4,6 +4,8 @@
 //   cycle_commit_kernel  the collision latch and the cycle's log rows behind the plant step
 //   curve_wave_kernel    an arrived robot's next goal: a new curve into its region of the table       neupan.py:288-294, :314-318
 //                        (and, for npa_curve_batch, plain curves: csrc/curves.hip)
+//   route_sweep_kernel   not part of the cycle: one relaxation sweep of the goal fields behind npa_route_relax (csrc/curves.hip),
+//                        here because this unit has device code and the product library a size limit
 // One thread per robot (curve_wave_kernel: one wave), no workspace, no atomics; handle-free and stream-ordered like frontend.hip.  Every per-robot decision
 // is a select and every loop bound is a launch argument: the kernels only choose and copy, so a loop built from them gives
 // the bits of the host-paced loop (FleetPlanner.forward + run_closed_loop) whose rules they restate.
@@ -177,7 +179,75 @@ __global__ __launch_bounds__(npa_curve::kWave) void curve_wave_kernel(CurveWaveA
   if (word) *word = value;
 }
 
+// One sweep of npa_route_relax (include/neupan_amd.h, "goal fields"): a workgroup owns a 16 x 16 tile of one field, relaxes it
+// in LDS against a one-cell halo and stores the cells that fell.  Blocked cells and cells outside the array are BLOCKED in LDS,
+// so the rounds test values only.  No atomics: a cell of `fields` is written by its own thread alone and only ever lower; the
+// halo may be read while a neighbouring tile stores it -- the old or the new word, both lengths of real paths (the header has
+// the whole argument).  Arguments in one struct, as CurveWaveArgs.
+constexpr int RT_TILE = 16, RT_SPAN = RT_TILE + 2, RT_ROUNDS = 16;
+
+struct RouteArgs {
+  const uint8_t* blocked;
+  uint32_t *fields, *changed;
+  int nx, ny;
+  uint32_t mark;
+};
+
+__global__ __launch_bounds__(RT_TILE* RT_TILE) void route_sweep_kernel(RouteArgs a) {
+  __shared__ uint32_t tile[RT_SPAN * RT_SPAN];
+  const int tid = threadIdx.x, i0 = blockIdx.x * RT_TILE - 1, j0 = blockIdx.y * RT_TILE - 1;
+  uint32_t* field = a.fields + (size_t)blockIdx.z * ((size_t)a.nx * a.ny);
+  for (int k = tid; k < RT_SPAN * RT_SPAN; k += RT_TILE * RT_TILE) {
+    const int i = i0 + k % RT_SPAN, j = j0 + k / RT_SPAN;
+    uint32_t v = NPA_ROUTE_BLOCKED;
+    if (i >= 0 && i < a.nx && j >= 0 && j < a.ny) {
+      const int c = j * a.nx + i;                             // (nx ny <= NPA_ROUTE_MAX_CELLS: an int)
+      if (a.blocked[c] == 0) v = field[c];
+    }
+    tile[k] = v;
+  }
+  __syncthreads();
+  const int at = ((tid >> 4) + 1) * RT_SPAN + (tid & 15) + 1;
+  const uint32_t began = tile[at];
+  uint32_t v = began;
+#pragma nounroll
+  for (int round = 0; round < RT_ROUNDS; ++round) {
+    const uint32_t e = tile[at + 1], w = tile[at - 1], n = tile[at + RT_SPAN], s = tile[at - RT_SPAN];
+    uint32_t m = v;
+    // (a value below UNREACHED is below 7 * 2^26: the sums cannot wrap)
+    m = e < NPA_ROUTE_UNREACHED ? min(m, e + 5u) : m;
+    m = w < NPA_ROUTE_UNREACHED ? min(m, w + 5u) : m;
+    m = n < NPA_ROUTE_UNREACHED ? min(m, n + 5u) : m;
+    m = s < NPA_ROUTE_UNREACHED ? min(m, s + 5u) : m;
+    const bool fe = e != NPA_ROUTE_BLOCKED, fw = w != NPA_ROUTE_BLOCKED, fn = n != NPA_ROUTE_BLOCKED, fs = s != NPA_ROUTE_BLOCKED;
+    const uint32_t ne = tile[at + RT_SPAN + 1], nw = tile[at + RT_SPAN - 1], se = tile[at - RT_SPAN + 1], sw = tile[at - RT_SPAN - 1];
+    m = (fe && fn && ne < NPA_ROUTE_UNREACHED) ? min(m, ne + 7u) : m;
+    m = (fw && fn && nw < NPA_ROUTE_UNREACHED) ? min(m, nw + 7u) : m;
+    m = (fe && fs && se < NPA_ROUTE_UNREACHED) ? min(m, se + 7u) : m;
+    m = (fw && fs && sw < NPA_ROUTE_UNREACHED) ? min(m, sw + 7u) : m;
+    const bool fell = began != NPA_ROUTE_BLOCKED && m < v;
+    if (!__syncthreads_or(fell)) break;                       // (also: every read of this round is in front of its writes)
+    if (fell) tile[at] = v = m;
+    __syncthreads();
+  }
+  if (v < began) {                                            // (a blocked or outside cell kept `began`)
+    field[(j0 + 1 + (tid >> 4)) * a.nx + i0 + 1 + (tid & 15)] = v;
+    a.changed[blockIdx.z] = a.mark;
+  }
+}
+
 }  // namespace
+
+extern "C" hipError_t npa_launch_route_relax(const uint8_t* blocked, int nx, int ny, int n_fields, uint32_t* fields, int sweeps,
+                                             uint32_t sweep_base, uint32_t* changed, hipStream_t stream) {
+  RouteArgs a = {blocked, fields, changed, nx, ny, sweep_base};
+  const dim3 grid((nx + RT_TILE - 1) / RT_TILE, (ny + RT_TILE - 1) / RT_TILE, n_fields);
+  for (int s = 0; s < sweeps; ++s) {
+    a.mark = sweep_base + (uint32_t)s + 1u;
+    hipLaunchKernelGGL(route_sweep_kernel, grid, dim3(RT_TILE * RT_TILE), 0, stream, a);
+  }
+  return hipGetLastError();
+}
 
 extern "C" hipError_t npa_launch_curve_batch(int batch, int style, const double* start, const double* goal, const double* interval,
                                              double min_radius, int capacity, const int* mask, double* rows_out, int* n_rows,
