@@ -244,3 +244,192 @@ def clearance_cases(rect=RECT):
         out[name + "_fine"] = (fine, (-1.5, -1.5), 0.05, V, np.array([[-0.05, 0.02, 0.4], [0.9, -0.6, 2.0]]), 1.0)
         out[name + "_coarse"] = (coarse, (-4.0, -4.0), 8.0, V, np.array([[0.3, -0.2, 1.0], [5.2, 0.3, 0.1]]), 1.0)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- the edge cases
+# (tests/test_grid_edges_gpu.py; tests/test_grid.py replays the kernel's window and trip schedule over them on the CPU)
+DENSE_POSES = np.array([[0.05, -0.03, 0.4], [0.25, 0.1, 1.1], [0.9, 0.2, 0.3], [2.6, 2.5, 0.7]])
+DENSE_ORIGIN, DENSE_RES, DENSE_REACH = (-3.2, -3.2), 0.1, 1.0
+ANNEX_POSE = np.array([6.4, 0.0, 0.2])             # in the middle of dense_map(64)'s free annex: an empty window
+
+
+def dense_map(annex=0):
+    """64 x 64 cells of 0.1 m from (-3.2, -3.2), occupied where the centre is farther than 1.6 m from (0, 0); annex: that
+    many free columns to its right (a robot there has an empty window)"""
+    c = DENSE_ORIGIN[0] + (np.arange(64) + 0.5) * DENSE_RES
+    occ = (np.hypot(c[None, :], c[:, None]) > 1.6).astype(np.uint8)
+    return np.concatenate([occ, np.zeros((64, annex), dtype=np.uint8)], axis=1)
+
+
+def polygon(E):
+    """a convex counter-clockwise E-gon: E points of the ellipse 1.25 x 0.8 at uneven, increasing angles (circumradius <= 1.25)"""
+    k = np.arange(E)
+    a = 2.0 * np.pi * (k + 0.25 * np.sin(2.1 * k + E)) / E
+    return np.stack([1.25 * np.cos(a), 0.8 * np.sin(a)], axis=1)
+
+
+def cross_products(V):
+    """the cross product of every pair of consecutive edges: all positive iff V is strictly convex and counter-clockwise"""
+    E = np.roll(V, -1, axis=0) - V
+    F = np.roll(E, -1, axis=0)
+    return E[:, 0] * F[:, 1] - E[:, 1] * F[:, 0]
+
+
+def dense_shapes():
+    return {"rect": RECT, "tri": TRI, **{f"e{E}": polygon(E) for E in (5, 6, 7, 8)}}
+
+
+# Counted windows: 16 x 16 cells of 0.25 m from (-2, -2) and a reach that makes the whole grid every robot's window, so the
+# queue position of a cell is its rank among the occupied cells in row-major order.  The robot stands OUTSIDE the grid with
+# TRI's nose 0.1 m from one cell, the target; every other cell within 0.01 m of that distance stays free, so the target is the
+# strictly nearest occupied cell, and exactly `p` occupied cells come before it and K - 1 - p after it.
+COUNT_ORIGIN, COUNT_RES, COUNT_N, COUNT_REACH = (-2.0, -2.0), 0.25, 16, 6.0
+COUNT_K = (63, 64, 65, 127, 128, 129, 192)
+COUNT_STAND = {"low": (0.1, -2.6, np.pi / 2),       # below the grid: the target is cell 8 of row 0 (window index 8)
+               "mid": (-2.6, -0.6, 0.0),            # left of it: cell 0 of row 5 (index 80)
+               "high": (0.1, 2.6, -np.pi / 2)}      # above it: cell 8 of row 15 (index 248)
+COUNT_TARGET = {"low": 8, "mid": 80, "high": 248}
+COUNT_SEPARATION = 0.01
+
+
+def _spread(pool, n):
+    """n of the sorted indices `pool`, evenly spread over it"""
+    assert 0 <= n <= len(pool), (n, len(pool))
+    return [pool[int(q)] for q in np.floor(np.arange(n) * (len(pool) / max(n, 1)))]
+
+
+def counted_window(K, p):
+    """(occ, pose, window index of the target) with K occupied cells, the strictly nearest of them at queue position p"""
+    stand = "low" if p == 0 else ("high" if p == K - 1 else "mid")
+    pose, n = np.array(COUNT_STAND[stand]), COUNT_N
+    key = ("count_d", stand)
+    if key not in _REF:
+        Vw = wr.world_vertices(TRI, pose)
+        _REF[key] = np.array([box_polygon(Vw, _box(COUNT_ORIGIN, COUNT_RES, k % n, k // n))[0] for k in range(n * n)])
+    d = _REF[key]
+    t = int(np.argmin(d))
+    assert t == COUNT_TARGET[stand] and 0.09 < d[t] < 0.11, (stand, t, d[t])
+    free = d > d[t] + COUNT_SEPARATION
+    before, after = [k for k in range(t) if free[k]], [k for k in range(t + 1, n * n) if free[k]]
+    occ = np.zeros(n * n, dtype=np.uint8)
+    occ[_spread(before, p) + [t] + _spread(after, K - 1 - p)] = 1
+    assert occ.sum() == K and occ[:t].sum() == p
+    return occ.reshape(n, n), pose, t
+
+
+def counted_positions(K):
+    """first, the 64th, the 65th (the first cell ever carried), last -- those a window of K cells has"""
+    return sorted({p for p in (0, 63, 64, K - 1) if p < K})
+
+
+def fill_127():
+    """63 occupied cells in the first 64 of the window and all of the next 64: the fullest queue the schedule can reach, 127.
+    Rows 8 .. 15 are free; the robot stands in them, TRI's nose 0.1 m above cell 8 of row 7."""
+    occ = np.zeros(COUNT_N * COUNT_N, dtype=np.uint8)
+    occ[1:128] = 1
+    return occ.reshape(COUNT_N, COUNT_N), np.array([0.1, 0.6, -np.pi / 2])
+
+
+# robots at the border of the fixture map (x in [-5, 5], y in [-4, 4], a wall of one cell all round), reach 0.6
+BORDER_ACROSS = np.array([[4.6, 0.3, 0.2],                 # across the right wall
+                          [-4.9, 3.9, 2.0],                # across the upper left corner
+                          [0.3, -4.4, 1.0]])               # across the bottom wall, most of it outside
+BORDER_NEAR = {"rect": np.array([[6.3, 0.5, 0.1],          # outside, within reach of the right wall
+                                 [0.3, -5.3, 1.3],         # ... below the bottom wall
+                                 [-5.9, -4.9, 0.5]]),      # ... off the lower left corner
+               "tri": np.array([[5.6, 0.5, 0.1], [0.3, -4.6, 1.3], [-5.4, -4.4, 0.5]])}
+BORDER_BEYOND = np.array([[7.5, 0.0, 0.3], [-1.0, 6.5, -0.4], [-40.0, -33.0, 2.2]])      # outside, beyond reach: +inf
+
+
+def edge_clearance_cases():
+    """the clearance cases of tests/test_grid_edges_gpu.py against the restatement, in clearance_cases()' format: the dense map
+    (windows of hundreds of occupied cells: the queue fills, overflows, carries and drains) with E = 3 .. 8, the counted
+    windows, and robots at, across and beyond the border of the fixture map"""
+    out = {}
+    for name, V in dense_shapes().items():
+        out[name + "_dense"] = (dense_map(), DENSE_ORIGIN, DENSE_RES, np.asarray(V, dtype=np.float64), DENSE_POSES, DENSE_REACH)
+    for K in COUNT_K:
+        for p in counted_positions(K):
+            occ, pose, _ = counted_window(K, p)
+            out[f"count_{K}_at_{p}"] = (occ, COUNT_ORIGIN, COUNT_RES, TRI, pose[None, :], COUNT_REACH)
+    occ, pose = fill_127()
+    out["count_fill_127"] = (occ, COUNT_ORIGIN, COUNT_RES, TRI, pose[None, :], COUNT_REACH)
+    fx = (fixture_map(), ORIGIN, RES)
+    for name, V in (("rect", RECT), ("tri", TRI)):
+        out[name + "_border"] = fx + (np.asarray(V, dtype=np.float64), np.concatenate([BORDER_ACROSS, BORDER_NEAR[name], BORDER_BEYOND]), 0.6)
+    return out
+
+
+def ref_clearance(name):
+    """(c_g [B], margin [B]) of edge_clearance_cases()[name] by the restatement, made once and never written to"""
+    key = ("clearance", name)
+    if key not in _REF:
+        occ, origin, res, V, poses, reach = edge_clearance_cases()[name]
+        got = np.array([clearance(occ, origin, res, V, st, reach) for st in poses])
+        got.setflags(write=False)
+        _REF[key] = got
+    return _REF[key][:, 0], _REF[key][:, 1]
+
+
+# Decided at heading 0 (cos 0 = 1 and sin 0 = 0 on host and device): RECT at (0.8, 1.0, 0) has its lower left vertex at (0, 0)
+# exactly, its left edge on x = 0 and its upper edge on y = 2, and the faces of a map of 0.25 m cells from (-2, -2) are dyadic.
+# One occupied cell (i, j) each; the expectation is derived by hand and exact.
+DECIDED_ORIGIN, DECIDED_RES, DECIDED_N, DECIDED_POSE = (-2.0, -2.0), 0.25, 20, (0.8, 1.0, 0.0)
+DECIDED = [  # (what, cell (i, j), reach, expected)
+    ("the left edge flush with a cell's right face", (7, 10), 1.0, 0.0),             # the cell [-0.25, 0] x [0.5, 0.75]
+    ("the upper edge flush with a cell's lower face", (10, 16), 1.0, 0.0),           # [0.5, 0.75] x [2, 2.25]
+    ("a vertex on a cell's corner", (7, 7), 1.0, 0.0),                               # [-0.25, 0] x [-0.25, 0] meets (0, 0)
+    ("a gap of one cell, reach equal to it", (6, 10), 0.25, 0.25),                   # [-0.5, -0.25] x [0.5, 0.75]
+    ("a gap of one cell, reach 2^-20 less", (6, 10), 0.25 - 2.0 ** -20, np.inf),
+    ("a gap of one cell off the corner, reach above it", (6, 6), 0.5, float(np.sqrt(0.125))),   # [-0.5, -0.25]^2: the diagonal
+]
+
+
+def decided_map(cell):
+    occ = np.zeros((DECIDED_N, DECIDED_N), dtype=np.uint8)
+    occ[cell[1], cell[0]] = 1
+    return occ
+
+
+# ---- the scan
+def ref_scan_bearing_only(p):
+    """ref_scan of the fixture map with std = 0 and NOISE's angle_std: the plain cast at the turned angle"""
+    key = ("bearing", p)
+    if key not in _REF:
+        occ, origin, res = maps()["fixture"]
+        lo, hi = LIMITS[p]
+        g = host_draws(NOISE["seed"], p, 0, N_BEAMS[p])
+        _REF[key] = scan(occ, origin, res, POSES[p], N_BEAMS[p], lo, hi, RMAX, OFFSET, 0.0, NOISE["angle_std"], g)
+    return _REF[key]
+
+
+# Translation: the fixture map and the poses moved by (2^20, -2^21).  Every pose coordinate is a multiple of 2^-10, so every face
+# and every (face - origin of the ray) is exact and the same in both runs; the heading is untouched.
+SHIFT = (2.0 ** 20, -(2.0 ** 21))
+SHIFT_POSES = np.array([[-1139, 379, 0.3], [2663, -615, 2.0], [-7475, 1239, 0.05], [300, 6500, -1.5], [5800, -4700, 2.4],
+                        [-5120, -1024, 0.0]]) * np.array([2.0 ** -10, 2.0 ** -10, 1.0])
+SHIFT_BEAMS = 257
+
+
+def ref_scan_shift(p):
+    """the fixture map from SHIFT_POSES[p] at its own origin, SHIFT_BEAMS beams over the full circle, no sensor offset"""
+    key = ("shift", p)
+    if key not in _REF:
+        _REF[key] = scan(fixture_map(), ORIGIN, RES, SHIFT_POSES[p], SHIFT_BEAMS, -np.pi, np.pi, RMAX)
+    return _REF[key]
+
+
+# A ray along a face: 12 x 10 cells of 0.25 m from (-1, -1); the ray starts at (-0.87, Y(4)) = (-0.87, 0) with d = (1, 0).
+FACE_ORIGIN, FACE_RES, FACE_ROW, FACE_START = (-1.0, -1.0), 0.25, 4, (-0.87, 0.0)
+
+
+def face_maps():
+    """{name: (occ, rows the ray touches)}: cells in row 4 only, in row 3 only, and in both (the same columns)"""
+    out = {}
+    for name, rows in (("above", (4,)), ("below", (3,)), ("both", (3, 4))):
+        occ = np.zeros((10, 12), dtype=np.uint8)
+        for j in rows:
+            occ[j, 5] = occ[j, 9] = 1
+        occ[7, 3] = occ[1, 6] = 1                    # cells the ray never meets
+        out[name] = occ
+    return out

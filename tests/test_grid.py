@@ -172,6 +172,145 @@ def test_the_excluded_share_is_within_the_cap_on_every_fixture():
         for st in poses:
             c, margin = gr.clearance(occ, origin, res, V, st, reach)
             assert margin >= gr.CLEARANCE_MARGIN, (name, st, c, margin)
+    # the edge cases of tests/test_grid_edges_gpu.py: the clearance (none excluded), the bearing-only noise, the moved map
+    for name, (_, _, _, _, poses, _) in gr.edge_clearance_cases().items():
+        c, margin = gr.ref_clearance(name)
+        print(name, "clearance", c.tolist(), "smallest margin", float(margin.min()))
+        assert len(c) == len(poses) and (margin >= gr.CLEARANCE_MARGIN).all(), (name, c, margin)
+    for what, ref, count in (("bearing noise alone", gr.ref_scan_bearing_only, len(gr.POSES)), ("moved map", gr.ref_scan_shift, len(gr.SHIFT_POSES))):
+        ill = np.concatenate([ref(p)["ill"] for p in range(count)])
+        print(what, int(ill.sum()), "of", ill.size)
+        assert ill.sum() <= gr.EXCLUDED_CAP * ill.size
+
+
+# ---------------------------------------------------------------------------------------------------- the clearance's queue
+def window(occ, origin, res, V, pose, reach):
+    """(i0, i1, j0, j1) of grid_clearance_kernel: the header's window rule with the kernel's extra cell, clamped to the grid"""
+    import world_ref as wr
+    ny, nx = np.asarray(occ).shape
+    Vw = wr.world_vertices(V, pose)
+
+    def clamp(v, n):
+        return int(min(max(v, 0.0), float(n - 1)))
+    i0 = clamp(math.floor(((Vw[:, 0].min() - reach) - origin[0]) / res) - 1.0, nx)
+    i1 = clamp(math.floor(((Vw[:, 0].max() + reach) - origin[0]) / res) + 1.0, nx)
+    j0 = clamp(math.floor(((Vw[:, 1].min() - reach) - origin[1]) / res) - 1.0, ny)
+    j1 = clamp(math.floor(((Vw[:, 1].max() + reach) - origin[1]) / res) + 1.0, ny)
+    return i0, i1, j0, j1
+
+
+def schedule(occ, win):
+    """The kernel's trips over a window, replayed: every trip gathers the occupied ones of the next 64 cells; a batch is
+    measured when 64 or more are queued or the window has ended, the rest is carried to the front.  Returns dict(occupied,
+    fills: the queue's fill at every measurement, batches, carries, drains: measurements after the window had ended)."""
+    i0, i1, j0, j1 = win
+    cells = (np.asarray(occ)[j0:j1 + 1, i0:i1 + 1] != 0).ravel()          # window order: k = (j - j0) * wn + (i - i0)
+    total, queued, k0 = cells.size, 0, 0
+    fills, carries, drains = [], 0, 0
+    while k0 < total or queued > 0:
+        if k0 < total:
+            assert queued < 64
+            queued += int(cells[k0:k0 + 64].sum())
+            if queued < 64 and k0 + 64 < total:
+                k0 += 64
+                continue
+        else:
+            drains += 1
+        assert queued <= 128
+        take = min(queued, 64)
+        if take:
+            fills.append(queued)
+        carries += queued > take
+        queued -= take
+        k0 += 64
+    return dict(occupied=int(cells.sum()), fills=fills, batches=len(fills), carries=int(carries), drains=drains)
+
+
+def test_the_new_clearance_cases_fill_overflow_carry_and_drain_the_queue():
+    """what tests/test_grid_edges_gpu.py's clearance cases are for, and what the older cases never did"""
+    for name, (occ, origin, res, V, poses, reach) in gr.clearance_cases().items():
+        for st in poses:
+            s = schedule(occ, window(occ, origin, res, V, st, reach))
+            assert s["carries"] == 0 and s["drains"] == 0 and s["batches"] <= 1 and s["occupied"] < 64, (name, st, s)
+    seen = []
+    for name, (occ, origin, res, V, poses, reach) in gr.edge_clearance_cases().items():
+        for b, st in enumerate(poses):
+            s = schedule(occ, window(occ, origin, res, V, st, reach))
+            print(f"{name} pose {b}: E {len(V)}, {s['occupied']} occupied, {s['batches']} batches, {s['carries']} carries, "
+                  f"{s['drains']} drains after the end, fills {s['fills']}")
+            seen.append(s)
+    fills = [f for s in seen for f in s["fills"]]
+    print("largest fill", max(fills), "most batches", max(s["batches"] for s in seen), "most carries", max(s["carries"] for s in seen))
+    assert 64 in fills and any(64 < f < 127 for f in fills) and max(fills) == 127                # (127 = 63 left + 64 gathered)
+    assert max(s["carries"] for s in seen) >= 8 and max(s["batches"] for s in seen) > 8
+    assert any(s["drains"] for s in seen)
+    # the batch test's neighbour in the free annex of the dense map has an empty window
+    occ = gr.dense_map(64)
+    for V in gr.dense_shapes().values():
+        assert schedule(occ, window(occ, gr.DENSE_ORIGIN, gr.DENSE_RES, V, gr.ANNEX_POSE, gr.DENSE_REACH))["occupied"] == 0
+
+
+def test_the_polygons_are_convex_and_the_dense_map_is_the_stated_one():
+    shapes = gr.dense_shapes()
+    assert [len(shapes[k]) for k in ("tri", "rect", "e5", "e6", "e7", "e8")] == [3, 4, 5, 6, 7, 8]
+    for name, V in shapes.items():
+        V = np.asarray(V)
+        assert (gr.cross_products(V) > 0).all() and np.hypot(V[:, 0], V[:, 1]).max() < 1.3, name
+    occ = gr.dense_map()
+    assert occ.shape == (64, 64) and occ[0, 0] == 1 and occ[32, 32] == 0 and occ[32, 47] == 0 and occ[32, 48] == 1   # centres 1.55, 1.65
+    assert (gr.dense_map(64)[:, :64] == occ).all() and not gr.dense_map(64)[:, 64:].any()
+    got = np.concatenate([gr.ref_clearance(k + "_dense")[0] for k in shapes])
+    assert (got == 0).any() and np.isinf(got).any() and ((got > 0) & np.isfinite(got)).any()
+    assert all(np.isfinite(gr.ref_clearance(k + "_dense")[0][1]) and gr.ref_clearance(k + "_dense")[0][1] > 0 for k in shapes)
+
+
+def test_the_counted_windows_hold_their_cell_at_its_queue_position():
+    import world_ref as wr
+    n, count = gr.COUNT_N, 0
+    for K in gr.COUNT_K:
+        assert gr.counted_positions(K) == sorted({0, K - 1} | ({63} if K > 63 else set()) | ({64} if K > 64 else set()))
+        for p in gr.counted_positions(K):
+            occ, pose, t = gr.counted_window(K, p)
+            assert window(occ, gr.COUNT_ORIGIN, gr.COUNT_RES, gr.TRI, pose, gr.COUNT_REACH) == (0, n - 1, 0, n - 1)    # total = 256
+            flat = occ.ravel()
+            assert flat.sum() == K and flat[t] == 1 and flat[:t].sum() == p                    # K cells, the target the p-th
+            Vw = wr.world_vertices(gr.TRI, pose)
+            d = np.array([gr.box_polygon(Vw, gr._box(gr.COUNT_ORIGIN, gr.COUNT_RES, k % n, k // n))[0] for k in np.nonzero(flat)[0]])
+            order = np.sort(d)
+            assert d[p] == order[0] and order[1] - order[0] > 1e-3 and order[0] > 0.0, (K, p, order[:3])   # strictly nearest
+            assert gr.ref_clearance(f"count_{K}_at_{p}")[0][0] == order[0]
+            count += 1
+    assert count == 23
+    occ, pose = gr.fill_127()
+    assert occ.sum() == 127 and window(occ, gr.COUNT_ORIGIN, gr.COUNT_RES, gr.TRI, pose, gr.COUNT_REACH) == (0, n - 1, 0, n - 1)
+    assert schedule(occ, (0, n - 1, 0, n - 1))["fills"] == [127, 63]
+
+
+def test_the_border_decided_and_scan_cases_hold_what_they_are_for():
+    for shape in ("rect", "tri"):
+        c = gr.ref_clearance(shape + "_border")[0]
+        assert (c[:3] == 0).all() and (np.isfinite(c[3:6]) & (c[3:6] > 0)).all() and np.isinf(c[6:]).all(), (shape, c)
+    # the decided cases sit ON a decision, where the restatement has no margin; it agrees with the hand-made value all the same
+    for what, cell, reach, want in gr.DECIDED:
+        c, margin = gr.clearance(gr.decided_map(cell), gr.DECIDED_ORIGIN, gr.DECIDED_RES, gr.RECT, gr.DECIDED_POSE, reach)
+        assert c == want or abs(c - want) <= 1e-12, (what, c, want)
+    assert sum(m < gr.CLEARANCE_MARGIN for m in (gr.clearance(gr.decided_map(cell), gr.DECIDED_ORIGIN, gr.DECIDED_RES, gr.RECT,
+                                                             gr.DECIDED_POSE, reach)[1] for _, cell, reach, _ in gr.DECIDED)) >= 5
+    # bearing noise alone turns beams: the hits are not the plain scan's
+    assert any((gr.ref_scan_bearing_only(p)["ranges"] != gr.ref_scan("fixture", p)["ranges"]).any() for p in range(len(gr.POSES)))
+    # the moved map: poses inside and outside the grid, on multiples of 2^-10, and the shift keeps them so
+    P = gr.SHIFT_POSES
+    assert (P[:, :2] * 1024 == np.round(P[:, :2] * 1024)).all() and ((P[:, :2] + gr.SHIFT) - gr.SHIFT == P[:, :2]).all()
+    inside = (np.abs(P[:, 0]) < 5) & (np.abs(P[:, 1]) < 4)
+    assert inside.sum() >= 2 and (~inside).sum() >= 2
+    assert all((gr.ref_scan_shift(p)["hit"] == gr.HIT_GRID).any() for p in range(len(P)))
+    # a ray along a face: the closed boxes of both rows are touched, at the same time; without the touched rows it is a miss
+    o, d = gr.FACE_START, (1.0, 0.0)
+    assert gr.faces(gr.FACE_ORIGIN[1], gr.FACE_RES, 10)[gr.FACE_ROW] == o[1]
+    for name, occ in gr.face_maps().items():
+        bare = occ.copy()
+        bare[[gr.FACE_ROW - 1, gr.FACE_ROW], :] = 0
+        assert gr.cast(occ, gr.FACE_ORIGIN, gr.FACE_RES, o, d) == 0.25 - (-0.87) and gr.cast(bare, gr.FACE_ORIGIN, gr.FACE_RES, o, d) == np.inf
 
 
 def test_the_fixtures_hold_the_cases_they_are_for():
