@@ -178,9 +178,14 @@ int npa_set_adjust_batch(npa_handle *h, const float *theta, int batch);
 size_t npa_workspace_bytes(const npa_handle *h, int batch);
 size_t npa_state_bytes(const npa_handle *h, int batch);
 /* Byte offsets inside the workspace of the arrays a caller may look at BETWEEN npa_forward_iter calls (stream-ordered),
- * out[0..n), n <= 8: the working nominal cur_s [B][3][T+1], cur_u [B][2][T], cur_d [B][T], and the sorted rows the last
+ * out[0..n), n <= 9: the working nominal cur_s [B][3][T+1], cur_u [B][2][T], cur_d [B][T], and the sorted rows the last
  * selection launch emitted -- mu [B][T+1][M][E], lam [B][T+1][M][2], pts [B][T+1][M][2], dist [B][T+1][M], count [B][T+1]
- * (int32): the layout of npa_dune_stage's outputs, so a gradient pass can reuse them instead of re-running the stage. */
+ * (int32): the layout of npa_dune_stage's outputs, so a gradient pass can reuse them instead of re-running the stage.
+ * n = 9 adds out[8], the dispatch-order block of the QP launches (int32; diagnostics): cnt [K][32] -- per QP launch of the
+ * forward call, how many scenes it filed under each class of iteration counts (class c: 31 - c iterations, clamped) --, then
+ * list [2][32][B] -- the scenes of each class, ping-pong by launch parity --, then ticket [B], the workgroup a scene was last
+ * solved under.  Launch j hands its scenes out in the order of row j - 1's lists, the longest solves first; a handle created
+ * with NPA_QP_ORDER=0 in the environment uses scene order and files nothing (the results are the same bits either way). */
 int npa_workspace_layout(const npa_handle *h, int batch, size_t *out, int n);
 /* Byte offset inside the workspace of the per-scene QP diagnostics written by the last NRMP launch
  * of npa_forward_batch: [B][16] doubles per scene:

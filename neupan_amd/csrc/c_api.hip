@@ -46,7 +46,8 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                                     float* out_s, float* out_u, float* out_d, float* out_min_distance,
                                     int* out_iters, float* out_nrmp_points, int* flags, float* state,
                                     double* qp_info, double* warm, float* trig_out, float* dbg_abc, float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta);
+                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta,
+                                    QpSched sched);
 extern "C" int npa_select_geo_group_supported(int E);
 extern "C" hipError_t npa_launch_select_geo_group(const DevParams& P, const SelGeoGroup& G, int n, int batch, int t0, int n_stride_max,
                                                   int debug, unsigned audit_thresh, float margin_scale, int rows_bf16,
@@ -84,17 +85,18 @@ static int check_theta_batch(const npa_handle* h, int batch, const char* who) {
 
 extern "C" size_t npa_workspace_bytes(const npa_handle* h, int batch) {
   if (!h || batch < 1) return 0;
-  return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h)).total * sizeof(float);
+  return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h), h->P.K).total * sizeof(float);
 }
 extern "C" size_t npa_workspace_qp_info_offset(const npa_handle* h, int batch) {
   if (!h || batch < 1) return 0;
-  return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h)).qp_info * sizeof(float);
+  return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h), h->P.K).qp_info * sizeof(float);
 }
 extern "C" int npa_workspace_layout(const npa_handle* h, int batch, size_t* out, int n) {
   if (!h || batch < 1 || !out || n < 1) return fail(NPA_E_ARG, "npa_workspace_layout: bad argument");
-  const ScratchLayout L = npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h));
-  const size_t v[8] = {L.cur_s * 4, L.cur_u * 4, L.cur_d * 4, L.mu * 4, L.lam * 4, L.pts * 4, L.dist * 4, L.count * 4};
-  for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+  const ScratchLayout L = npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h), h->P.K);
+  // ([8]: the dispatch-order block of the QP launches -- cnt [K][32], list [2][32][batch], ticket [batch], ints; pan_common.h)
+  const size_t v[9] = {L.cur_s * 4, L.cur_u * 4, L.cur_d * 4, L.mu * 4, L.lam * 4, L.pts * 4, L.dist * 4, L.count * 4, L.sched * 4};
+  for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
   return NPA_OK;
 }
 extern "C" size_t npa_state_bytes(const npa_handle* h, int batch) {
@@ -197,7 +199,8 @@ extern "C" int npa_nrmp_stage(npa_handle* h, int batch, const float* nom_s, cons
   if (int rc = check_theta_batch(h, batch, "npa_nrmp_stage")) return rc;
   HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
                         out_s, out_u, out_d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        qp_info, nullptr, nullptr, nullptr, nullptr, x64, (hipStream_t)stream, nullptr, nullptr, h->theta));
+                        qp_info, nullptr, nullptr, nullptr, nullptr, x64, (hipStream_t)stream, nullptr, nullptr, h->theta,
+                        QpSched{nullptr, nullptr, nullptr, nullptr, nullptr}));
   return NPA_OK;
 }
 
@@ -211,7 +214,8 @@ extern "C" int npa_nrmp_params(npa_handle* h, int batch, const float* nom_s, con
   HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, nom_s, nom_u, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                         nullptr, nullptr, nullptr, out_abc, h->P.M > 0 ? out_f : nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr,
-                        nullptr));         // (the linearisation and the hinge rows do not depend on the adjust parameters)
+                        nullptr,           // (the linearisation and the hinge rows do not depend on the adjust parameters)
+                        QpSched{nullptr, nullptr, nullptr, nullptr, nullptr}));
   return NPA_OK;
 }
 
@@ -240,7 +244,8 @@ extern "C" int npa_nrmp_backward(npa_handle* h, int batch, const float* nom_s, c
 __global__ void stage_kernel(float* __restrict__ cur_s, const float* __restrict__ nom_s, size_t ns,
                              float* __restrict__ cur_u, const float* __restrict__ nom_u, size_t nu,
                              int* __restrict__ flags, size_t nflag, int* __restrict__ count, size_t ncount,
-                             int* __restrict__ state, size_t nstate, float* __restrict__ trig, int T) {
+                             int* __restrict__ state, size_t nstate, float* __restrict__ trig, int T,
+                             int* __restrict__ sched_cnt, size_t nsched) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;; i += stride) {
     bool any = false;
@@ -255,16 +260,18 @@ __global__ void stage_kernel(float* __restrict__ cur_s, const float* __restrict_
     if (i < nflag) { flags[i] = 0; any = true; }
     if (i < ncount) { count[i] = 0; any = true; }
     if (i < nstate) { state[i] = 0; any = true; }
+    if (i < nsched) { sched_cnt[i] = 0; any = true; }      // the class counters of every QP launch of the call (pan_common.h)
     if (!any) break;
   }
 }
 
 // stage_kernel for a group of forward calls of one size (merged launches, pan_common.h): blockIdx.y = the call
-__global__ void stage_group_kernel(StageGroup G, size_t ns, size_t nu, size_t nflag, size_t ncount, size_t nstate, int T) {
+__global__ void stage_group_kernel(StageGroup G, size_t ns, size_t nu, size_t nflag, size_t ncount, size_t nstate, int T,
+                                   size_t nsched) {
   const StageCall& q = G.c[blockIdx.y];
   float* __restrict__ cur_s = q.cur_s; const float* __restrict__ nom_s = q.nom_s; float* __restrict__ cur_u = q.cur_u;
   const float* __restrict__ nom_u = q.nom_u; int* __restrict__ flags = q.flags; int* __restrict__ count = q.count;
-  int* __restrict__ state = q.state; float* __restrict__ trig = q.trig;
+  int* __restrict__ state = q.state; float* __restrict__ trig = q.trig; int* __restrict__ sched_cnt = q.sched_cnt;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;; i += stride) {
     bool any = false;
@@ -279,8 +286,26 @@ __global__ void stage_group_kernel(StageGroup G, size_t ns, size_t nu, size_t nf
     if (i < nflag) { flags[i] = 0; any = true; }
     if (i < ncount) { count[i] = 0; any = true; }
     if (i < nstate) { state[i] = 0; any = true; }
+    if (i < nsched) { sched_cnt[i] = 0; any = true; }      // the class counters of every QP launch of the call (pan_common.h)
     if (!any) break;
   }
+}
+
+// The dispatch-order block of one QP launch (pan_common.h NPA_SCHED_NCLS; the kernels: nrmp_qp_device.h qp_sched_pick): launch j
+// of a forward call -- counted since npa_forward_begin, every launch of the forward path covers the whole batch -- reads counter
+// row j - 1 and list set (j - 1) & 1 (nothing for j = 0: scene order) and writes row j and set j & 1.  Beyond the K rows, or on
+// a handle created under NPA_QP_ORDER=0, everything is null: scene order, nothing filed.
+static QpSched sched_ptrs(const npa_handle* h, PendingCall* pc, const ScratchLayout& L) {
+  QpSched s{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const int j = pc->qp_seq++;
+  if (!h->qp_order || j >= h->P.K) return s;
+  int* cnt = (int*)(pc->ws + L.sched);
+  int* list = cnt + npa_sched_cnt_ints(h->P.K);
+  const size_t set = (size_t)NPA_SCHED_NCLS * pc->batch;
+  if (j > 0) { s.in_cnt = cnt + (size_t)(j - 1) * NPA_SCHED_NCLS; s.in_list = list + (size_t)((j - 1) & 1) * set; }
+  s.out_cnt = cnt + (size_t)j * NPA_SCHED_NCLS; s.out_list = list + (size_t)(j & 1) * set;
+  s.ticket = list + 2 * set;
+  return s;
 }
 
 // ---- forward = begin + K x iter + end ------------------------------------------------------------
@@ -339,7 +364,7 @@ static int forward_begin_impl(npa_handle* h, int batch, int n_stride, const floa
   hipStream_t stream = (hipStream_t)stream_;
   const int T = P.T;
   const bool reset_state = (flags & NPA_FWD_RESET_STATE) != 0;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h));
+  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h), h->P.K);
   float* ws = (float*)workspace;
   pc->batch = batch; pc->n_stride = n_stride; pc->ref_s = ref_s; pc->ref_us = ref_us; pc->points = points;
   pc->velocities = velocities; pc->n_points = n_points; pc->out_s = out_s; pc->out_u = out_u; pc->out_d = out_d;
@@ -348,17 +373,20 @@ static int forward_begin_impl(npa_handle* h, int batch, int n_stride, const floa
   pc->dune = P.M > 0 && points != nullptr;
   pc->nom_s = nom_s; pc->nom_u = nom_u; pc->reset_state = reset_state;
   pc->theta = h->theta;
+  pc->qp_seq = 0;
   if (pc->dune) key_policy(h, batch, n_stride);
   if (launch_stage) {
     // one launch instead of two copies and up to three memsets (each costs tens of microseconds of stream time)
     const size_t ns = (size_t)batch * 3 * (T + 1), nu2 = (size_t)batch * 2 * T;
     const size_t nflag = (size_t)batch * 4, ncount = (size_t)batch * (T + 1);
     const size_t nstate = reset_state ? npa_state_bytes(h, batch) / 4 : 0;
-    const size_t work = std::max(std::max(ns, nu2), std::max(std::max(nflag, ncount), nstate));
+    const size_t nsched = npa_sched_cnt_ints(P.K);
+    const size_t work = std::max(std::max(std::max(ns, nu2), nsched), std::max(std::max(nflag, ncount), nstate));
     const int threads = 256;
     const int blocks = (int)std::min<size_t>((work + threads - 1) / threads, 512);
     hipLaunchKernelGGL(stage_kernel, dim3(blocks), dim3(threads), 0, stream, ws + L.cur_s, nom_s, ns, ws + L.cur_u, nom_u, nu2,
-                       (int*)(ws + L.flags), nflag, (int*)(ws + L.count), ncount, (int*)state, nstate, ws + L.trig, T);
+                       (int*)(ws + L.flags), nflag, (int*)(ws + L.count), ncount, (int*)state, nstate, ws + L.trig, T,
+                       (int*)(ws + L.sched), nsched);
     HIP_TRY(hipGetLastError());
   }
   pc->active = true;
@@ -440,21 +468,23 @@ extern "C" int npa_group_begin_merged(int n, const npa_forward_call* calls, int 
   npa_handle* h0 = calls[0].h;
   const DevParams& P = h0->P;
   const int T = P.T, batch = calls[0].batch;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h0));
+  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h0), h0->P.K);
   StageGroup G;
   memset(&G, 0, sizeof(G));
   for (int c = 0; c < n; ++c) {
     const PendingCall& pc = calls[c].h->pc;
     G.c[c] = StageCall{pc.ws + L.cur_s, pc.nom_s, pc.ws + L.cur_u, pc.nom_u, (int*)(pc.ws + L.flags), (int*)(pc.ws + L.count),
-                       (int*)pc.state, pc.ws + L.trig};
+                       (int*)pc.state, pc.ws + L.trig, (int*)(pc.ws + L.sched)};
   }
   const size_t ns = (size_t)batch * 3 * (T + 1), nu2 = (size_t)batch * 2 * T;
   const size_t nflag = (size_t)batch * 4, ncount = (size_t)batch * (T + 1);
   const size_t nstate = h0->pc.reset_state ? npa_state_bytes(h0, batch) / 4 : 0;
-  const size_t work = std::max(std::max(ns, nu2), std::max(std::max(nflag, ncount), nstate));
+  const size_t nsched = npa_sched_cnt_ints(P.K);
+  const size_t work = std::max(std::max(std::max(ns, nu2), nsched), std::max(std::max(nflag, ncount), nstate));
   const int threads = 256;
   const int blocks = (int)std::min<size_t>((work + threads - 1) / threads, 512);
-  hipLaunchKernelGGL(stage_group_kernel, dim3(blocks, n), dim3(threads), 0, h0->pc.stream, G, ns, nu2, nflag, ncount, nstate, T);
+  hipLaunchKernelGGL(stage_group_kernel, dim3(blocks, n), dim3(threads), 0, h0->pc.stream, G, ns, nu2, nflag, ncount, nstate, T,
+                     nsched);
   HIP_TRY(hipGetLastError());
   return NPA_OK;
 }
@@ -470,7 +500,7 @@ extern "C" int npa_group_iter_merged(int n, const npa_forward_call* calls, int k
   const DevParams& P = h0->P;
   if (k < 0 || k >= P.K) return fail(NPA_E_ARG, "npa_forward_batch_group: iteration index out of range");
   const int T = P.T, batch = calls[0].batch;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h0));
+  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h0), h0->P.K);
   hipStream_t stream = h0->pc.stream;
   for (int c = 0; c < n; ++c)
     if (!calls[c].h->pc.active) return fail(NPA_E_ARG, "npa_forward_batch_group: a call of the group is not in progress");
@@ -502,7 +532,7 @@ extern "C" int npa_group_iter_merged(int n, const npa_forward_call* calls, int k
     Q.c[c] = QpCall{cur_s, cur_u, pc.ref_s, pc.ref_us, ws + L.mu, ws + L.lam, ws + L.pts, ws + L.dist, (const int*)(ws + L.count),
                     cur_s, cur_u, ws + L.cur_d, pc.out_s, pc.out_u, pc.out_d, pc.out_md, pc.out_iters, pc.out_np,
                     (int*)(ws + L.flags), pc.state, (double*)(ws + L.qp_info), h->qp_warm ? (double*)(ws + L.warm) : nullptr,
-                    pc.dune ? ws + L.trig : nullptr, pc.theta};
+                    pc.dune ? ws + L.trig : nullptr, pc.theta, sched_ptrs(h, &h->pc, L)};
   }
   EventPair* ev = next_event(h0, h0->ev_qp, h0->n_qp);
   HIP_TRY(npa_launch_qp_group(P, Q, n, batch, stream, ev ? ev->a : nullptr, ev ? ev->b : nullptr));
@@ -519,7 +549,7 @@ extern "C" int npa_forward_iter(npa_handle* h, int k) {
   if (k < 0 || k >= P.K) return fail(NPA_E_ARG, "npa_forward_iter: iteration index out of range");
   const int T = P.T, batch = pc->batch;
   const bool geo = h->key_terms == 4;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h));
+  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h), h->P.K);
   float* ws = pc->ws;
   float *cur_s = ws + L.cur_s, *cur_u = ws + L.cur_u, *cur_d = ws + L.cur_d;
   float *mu = ws + L.mu, *lam = ws + L.lam, *pts = ws + L.pts, *dist = ws + L.dist;
@@ -554,7 +584,7 @@ extern "C" int npa_forward_iter(npa_handle* h, int k) {
                         cur_d, pc->out_s, pc->out_u, pc->out_d, pc->out_md, pc->out_iters, pc->out_np, flags,
                         pc->state, qp_info, h->qp_warm ? (double*)(ws + L.warm) : nullptr, pc->dune ? ws + L.trig : nullptr,
                         nullptr, nullptr, nullptr, stream,
-                        ev ? ev->a : nullptr, ev ? ev->b : nullptr, pc->theta));
+                        ev ? ev->a : nullptr, ev ? ev->b : nullptr, pc->theta, sched_ptrs(h, pc, L)));
   if (h->cal.key_auto && pc->dune && k == P.K - 1)
     HIP_TRY(hipMemcpyAsync(h->sel_stats_host, h->sel_stats_dev, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   return NPA_OK;

@@ -51,6 +51,7 @@ struct Knobs {
   std::string calib_key;           // knob part of the pack's cache key
   // per handle, not part of the key
   bool sel_debug = false, qp_cold = false, qp_generic = false, skip_selftest = false, pack_cache = true;
+  bool qp_order = true;            // NPA_QP_ORDER=0: the QP launches hand their scenes out in scene order
   double audit_rate = 1.0 / 64.0;  // audit tiles: one slice wave in 64 (NPA_AUDIT_RATE in [0, 1]; 0 = candidates only)
   float margin_scale = 1.f;
 };
@@ -65,6 +66,7 @@ static Knobs read_knobs() {
   k.sel_debug = getenv("NPA_SEL_DEBUG") != nullptr;
   k.qp_cold = getenv("NPA_QP_COLD") != nullptr;
   k.qp_generic = getenv("NPA_QP_GENERIC") != nullptr;
+  if (const char* env = getenv("NPA_QP_ORDER")) k.qp_order = atoi(env) != 0;
   k.skip_selftest = getenv("NPA_SKIP_SELFTEST") != nullptr;
   if (const char* env = getenv("NPA_PACK_CACHE")) k.pack_cache = atoi(env) != 0;
   if (const char* env = getenv("NPA_AUDIT_RATE")) { double v = atof(env); if (v >= 0.0 && v <= 1.0) k.audit_rate = v; }
@@ -480,6 +482,7 @@ static int create_handle(npa_handle* h, bool need_w, const npa_dune_weights* w) 
   const Knobs knobs = read_knobs();
   h->knobs = knobs.calib;
   h->sel_debug = knobs.sel_debug; h->qp_warm = !knobs.qp_cold; h->qp_generic = knobs.qp_generic;
+  h->qp_order = knobs.qp_order;
 #ifdef NPA_EXPERIMENTS
   read_experiment_knobs(h);
 #endif

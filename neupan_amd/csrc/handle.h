@@ -39,6 +39,7 @@ struct PendingCall {
   bool dune = false;
   const float *nom_s = nullptr, *nom_u = nullptr;     // (the staging launch's sources: the merged group path launches it later)
   bool reset_state = false;
+  int qp_seq = 0;                    // QP launches of this call so far: the row of class counters the next one writes (pan_common.h)
   const float* theta = nullptr;      // the handle's per-scene parameter block as it was when the call began (npa_set_adjust_batch)
 };
 
@@ -150,6 +151,7 @@ struct npa_handle {
   std::vector<EventPair> ev_dune, ev_sel, ev_qp;
   size_t n_dune = 0, n_sel = 0, n_qp = 0;
   bool qp_generic = false;
+  bool qp_order = true;                  // the QP launches dispatch their solves longest-first from the lists of the launch before (NPA_QP_ORDER=0: off)
 };
 
 inline int mdim(const DevParams& P) { return P.M > 0 ? P.M : 1; }

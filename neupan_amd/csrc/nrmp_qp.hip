@@ -67,7 +67,10 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                                     float* out_min_distance, int* out_iters, float* out_nrmp_points, int* flags,
                                     float* state, double* qp_info, double* warm, float* trig_out, float* dbg_abc,
                                     float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta) {
+                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta,
+                                    QpSched sched) {
+  // (the dispatch-order block describes a launch over the whole batch of a forward call: a partial launch gets none)
+  if (scene0 != 0) sched = QpSched{nullptr, nullptr, nullptr, nullptr, nullptr};
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;     // tests: the generic (LDS) instantiation for every (T, M)
   const bool fast = qp_fast_path(P.T, P.M) && !force_generic;
   const size_t shmem = npa_qp_shmem_bytes_path(P.T, P.M, fast ? 1 : 0);      // one scene (wave) per workgroup, see the kernel
@@ -85,7 +88,8 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
                         P, cur_s_in, cur_u_in, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, dist_sorted, count,  \
                         cur_s_out, cur_u_out, cur_d_out, out_s, out_u, out_d, out_min_distance, out_iters,            \
                         out_nrmp_points, flags, state, qp_info, warm, scene0, batch,                                 \
-                        QpBackward{nullptr, nullptr, nullptr, nullptr, nullptr, dbg_abc, dbg_f, dbg_x}, trig_out, theta)
+                        QpBackward{nullptr, nullptr, nullptr, nullptr, nullptr, dbg_abc, dbg_f, dbg_x}, trig_out, theta,   \
+                        sched)
   if (fast && P.T == 10) QP_LAUNCH(10, 10);
   else if (fast && P.T == 20) QP_LAUNCH(20, 10, false, true);
   else QP_LAUNCH(0, 0);
@@ -111,9 +115,9 @@ extern "C" hipError_t npa_launch_qp_group(const DevParams& P, const QpGroup& G, 
     attr_set.done(dev_);
   }
   if (P.T == 10)
-    hipExtLaunchKernelGGL((nrmp_qp_group_kernel<10, 10>), dim3(batch, n), dim3(QP_THREADS), shmem, stream, ev_start, ev_stop, 0, P, G, batch);
+    hipExtLaunchKernelGGL((nrmp_qp_group_kernel<10, 10>), dim3(batch, n), dim3(QP_THREADS), shmem, stream, ev_start, ev_stop, 0, P, G, batch, n);
   else
-    hipExtLaunchKernelGGL((nrmp_qp_group_kernel<20, 10, true>), dim3(batch, n), dim3(QP_THREADS), shmem, stream, ev_start, ev_stop, 0, P, G, batch);
+    hipExtLaunchKernelGGL((nrmp_qp_group_kernel<20, 10, true>), dim3(batch, n), dim3(QP_THREADS), shmem, stream, ev_start, ev_stop, 0, P, G, batch, n);
   return hipGetLastError();
 }
 
@@ -142,7 +146,8 @@ extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, cons
                      ref_us, mu_sorted, lam_sorted, pts_sorted, (const float*)nullptr, count, out_s, out_u, out_d,        \
                      (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr,  \
                      (int*)nullptr, (float*)nullptr, qp_info, (double*)nullptr, 0, batch,                                 \
-                     QpBackward{grad_s, grad_u, grad_d, grad_theta, grad_nom_s, nullptr, nullptr, nullptr}, (float*)nullptr, theta)
+                     QpBackward{grad_s, grad_u, grad_d, grad_theta, grad_nom_s, nullptr, nullptr, nullptr}, (float*)nullptr, theta, \
+                     QpSched{nullptr, nullptr, nullptr, nullptr, nullptr})
   if (fast && P.T == 10) QPB_LAUNCH(10, 10, true);
   else if (fast && P.T == 20) QPB_LAUNCH(20, 10, true, true);
   else QPB_LAUNCH(0, 0, true);

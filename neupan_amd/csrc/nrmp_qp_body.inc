@@ -3,18 +3,17 @@
 // (call, scene)).  A textual body, not a function of its own, so
 // that the kernel's token stream -- and with it its machine code, which the counter records of profiles/ are tied to --
 // is what it was.  Expects in scope: the kernel's parameters (`theta` among them), `sm_all` (the scene's LDS block, LDS address 0), `lane`, `b`
-// (the GLOBAL scene number: the row of every per-scene array, theta included).
+// (the GLOBAL scene number: the row of every per-scene array, theta included), `QP_SCHED_FILE(iterations)` (files scene b for the
+// next launch's dispatch order, nrmp_qp_device.h: qp_sched_file; one lane calls it).
   double* sm = sm_all;
-  if (flags && flags[b * 4 + 0]) return;
+  // (a stopped scene is not solved, and still files itself for the next launch: every workgroup of a launch files one scene)
+  if (flags && flags[b * 4 + 0]) {
+    if (lane == 0) QP_SCHED_FILE(0);
+    return;
+  }
   // ASET_T is still a template parameter because the counter records of profiles/ and tests/test_bench_contract.py look the
   // kernels up by their demangled names, which spell every argument out
   static_assert(!ASET_T, "the active-set launch is retired (DESIGN.md 3.3): ASET_T only keeps the kernels' names");
-  // REMNANT of the retired active-set launch, kept because removing it changes the pinned machine code: nothing sets flags[3]
-  // any more, so this skip never fires.  It leaves with the next counter collection (DESIGN.md section 7).
-  if (flags && flags[b * 4 + 3]) {
-    if (lane == 0) flags[b * 4 + 3] = 0;
-    return;
-  }
   // this wave is a long dependent chain that shares its SIMD with throughput-bound selection waves of
   // the other batches in flight: win the issue arbitration, it needs few slots but needs them promptly
   __builtin_amdgcn_s_setprio(3);
@@ -1414,16 +1413,13 @@
     double* qi = qp_info + (size_t)b * QP_INFO_STRIDE;
     qi[0] = best_it; qi[1] = best_merit; qi[2] = last_mu; qi[3] = status; qi[4] = it;
     qi[14] = it_total; qi[15] = warm_code;
-#ifndef NPA_QP_PROF
-    // REMNANT of the retired active-set launch, kept because removing it changes the pinned machine code: P.qp_aset is always 0,
-    // so nothing is cleared.  It leaves with the next counter collection (DESIGN.md section 7).
-    if (P.qp_aset && !(can_warm)) { qi[5] = 0; qi[6] = 0; qi[7] = 0; qi[8] = 0; }
-#endif
 #ifdef NPA_QP_PROF
     PROF(9);
     for (int i = 0; i < 10; ++i) qi[5 + i] = (double)pacc_[i];
 #endif
   }
+  // the next launch of this forward call dispatches its solves longest-first: file the scene under its iteration count
+  if (lane == 0) QP_SCHED_FILE(it_total);
 
   // ---- per-forward outputs of the last executed iteration -------------------------------------
   const int cnt0 = (obs && count) ? count[(size_t)b * (T + 1)] : 0;

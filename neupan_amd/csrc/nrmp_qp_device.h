@@ -316,6 +316,44 @@ __device__ __forceinline__ void st2(double* p, double a, double b) { *reinterpre
     __builtin_amdgcn_wave_barrier();                         \
   } while (0)
 
+// ---- dispatch order: which scene a workgroup solves (pan_common.h NPA_SCHED_NCLS) ---------------------------------
+// The previous QP launch of the forward call filed every scene under the class of its iteration count (qp_sched_file, class 0 =
+// the longest solves) and counted the classes in cnt[32].  The workgroup of rank r takes the r-th scene of the classes laid end
+// to end: lanes 0..31 hold the counters, an inclusive prefix sum over them (two DPP rows) gives the class boundaries, the class
+// is the first lane whose prefix exceeds r.  The launch that wrote the lists is complete (same stream) and nothing changes them
+// during this launch, so every wave reads the same words: when the counters do not add up to the batch -- a launch that did not
+// file, a damaged row -- EVERY workgroup takes scene order (b = rank) and each scene is still solved exactly once.  The result is
+// clamped into the batch: a damaged list cannot address outside it.  cnt == null: scene order.
+__device__ __forceinline__ int qp_sched_pick(const int* __restrict__ cnt, const int* __restrict__ list, int rank, int nscene, int lane) {
+  if (!cnt) return rank;
+  const int c0 = cnt[lane & (NPA_SCHED_NCLS - 1)];
+  const int c = lane < NPA_SCHED_NCLS ? c0 : 0;
+  int s = c;
+  s += __builtin_amdgcn_update_dpp(0, s, 0x111, 0xF, 0xF, true);     // row_shr:1, 2, 4, 8, zero-filled: prefix inside a 16-lane row
+  s += __builtin_amdgcn_update_dpp(0, s, 0x112, 0xF, 0xF, true);
+  s += __builtin_amdgcn_update_dpp(0, s, 0x114, 0xF, 0xF, true);
+  s += __builtin_amdgcn_update_dpp(0, s, 0x118, 0xF, 0xF, true);
+  s += __builtin_amdgcn_update_dpp(0, s, 0x142, 0xA, 0xF, false);    // row_bcast:15: row 0's total into row 1 (rows 0, 2 receive 0)
+  if (__builtin_amdgcn_readlane(s, NPA_SCHED_NCLS - 1) != nscene) return rank;
+  const unsigned long long over = __builtin_amdgcn_ballot_w64(lane < NPA_SCHED_NCLS && s > rank);   // (never 0: the total exceeds rank)
+  const int cls = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(over | (1ull << (NPA_SCHED_NCLS - 1))));
+  int off = rank - __builtin_amdgcn_readlane(s - c, cls);
+  off = off < 0 ? 0 : (off >= nscene ? nscene - 1 : off);
+  const int b = __builtin_amdgcn_readfirstlane(list[(size_t)cls * nscene + off]);
+  return b < 0 ? 0 : (b >= nscene ? nscene - 1 : b);
+}
+// ... and the filing, by one lane at the end of a solve: class 31 - min(iterations, 31), a stopped scene (no solve) class 31.
+// L: the linear workgroup number the scene was solved under.  cnt == null: nothing is filed.  (A position outside the class's
+// block -- counters that were not cleared -- is dropped: the next launch then sees a list it cannot trust only through a sum
+// that still equals the batch, and that launch is clamped.)
+__device__ __forceinline__ void qp_sched_file(int* cnt, int* list, int* ticket, int it_total, int b, int L, int nscene) {
+  if (!cnt) return;
+  const int cls = NPA_SCHED_NCLS - 1 - (it_total < 0 ? 0 : (it_total > NPA_SCHED_NCLS - 1 ? NPA_SCHED_NCLS - 1 : it_total));
+  const int pos = __hip_atomic_fetch_add(&cnt[cls], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if ((unsigned)pos < (unsigned)nscene) list[(size_t)cls * nscene + pos] = b;
+  ticket[b] = L;
+}
+
 // TT > 0: horizon known at compile time -> the reduced KKT matrix, its Cholesky factor (rows and
 // columns) and the columns of Phi live in registers, one matrix row per lane, every loop over
 // the horizon is unrolled and all broadcasts are v_readlane (no LDS round trip on the serial
@@ -381,7 +419,8 @@ void nrmp_qp_kernel(
     float* __restrict__ out_u, float* __restrict__ out_d, float* __restrict__ out_min_distance,
     int* __restrict__ out_iters, float* __restrict__ out_nrmp_points, int* __restrict__ flags,
     float* __restrict__ state, double* __restrict__ qp_info, double* __restrict__ warm, int scene0, int nscene,
-    QpBackward bw, float* __restrict__ trig_out, const float* __restrict__ theta) {
+    QpBackward bw, float* __restrict__ trig_out, const float* __restrict__ theta,
+    QpSched sched) {
   extern __shared__ __attribute__((aligned(16))) double sm_all[];
   // one scene (one wave) per workgroup: the dispatcher spreads the waves of a launch evenly over the CUs, and -- the
   // reason it is fixed here and not a launch parameter -- the scene's LDS block starts at LDS address 0, so every array
@@ -390,22 +429,34 @@ void nrmp_qp_kernel(
   // every iteration of the solve.
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= nscene) return;
-  const int b = blockIdx.x + scene0;
+  // (dispatch order, forward solves only: the launcher passes the block with scene0 == 0 alone)
+  int b_ = blockIdx.x;
+  if constexpr (!BWD) b_ = qp_sched_pick(sched.in_cnt, sched.in_list, blockIdx.x, nscene, lane);
+  const int b = b_ + scene0;
+  // what the body's tail files the scene with: read there, from the kernel arguments, not carried through the solve
+#define QP_SCHED_FILE(IT) do { if constexpr (!BWD) qp_sched_file(sched.out_cnt, sched.out_list, sched.ticket, (IT), b, (int)blockIdx.x, nscene); } while (0)
 #include "nrmp_qp_body.inc"
+#undef QP_SCHED_FILE
 }
 
-// nrmp_qp_kernel over a GROUP of forward calls (pan_common.h: merged launches): blockIdx.y = the call, blockIdx.x = the scene
-// of that call; the per-call pointers come out of the kernel arguments, the body is the same statements.  Forward solves only.
+// nrmp_qp_kernel over a GROUP of n forward calls (pan_common.h: merged launches): the grid is (nscene, n), workgroup L of it
+// (row-major) solves for call L % n the scene that call's dispatch order gives rank L / n (qp_sched_pick; scene L / n without one); the per-call pointers come out of the kernel arguments, the body is the same statements.  Forward solves only.
 template <int TT, int MM, bool SCANW = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(QP_THREADS, QP_THREADS), amdgpu_waves_per_eu(NPA_QP_WAVES, 3)))
-void nrmp_qp_group_kernel(DevParams P, QpGroup G, int nscene) {
+void nrmp_qp_group_kernel(DevParams P, QpGroup G, int nscene, int n) {
   extern __shared__ __attribute__((aligned(16))) double sm_all[];
   constexpr bool BWD = false, ASET_T = false;
   constexpr int WV = NPA_QP_WAVES;
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= nscene) return;
-  const int b = blockIdx.x;
-  const QpCall& q = G.c[blockIdx.y];
+  // the linear workgroup number, dealt round-robin to the calls: the same rank of all n calls is dispatched side by side (with the
+  // calls as blocks of nscene workgroups the per-call order is worth nothing: the long solves of the last call still start last)
+  const unsigned sched_L = blockIdx.y * (unsigned)nscene + blockIdx.x, sched_rank = sched_L / (unsigned)n;
+  const int sched_call = __builtin_amdgcn_readfirstlane((int)(sched_L - sched_rank * (unsigned)n));       // L % n
+  const QpCall& q = G.c[sched_call];
+  const int b = qp_sched_pick(q.sched.in_cnt, q.sched.in_list, (int)sched_rank, nscene, lane);
+#define QP_SCHED_FILE(IT) do { const QpSched& so_ = G.c[sched_call].sched; \
+    qp_sched_file(so_.out_cnt, so_.out_list, so_.ticket, (IT), b, (int)(blockIdx.y * (unsigned)nscene + blockIdx.x), nscene); } while (0)
   const float* cur_s_in = q.cur_s_in; const float* cur_u_in = q.cur_u_in;
   const float* __restrict__ ref_s = q.ref_s; const float* __restrict__ ref_us = q.ref_us;
   const float* __restrict__ mu_sorted = q.mu_sorted; const float* __restrict__ lam_sorted = q.lam_sorted;
@@ -419,4 +470,5 @@ void nrmp_qp_group_kernel(DevParams P, QpGroup G, int nscene) {
   const float* __restrict__ theta = q.theta;          // this call's parameter block (null: the uniform set of P), row b = its scene b
   const QpBackward bw{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 #include "nrmp_qp_body.inc"
+#undef QP_SCHED_FILE
 }

@@ -46,8 +46,8 @@ struct DevParams {
   // bounding box (the key pass of select_geo_kernel ranks on the distance to it, pan_common.h WP_TABH[4])
   int geo_rect;
   float rcx, rcy, rhx, rhy;
-  int qp_aset;                // always 0: a layout placeholder of the retired active-set launch.  Removing it shifts geo_tab and the
-                              // kernarg offsets of the pinned selection kernels: it leaves with the next counter collection
+  int qp_aset;                // always 0, read by nothing: a layout placeholder of the retired active-set launch.  Removing it shifts geo_tab
+                              // and the kernarg offsets of the selection kernels; the pack image's layout test pins the slot
   int geo_tab;                // the weight pack carries the correction table of the geometric key (WP_TAB) and its margins (WP_KTAB)
 };
 
@@ -64,16 +64,21 @@ struct SelGeoCall {
   unsigned* audit; int n_stride; unsigned audit_seed;
 };
 struct SelGeoGroup { SelGeoCall c[NPA_GROUP_MAX]; };
+// dispatch order of the QP solves (NPA_SCHED_NCLS below): the class counters and lists the previous QP launch of the forward call
+// wrote (null: scene order), the ones this launch writes (null: nothing is filed), the tickets.  ONE by-value kernel argument.
+struct QpSched { const int* in_cnt; const int* in_list; int* out_cnt; int* out_list; int* ticket; };
 struct QpCall {
   const float* cur_s_in; const float* cur_u_in; const float* ref_s; const float* ref_us; const float* mu_sorted;
   const float* lam_sorted; const float* pts_sorted; const float* dist_sorted; const int* count; float* cur_s_out;
   float* cur_u_out; float* cur_d_out; float* out_s; float* out_u; float* out_d; float* out_min_distance; int* out_iters;
   float* out_nrmp_points; int* flags; float* state; double* qp_info; double* warm; float* trig_out;
   const float* theta;         // [batch][8] per-scene adjust parameters of THIS call (npa_set_adjust_batch), or null: P's uniform set
+  QpSched sched;              // this call's dispatch-order block for this launch
 };
 struct QpGroup { QpCall c[NPA_GROUP_MAX]; };
 struct StageCall {
   float* cur_s; const float* nom_s; float* cur_u; const float* nom_u; int* flags; int* count; int* state; float* trig;
+  int* sched_cnt;             // the class counters of the call's QP launches (every row is cleared)
 };
 struct StageGroup { StageCall c[NPA_GROUP_MAX]; };
 
@@ -203,13 +208,25 @@ __device__ inline void npa_trig(float th, float& c, float& s) {
   s = (float)sin((double)th);
 }
 
+// ---- dispatch order of the QP solves (nrmp_qp_device.h: qp_sched_pick) ------------------------------------
+// A launch lasts as long as its slowest solve, and which solves are long is largely known one PAN iteration ahead: every solve
+// files its scene under the class of its iteration count (class 0 = the longest), and the next launch hands the scenes out class
+// by class.  Per forward call, behind the other blocks of the workspace (ints):
+//   cnt [K][NCLS]      one row of class counters per QP launch of the call; the staging launch zeroes every row
+//   list [2][NCLS][B]  the scenes of a class in the order they finished, ping-pong by launch parity
+//   ticket [B]         the linear workgroup number a scene was last solved under (diagnostics: the tests read the order from it)
+#define NPA_SCHED_NCLS 32
 struct ScratchLayout {
-  size_t cur_s, cur_u, cur_d, mu, lam, pts, dist, count, flags, warm, qp_info, trig, keys, total;
+  size_t cur_s, cur_u, cur_d, mu, lam, pts, dist, count, flags, warm, qp_info, trig, keys, sched, total;
 };
+__host__ __device__ inline size_t npa_sched_cnt_ints(int K) { return (size_t)(K > 0 ? K : 1) * NPA_SCHED_NCLS; }
+__host__ __device__ inline size_t npa_sched_ints(int B, int K) {
+  return npa_sched_cnt_ints(K) + (size_t)2 * NPA_SCHED_NCLS * B + (size_t)B;
+}
 __host__ __device__ inline size_t npa_warm_doubles(int T, int M) {   // per scene: x (2T + T), lf (T M), lc (8T - 4), ld (2T)
   return (size_t)2 * T + T + (size_t)T * M + (8 * T - 4) + 2 * T;
 }
-__host__ __device__ inline ScratchLayout npa_scratch_layout(int B, int T, int M, int E, int key_stride) {
+__host__ __device__ inline ScratchLayout npa_scratch_layout(int B, int T, int M, int E, int key_stride, int K) {
   ScratchLayout L;
   size_t o = 0;
   auto take = [&](size_t n) { size_t r = o; o += (n + 3) & ~(size_t)3; return r; };
@@ -227,6 +244,7 @@ __host__ __device__ inline ScratchLayout npa_scratch_layout(int B, int T, int M,
   L.qp_info = take((size_t)B * 16 * 2);          // per-scene solver diagnostics of the last QP (16 doubles)
   L.trig = take((size_t)B * (T + 1) * 2);        // (cos, sin) of every nominal heading, see npa_trig()
   L.keys = take((size_t)B * (T + 1) * key_stride);
+  L.sched = take(npa_sched_ints(B, K));          // dispatch order of the QP solves: cnt, list, ticket (see above)
   L.total = o;
   return L;
 }
