@@ -24,6 +24,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the exports of the library: everything else in it is built with hidden visibility */
+#pragma GCC visibility push(default)
 
 #define NPA_OK 0
 #define NPA_E_ARG (-1)      /* bad argument (null pointer, size out of range)            */
@@ -938,6 +940,7 @@ int npa_dune_labels(int edge_num, const double *G, const double *h, int64_t n, c
 const char *npa_last_error(void);
 const char *npa_version(void);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the exports of the library: everything else in it is built with hidden visibility */
+#pragma GCC visibility push(default)
 
 int npa_grid_scan(const uint8_t *cells, int nx, int ny, double x0, double y0, double res,
                   int batch, const npa_scan_params *params, const int32_t *n_beams, int beam_stride,
@@ -97,6 +99,7 @@ int npa_grid_clearance(const uint8_t *cells, int nx, int ny, double x0, double y
 /* message of the calling thread's last failed call of this library */
 const char *npa_grid_last_error(void);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

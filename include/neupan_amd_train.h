@@ -52,6 +52,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* the exports of the library: everything else in it is built with hidden visibility */
+#pragma GCC visibility push(default)
 
 /* P = 4512 + 33 * edge_num.  Host only.  NPA_E_ARG (< 0) for edge_num outside 3 .. NPA_MAX_E. */
 int npa_dune_train_param_count(int edge_num);
@@ -79,6 +81,7 @@ int npa_dune_train_steps(int runs, int edge_num, const float *G, const float *h,
 /* message of the calling thread's last failed call of this library */
 const char *npa_dune_train_last_error(void);
 
+#pragma GCC visibility pop
 #ifdef __cplusplus
 }
 #endif

@@ -24,8 +24,9 @@ OBJ = os.path.join(HERE, "_obj")
 EXPERIMENTS = os.environ.get("NPA_EXPERIMENTS", "0") not in ("", "0")
 # -ffp-contract=fast-honor-pragmas is hipcc's default for device code, stated here so that it is the BUILD's property, not the
 # compiler's: the bit-exact legs (A / B / C, fa against the reference's tensors) are written with __f*_rn intrinsics where the
-# reference rounds every operation, and with explicit fmaf where it does not
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-ffp-contract=fast-honor-pragmas",
+# reference rounds every operation, and with explicit fmaf where it does not.  -fvisibility=hidden: a library exports what its
+# public header declares (the headers push default visibility) and, for the main one, the diagnostics at the end of csrc/launch.h
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-fvisibility=hidden", "-ffp-contract=fast-honor-pragmas",
          "-Wno-unused-result", "-Wno-unused-value"] + (["-DNPA_EXPERIMENTS"] if EXPERIMENTS else [])
 
 
@@ -49,7 +50,7 @@ LIBRARIES = {
                     ["dune.hip", "nrmp_qp.hip", "frontend.hip", "dune_labels.hip", "c_api.hip", "create.hip", "pack_image.hip",
                      "serve_group.hip", "ingest.hip", "clearance.hip", "world.hip", "behave.hip", "cycle.hip", "lon.hip", "curves.hip"],
                     ("neupan_amd.h",),
-                    ("handle.h", "pan_common.h", "pack_image.h", "curves.h", "scan_beam.h", "scan_noise.h", "dune_device.h",
+                    ("handle.h", "launch.h", "pan_common.h", "curves.h", "scan_beam.h", "scan_noise.h", "dune_device.h",
                      "select_geo_carve.inc", "select_geo_body.inc", "nrmp_qp_device.h", "nrmp_qp_body.inc")),
     # the fused DUNE training step
     "train": Library(os.path.join(HERE, "libneupan_amd_train.so"), ["dune_train.hip"], ("neupan_amd_train.h", "neupan_amd.h")),

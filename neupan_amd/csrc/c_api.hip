@@ -2,25 +2,13 @@
 // carving, launch sequencing, the stage entry points, the front-end / ingest / label wrappers.  Creation, calibration and the
 // self-test are create.hip; the two share the handle (handle.h) and nothing else.  Host-side only, no torch types.
 #include "handle.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
-extern "C" hipError_t npa_launch_encode(const DevParams& P, const float* wpack, int batch, int scene0, int t0,
-                                        int n_stride, const float* cur_s, const float* points, const float* vel,
-                                        const int* n_points, const int* flags, unsigned* gkeys, const float* trig,
-                                        int n_cu, int blocks_per_cu, int key_terms, hipStream_t stream,
-                                        hipEvent_t ev_start, hipEvent_t ev_stop);
-extern "C" hipError_t npa_launch_trig(const float* cur_s, int batch, int T, float* trig, hipStream_t stream);
-extern "C" hipError_t npa_launch_select_geo(const DevParams& P, const float* wpack, int batch, int scene0, int t0,
-                                            int n_stride, const float* cur_s, const float* points, const float* vel,
-                                            const int* n_points, const int* flags, const float* trig, float* mu_sorted,
-                                            float* lam_sorted, float* pts_sorted, float* dist_sorted, int* count,
-                                            unsigned* stats, int debug, unsigned* audit, unsigned audit_thresh,
-                                            unsigned audit_seed, float margin_scale, int rows_bf16, hipStream_t stream,
-                                            hipEvent_t ev_start, hipEvent_t ev_stop);
 // The one experiment on record that is still compiled (measured slower than the default path) is the
 // first form of the geometric selection, select_kernel<E, true> behind NPA_SELECT_V1, and only with -DNPA_EXPERIMENTS
 // (NPA_EXPERIMENTS=1 python -m neupan_amd.build).  The default build has neither its kernel nor its environment knob.
@@ -33,46 +21,17 @@ extern "C" hipError_t npa_launch_select_geo(const DevParams& P, const float* wpa
 #else
 #define NPA_VERSION_SUFFIX ""
 #endif
-extern "C" hipError_t npa_launch_select(const DevParams& P, const float* wpack, int batch, int scene0, int t0,
-                                        int n_stride, const float* cur_s, const float* points, const float* vel,
-                                        const int* n_points, const int* flags, const unsigned* gkeys,
-                                        const float* trig, float* mu_sorted, float* lam_sorted, float* pts_sorted,
-                                        float* dist_sorted, int* count, int key_terms, float e0, unsigned* stats,
-                                        int debug, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
-extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, const float* cur_s_in,
-                                    const float* cur_u_in, const float* ref_s, const float* ref_us, const float* mu_sorted,
-                                    const float* lam_sorted, const float* pts_sorted, const float* dist_sorted,
-                                    const int* count, float* cur_s_out, float* cur_u_out, float* cur_d_out,
-                                    float* out_s, float* out_u, float* out_d, float* out_min_distance,
-                                    int* out_iters, float* out_nrmp_points, int* flags, float* state,
-                                    double* qp_info, double* warm, float* trig_out, float* dbg_abc, float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta,
-                                    QpSched sched);
-extern "C" int npa_select_geo_group_supported(int E);
-extern "C" hipError_t npa_launch_select_geo_group(const DevParams& P, const SelGeoGroup& G, int n, int batch, int t0, int n_stride_max,
-                                                  int debug, unsigned audit_thresh, float margin_scale, int rows_bf16,
-                                                  hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop);
-extern "C" int npa_qp_group_supported(int T, int M);
-extern "C" hipError_t npa_launch_qp_group(const DevParams& P, const QpGroup& G, int n, int batch, hipStream_t stream,
-                                          hipEvent_t ev_start, hipEvent_t ev_stop);
-extern "C" hipError_t npa_launch_nominal(int batch, int T, int kin, double dt, double L, const double* state,
-                                         const float* vel, const double* ref_speed, const double* path,
-                                         const int* curve_off, const int* curve_len, const int* point_index,
-                                         const double* interval, float* nom_s, float* nom_u, float* ref_s,
-                                         float* ref_us, hipStream_t stream);
-extern "C" hipError_t npa_launch_scan(int batch, int beam_stride, const double* ranges, const double* beam_vel,
-                                      const int* n_beams, const npa_scan_params* params, int mode, int out_stride,
-                                      float* points, float* velocities, int* count, hipStream_t stream);
-extern "C" int npa_ingest_offsets(int batch, int T, int n_stride, int with_vel, size_t* out, int n);
-extern "C" hipError_t npa_launch_ingest_unpack(int batch, int T, int n_stride, int with_vel, const void* record,
-                                               size_t record_bytes, float* nom_s, float* nom_u, float* ref_s, float* ref_us,
-                                               float* points, float* velocities, int* n_points, int* status,
-                                               hipStream_t stream);
 
 extern "C" const char* npa_last_error(void) { return g_err.c_str(); }
 extern "C" const char* npa_version(void) { return "neupan_amd 0.5.2 (gfx950, hipcc " NPA_HIPCC_VERSION ")" NPA_VERSION_SUFFIX; }
 // per-slice stride of the key buffer inside the workspace: none with geometric keys (select_kernel keeps them in LDS)
 static int kstride(const npa_handle* h) { return h->key_terms == 4 ? 0 : h->P.key_stride; }
+// the selection launchers' rows_bf16: 1 = the reduced-precision tier of the rows, 2 = the bf16 tier of the keys, 0 = exact
+static int rows_tier(const npa_handle* h) { return h->rows_bf16 ? 1 : (h->cal.keys_bf16 ? 2 : 0); }
+// the workspace of a forward call of `batch` scenes on this handle
+static ScratchLayout layout_of(const npa_handle* h, int batch) {
+  return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h), h->P.K);
+}
 
 // a solve of `batch` scenes on a handle whose block was registered for another number of rows would read past it (or leave
 // rows unread): refused
@@ -85,15 +44,15 @@ static int check_theta_batch(const npa_handle* h, int batch, const char* who) {
 
 extern "C" size_t npa_workspace_bytes(const npa_handle* h, int batch) {
   if (!h || batch < 1) return 0;
-  return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h), h->P.K).total * sizeof(float);
+  return layout_of(h, batch).total * sizeof(float);
 }
 extern "C" size_t npa_workspace_qp_info_offset(const npa_handle* h, int batch) {
   if (!h || batch < 1) return 0;
-  return npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h), h->P.K).qp_info * sizeof(float);
+  return layout_of(h, batch).qp_info * sizeof(float);
 }
 extern "C" int npa_workspace_layout(const npa_handle* h, int batch, size_t* out, int n) {
   if (!h || batch < 1 || !out || n < 1) return fail(NPA_E_ARG, "npa_workspace_layout: bad argument");
-  const ScratchLayout L = npa_scratch_layout(batch, h->P.T, mdim(h->P), h->P.E, kstride(h), h->P.K);
+  const ScratchLayout L = layout_of(h, batch);
   // ([8]: the dispatch-order block of the QP launches -- cnt [K][32], list [2][32][batch], ticket [batch], ints; pan_common.h)
   const size_t v[9] = {L.cur_s * 4, L.cur_u * 4, L.cur_d * 4, L.mu * 4, L.lam * 4, L.pts * 4, L.dist * 4, L.count * 4, L.sched * 4};
   for (int i = 0; i < n && i < 9; ++i) out[i] = v[i];
@@ -172,19 +131,21 @@ extern "C" int npa_dune_stage(npa_handle* h, int batch, int n_stride, const floa
   }
   float* trig = reinterpret_cast<float*>(reinterpret_cast<char*>(h->stage_cand) + key_bytes);
   HIP_TRY(npa_launch_trig(nom_s, batch, h->P.T, trig, (hipStream_t)stream));
+  SelGeoCall c{};                        // (flags stay null: no scene of a stage call is done)
+  c.wpack = h->wpack; c.cur_s = nom_s; c.points = points; c.vel = velocities; c.n_points = n_points; c.n_stride = n_stride;
+  c.mu_sorted = mu_sorted; c.lam_sorted = lam_sorted; c.pts_sorted = pts_sorted; c.dist_sorted = dist_sorted; c.count = count;
+  c.stats = h->sel_stats_dev; c.trig = trig; c.audit = h->rows_bf16 ? nullptr : h->audit_dev;
   if (!geo)
-    HIP_TRY(npa_launch_encode(h->P, h->wpack, batch, 0, 0, n_stride, nom_s, points, velocities, n_points, nullptr,
-                              (unsigned*)h->stage_cand, trig, h->n_cu, 5, h->key_terms, (hipStream_t)stream,
-                              nullptr, nullptr));
-  if (geo && !h->select_v1)
-    HIP_TRY(npa_launch_select_geo(h->P, h->wpack, batch, 0, 0, n_stride, nom_s, points, velocities, n_points, nullptr, trig,
-                                  mu_sorted, lam_sorted, pts_sorted, dist_sorted, count, h->sel_stats_dev, h->sel_debug,
-                                  h->rows_bf16 ? nullptr : h->audit_dev, h->audit_thresh, h->launch_seq++, h->margin_scale,
-                                  h->rows_bf16 ? 1 : (h->cal.keys_bf16 ? 2 : 0), (hipStream_t)stream, nullptr, nullptr));
-  else
-    HIP_TRY(npa_launch_select(h->P, h->wpack, batch, 0, 0, n_stride, nom_s, points, velocities, n_points, nullptr,
-                              (const unsigned*)h->stage_cand, trig, mu_sorted, lam_sorted, pts_sorted, dist_sorted, count,
-                              h->key_terms, h->key_e0, h->sel_stats_dev, h->sel_debug, (hipStream_t)stream, nullptr, nullptr));
+    HIP_TRY(npa_launch_encode(h->P, c, batch, 0, (unsigned*)h->stage_cand, h->n_cu, 5, h->key_terms, (hipStream_t)stream, nullptr,
+                              nullptr));
+  if (geo && !h->select_v1) {
+    c.audit_seed = h->launch_seq++;
+    HIP_TRY(npa_launch_select_geo(h->P, c, batch, 0, h->sel_debug, h->audit_thresh, h->margin_scale, rows_tier(h),
+                                  (hipStream_t)stream, nullptr, nullptr));
+  } else {
+    HIP_TRY(npa_launch_select(h->P, c, batch, 0, (const unsigned*)h->stage_cand, h->key_terms, h->key_e0, h->sel_debug,
+                              (hipStream_t)stream, nullptr, nullptr));
+  }
   return NPA_OK;
 }
 
@@ -197,10 +158,14 @@ extern "C" int npa_nrmp_stage(npa_handle* h, int batch, const float* nom_s, cons
   if (h->P.M > 0 && (!mu_sorted || !lam_sorted || !pts_sorted || !count || !out_d))
     return fail(NPA_E_ARG, "npa_nrmp_stage: obstacle arrays required when nrmp_max_num > 0");
   if (int rc = check_theta_batch(h, batch, "npa_nrmp_stage")) return rc;
-  HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
-                        out_s, out_u, out_d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        qp_info, nullptr, nullptr, nullptr, nullptr, x64, (hipStream_t)stream, nullptr, nullptr, h->theta,
-                        QpSched{nullptr, nullptr, nullptr, nullptr, nullptr}));
+  // (one solve from the nominal: the iterate's slots receive the solution, the forward path's outputs and its state stay null)
+  QpCall c{};
+  c.cur_s_in = nom_s; c.cur_u_in = nom_u; c.ref_s = ref_s; c.ref_us = ref_us; c.mu_sorted = mu_sorted; c.lam_sorted = lam_sorted;
+  c.pts_sorted = pts_sorted; c.count = count;
+  c.cur_s_out = out_s; c.cur_u_out = out_u; c.cur_d_out = out_d; c.qp_info = qp_info; c.theta = h->theta;
+  QpBackward extra{};
+  extra.dbg_x = x64;
+  HIP_TRY(npa_launch_qp(h->P, c, batch, extra, (hipStream_t)stream, nullptr, nullptr));
   return NPA_OK;
 }
 
@@ -210,21 +175,17 @@ extern "C" int npa_nrmp_params(npa_handle* h, int batch, const float* nom_s, con
   if (!h || batch < 1 || !nom_s || !nom_u || !out_abc) return fail(NPA_E_ARG, "npa_nrmp_params: bad argument");
   if (h->P.M > 0 && (!mu_sorted || !lam_sorted || !pts_sorted || !count || !out_f))
     return fail(NPA_E_ARG, "npa_nrmp_params: obstacle arrays required when nrmp_max_num > 0");
-  // (the reference trajectory only enters the cost: the nominal arrays stand in for it, the kernel returns before the solve)
-  HIP_TRY(npa_launch_qp(h->P, batch, 0, nom_s, nom_u, nom_s, nom_u, mu_sorted, lam_sorted, pts_sorted, nullptr, count,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, out_abc, h->P.M > 0 ? out_f : nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr,
-                        nullptr,           // (the linearisation and the hinge rows do not depend on the adjust parameters)
-                        QpSched{nullptr, nullptr, nullptr, nullptr, nullptr}));
+  // (no theta: the linearisation and the hinge rows do not depend on the adjust parameters; the reference trajectory only enters
+  // the cost: the nominal arrays stand in for it, the kernel returns before the solve)
+  QpCall c{};
+  c.cur_s_in = nom_s; c.cur_u_in = nom_u; c.ref_s = nom_s; c.ref_us = nom_u; c.mu_sorted = mu_sorted; c.lam_sorted = lam_sorted;
+  c.pts_sorted = pts_sorted; c.count = count;
+  QpBackward extra{};
+  extra.dbg_abc = out_abc; extra.dbg_f = h->P.M > 0 ? out_f : nullptr;
+  HIP_TRY(npa_launch_qp(h->P, c, batch, extra, (hipStream_t)stream, nullptr, nullptr));
   return NPA_OK;
 }
 
-extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, const float* nom_s, const float* nom_u,
-                                             const float* ref_s, const float* ref_us, const float* mu_sorted,
-                                             const float* lam_sorted, const float* pts_sorted, const int* count,
-                                             float* out_s, float* out_u, float* out_d, const float* grad_s,
-                                             const float* grad_u, const float* grad_d, float* grad_theta,
-                                             float* grad_nom_s, double* qp_info, hipStream_t stream, const float* theta);
 extern "C" int npa_nrmp_backward(npa_handle* h, int batch, const float* nom_s, const float* nom_u, const float* ref_s,
                                  const float* ref_us, const float* mu_sorted, const float* lam_sorted,
                                  const float* pts_sorted, const int32_t* count, float* out_s, float* out_u, float* out_d,
@@ -235,17 +196,23 @@ extern "C" int npa_nrmp_backward(npa_handle* h, int batch, const float* nom_s, c
   if (h->P.M > 0 && (!mu_sorted || !lam_sorted || !pts_sorted || !count || !out_d))
     return fail(NPA_E_ARG, "npa_nrmp_backward: obstacle arrays required when nrmp_max_num > 0");
   if (int rc = check_theta_batch(h, batch, "npa_nrmp_backward")) return rc;
-  HIP_TRY(npa_launch_qp_backward(h->P, batch, nom_s, nom_u, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, count,
-                                 out_s, out_u, out_d, grad_s, grad_u, grad_d, grad_theta, grad_nom_s, qp_info, (hipStream_t)stream, h->theta));
+  QpCall c{};
+  c.cur_s_in = nom_s; c.cur_u_in = nom_u; c.ref_s = ref_s; c.ref_us = ref_us; c.mu_sorted = mu_sorted; c.lam_sorted = lam_sorted;
+  c.pts_sorted = pts_sorted; c.count = count;
+  c.cur_s_out = out_s; c.cur_u_out = out_u; c.cur_d_out = out_d; c.qp_info = qp_info; c.theta = h->theta;
+  QpBackward extra{};
+  extra.grad_s = grad_s; extra.grad_u = grad_u; extra.grad_d = grad_d; extra.grad_theta = grad_theta; extra.grad_nom_s = grad_nom_s;
+  HIP_TRY(npa_launch_qp_backward(h->P, c, batch, extra, (hipStream_t)stream));
   return NPA_OK;
 }
 
-// staging of one forward call: working copy of the nominal trajectory, cleared flags / counts / state
-__global__ void stage_kernel(float* __restrict__ cur_s, const float* __restrict__ nom_s, size_t ns,
-                             float* __restrict__ cur_u, const float* __restrict__ nom_u, size_t nu,
-                             int* __restrict__ flags, size_t nflag, int* __restrict__ count, size_t ncount,
-                             int* __restrict__ state, size_t nstate, float* __restrict__ trig, int T,
-                             int* __restrict__ sched_cnt, size_t nsched) {
+// staging of one forward call: working copy of the nominal trajectory, cleared flags / counts / state.  ONE body for the two
+// kernels below.
+__device__ __forceinline__ void stage_body(const StageCall& q, size_t ns, size_t nu, size_t nflag, size_t ncount, size_t nstate, int T,
+                                           size_t nsched) {
+  float* __restrict__ cur_s = q.cur_s; const float* __restrict__ nom_s = q.nom_s; float* __restrict__ cur_u = q.cur_u;
+  const float* __restrict__ nom_u = q.nom_u; int* __restrict__ flags = q.flags; int* __restrict__ count = q.count;
+  int* __restrict__ state = q.state; float* __restrict__ trig = q.trig; int* __restrict__ sched_cnt = q.sched_cnt;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;; i += stride) {
     bool any = false;
@@ -265,30 +232,34 @@ __global__ void stage_kernel(float* __restrict__ cur_s, const float* __restrict_
   }
 }
 
-// stage_kernel for a group of forward calls of one size (merged launches, pan_common.h): blockIdx.y = the call
+__global__ void stage_kernel(float* __restrict__ cur_s, const float* __restrict__ nom_s, size_t ns,
+                             float* __restrict__ cur_u, const float* __restrict__ nom_u, size_t nu,
+                             int* __restrict__ flags, size_t nflag, int* __restrict__ count, size_t ncount,
+                             int* __restrict__ state, size_t nstate, float* __restrict__ trig, int T,
+                             int* __restrict__ sched_cnt, size_t nsched) {
+  stage_body(StageCall{cur_s, nom_s, cur_u, nom_u, flags, count, state, trig, sched_cnt}, ns, nu, nflag, ncount, nstate, T, nsched);
+}
+
+// for a group of forward calls of one size (merged launches, pan_common.h): blockIdx.y = the call
 __global__ void stage_group_kernel(StageGroup G, size_t ns, size_t nu, size_t nflag, size_t ncount, size_t nstate, int T,
                                    size_t nsched) {
-  const StageCall& q = G.c[blockIdx.y];
-  float* __restrict__ cur_s = q.cur_s; const float* __restrict__ nom_s = q.nom_s; float* __restrict__ cur_u = q.cur_u;
-  const float* __restrict__ nom_u = q.nom_u; int* __restrict__ flags = q.flags; int* __restrict__ count = q.count;
-  int* __restrict__ state = q.state; float* __restrict__ trig = q.trig; int* __restrict__ sched_cnt = q.sched_cnt;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;; i += stride) {
-    bool any = false;
-    if (i < ns) { cur_s[i] = nom_s[i]; any = true; }
-    if (i < ncount) {
-      const size_t b = i / (size_t)(T + 1), t = i - b * (size_t)(T + 1);
-      float c, sn;
-      npa_trig(nom_s[b * 3 * (size_t)(T + 1) + 2 * (size_t)(T + 1) + t], c, sn);
-      trig[2 * i] = c; trig[2 * i + 1] = sn;
-    }
-    if (i < nu) { cur_u[i] = nom_u[i]; any = true; }
-    if (i < nflag) { flags[i] = 0; any = true; }
-    if (i < ncount) { count[i] = 0; any = true; }
-    if (i < nstate) { state[i] = 0; any = true; }
-    if (i < nsched) { sched_cnt[i] = 0; any = true; }      // the class counters of every QP launch of the call (pan_common.h)
-    if (!any) break;
-  }
+  stage_body(G.c[blockIdx.y], ns, nu, nflag, ncount, nstate, T, nsched);
+}
+
+// what a staging launch covers, and its grid: one launch instead of two copies and up to three memsets (each costs tens of
+// microseconds of stream time)
+struct StageSizes { size_t ns, nu, nflag, ncount, nstate, nsched; int blocks; };
+static const int kStageThreads = 256;
+static StageSizes stage_sizes(const npa_handle* h, int batch, bool reset_state) {
+  const int T = h->P.T;
+  StageSizes z;
+  z.ns = (size_t)batch * 3 * (T + 1); z.nu = (size_t)batch * 2 * T;
+  z.nflag = (size_t)batch * 4; z.ncount = (size_t)batch * (T + 1);
+  z.nstate = reset_state ? npa_state_bytes(h, batch) / 4 : 0;
+  z.nsched = npa_sched_cnt_ints(h->P.K);
+  const size_t work = std::max(std::max(std::max(z.ns, z.nu), z.nsched), std::max(std::max(z.nflag, z.ncount), z.nstate));
+  z.blocks = (int)std::min<size_t>((work + kStageThreads - 1) / kStageThreads, 512);
+  return z;
 }
 
 // The dispatch-order block of one QP launch (pan_common.h NPA_SCHED_NCLS; the kernels: nrmp_qp_device.h qp_sched_pick): launch j
@@ -306,6 +277,44 @@ static QpSched sched_ptrs(const npa_handle* h, PendingCall* pc, const ScratchLay
   s.out_cnt = cnt + (size_t)j * NPA_SCHED_NCLS; s.out_list = list + (size_t)(j & 1) * set;
   s.ticket = list + 2 * set;
   return s;
+}
+
+// ---- the records of one forward call's launches, from (handle, pending call, layout) -------------------------------------------
+// Both the call-by-call path (npa_forward_begin / npa_forward_iter) and the merged one (npa_group_*_merged) launch from these.
+static StageCall stage_call(const PendingCall& pc, const ScratchLayout& L) {
+  StageCall s{};
+  s.cur_s = pc.ws + L.cur_s; s.nom_s = pc.nom_s; s.cur_u = pc.ws + L.cur_u; s.nom_u = pc.nom_u;
+  s.flags = (int*)(pc.ws + L.flags); s.count = (int*)(pc.ws + L.count); s.state = (int*)pc.state; s.trig = pc.ws + L.trig;
+  s.sched_cnt = (int*)(pc.ws + L.sched);
+  return s;
+}
+
+// (audit_seed stays 0: the caller that launches the geometric selection gives it h->launch_seq++)
+static SelGeoCall sel_call(const npa_handle* h, const PendingCall& pc, const ScratchLayout& L) {
+  float* ws = pc.ws;
+  SelGeoCall s{};
+  s.wpack = h->wpack; s.cur_s = ws + L.cur_s; s.points = pc.points; s.vel = pc.velocities; s.n_points = pc.n_points;
+  s.flags = (const int*)(ws + L.flags); s.n_stride = pc.n_stride;
+  s.mu_sorted = ws + L.mu; s.lam_sorted = ws + L.lam; s.pts_sorted = ws + L.pts; s.dist_sorted = ws + L.dist;
+  s.count = (int*)(ws + L.count); s.stats = h->sel_stats_dev; s.trig = ws + L.trig;
+  s.audit = h->rows_bf16 ? nullptr : h->audit_dev;
+  return s;
+}
+
+// (counts a QP launch of the call: sched_ptrs)
+static QpCall qp_call(const npa_handle* h, PendingCall* pc, const ScratchLayout& L) {
+  float* ws = pc->ws;
+  QpCall q{};
+  q.cur_s_in = q.cur_s_out = ws + L.cur_s; q.cur_u_in = q.cur_u_out = ws + L.cur_u; q.cur_d_out = ws + L.cur_d;
+  q.ref_s = pc->ref_s; q.ref_us = pc->ref_us;
+  q.mu_sorted = ws + L.mu; q.lam_sorted = ws + L.lam; q.pts_sorted = ws + L.pts; q.dist_sorted = ws + L.dist;
+  q.count = (const int*)(ws + L.count);
+  q.out_s = pc->out_s; q.out_u = pc->out_u; q.out_d = pc->out_d; q.out_min_distance = pc->out_md; q.out_iters = pc->out_iters;
+  q.out_nrmp_points = pc->out_np;
+  q.flags = (int*)(ws + L.flags); q.state = pc->state; q.qp_info = (double*)(ws + L.qp_info);
+  q.warm = h->qp_warm ? (double*)(ws + L.warm) : nullptr; q.trig_out = pc->dune ? ws + L.trig : nullptr;
+  q.theta = pc->theta; q.sched = sched_ptrs(h, pc, L);
+  return q;
 }
 
 // ---- forward = begin + K x iter + end ------------------------------------------------------------
@@ -340,53 +349,37 @@ static void key_policy(npa_handle* h, int batch, int n_stride) {
   ++h->calls_window;
 }
 
-// launch_stage = false: everything of npa_forward_begin except the staging launch (the merged group path stages all its
-// calls with one launch, npa_group_stage_merged below)
-static int forward_begin_impl(npa_handle* h, int batch, int n_stride, const float* nom_s, const float* nom_u,
-                              const float* ref_s, const float* ref_us, const float* points,
-                              const float* velocities, const int32_t* n_points, float* out_s, float* out_u,
-                              float* out_d, float* out_min_distance, int32_t* out_iters, float* out_nrmp_points,
-                              void* workspace, size_t workspace_bytes, void* state, size_t state_bytes,
-                              void* stream_, int flags, bool launch_stage) {
-  if (!h || batch < 1 || !nom_s || !nom_u || !ref_s || !ref_us || !out_s || !out_u || !workspace || !state)
+// npa_forward_begin on a call record (launch.h); launch_stage = false: everything except the staging launch (the merged group
+// path stages all its calls with one launch, npa_group_begin_merged below)
+int npa_forward_begin_call(const npa_forward_call& a, int flags, bool launch_stage) {
+  npa_handle* h = a.h;
+  if (!h || a.batch < 1 || !a.nom_s || !a.nom_u || !a.ref_s || !a.ref_us || !a.out_s || !a.out_u || !a.workspace || !a.state)
     return fail(NPA_E_ARG, "npa_forward_begin: null argument");
   const DevParams& P = h->P;
-  if (P.M > 0 && !out_d) return fail(NPA_E_ARG, "npa_forward_begin: out_d required when nrmp_max_num > 0");
-  if (workspace_bytes < npa_workspace_bytes(h, batch)) return fail(NPA_E_ARG, "workspace too small");
-  if (state_bytes < npa_state_bytes(h, batch)) return fail(NPA_E_ARG, "state buffer too small");
-  if (points && n_stride < 1) return fail(NPA_E_ARG, "n_stride < 1");
-  if (points && (n_stride < P.dune_max_num ? n_stride : P.dune_max_num) > P.key_stride)
+  if (P.M > 0 && !a.out_d) return fail(NPA_E_ARG, "npa_forward_begin: out_d required when nrmp_max_num > 0");
+  if (a.workspace_bytes < npa_workspace_bytes(h, a.batch)) return fail(NPA_E_ARG, "workspace too small");
+  if (a.state_bytes < npa_state_bytes(h, a.batch)) return fail(NPA_E_ARG, "state buffer too small");
+  if (a.points && a.n_stride < 1) return fail(NPA_E_ARG, "n_stride < 1");
+  if (a.points && (a.n_stride < P.dune_max_num ? a.n_stride : P.dune_max_num) > P.key_stride)
     return fail(NPA_E_UNSUPPORTED, "more than 32768 points per scene after decimation");
   std::lock_guard<std::mutex> lock(h->mu);
   PendingCall* pc = &h->pc;
   if (pc->active) return fail(NPA_E_ARG, "npa_forward_begin: previous forward on this handle not ended");
-  if (int rc = check_theta_batch(h, batch, "npa_forward_begin")) return rc;
-  hipStream_t stream = (hipStream_t)stream_;
-  const int T = P.T;
-  const bool reset_state = (flags & NPA_FWD_RESET_STATE) != 0;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h), h->P.K);
-  float* ws = (float*)workspace;
-  pc->batch = batch; pc->n_stride = n_stride; pc->ref_s = ref_s; pc->ref_us = ref_us; pc->points = points;
-  pc->velocities = velocities; pc->n_points = n_points; pc->out_s = out_s; pc->out_u = out_u; pc->out_d = out_d;
-  pc->out_md = out_min_distance; pc->out_iters = out_iters; pc->out_np = out_nrmp_points; pc->ws = ws;
-  pc->state = (float*)state; pc->stream = stream;
-  pc->dune = P.M > 0 && points != nullptr;
-  pc->nom_s = nom_s; pc->nom_u = nom_u; pc->reset_state = reset_state;
+  if (int rc = check_theta_batch(h, a.batch, "npa_forward_begin")) return rc;
+  pc->batch = a.batch; pc->n_stride = a.n_stride; pc->ref_s = a.ref_s; pc->ref_us = a.ref_us; pc->points = a.points;
+  pc->velocities = a.velocities; pc->n_points = a.n_points; pc->out_s = a.out_s; pc->out_u = a.out_u; pc->out_d = a.out_d;
+  pc->out_md = a.out_min_distance; pc->out_iters = a.out_iters; pc->out_np = a.out_nrmp_points; pc->ws = (float*)a.workspace;
+  pc->state = (float*)a.state; pc->stream = (hipStream_t)a.stream;
+  pc->dune = P.M > 0 && a.points != nullptr;
+  pc->nom_s = a.nom_s; pc->nom_u = a.nom_u; pc->reset_state = (flags & NPA_FWD_RESET_STATE) != 0;
   pc->theta = h->theta;
   pc->qp_seq = 0;
-  if (pc->dune) key_policy(h, batch, n_stride);
+  if (pc->dune) key_policy(h, a.batch, a.n_stride);
   if (launch_stage) {
-    // one launch instead of two copies and up to three memsets (each costs tens of microseconds of stream time)
-    const size_t ns = (size_t)batch * 3 * (T + 1), nu2 = (size_t)batch * 2 * T;
-    const size_t nflag = (size_t)batch * 4, ncount = (size_t)batch * (T + 1);
-    const size_t nstate = reset_state ? npa_state_bytes(h, batch) / 4 : 0;
-    const size_t nsched = npa_sched_cnt_ints(P.K);
-    const size_t work = std::max(std::max(std::max(ns, nu2), nsched), std::max(std::max(nflag, ncount), nstate));
-    const int threads = 256;
-    const int blocks = (int)std::min<size_t>((work + threads - 1) / threads, 512);
-    hipLaunchKernelGGL(stage_kernel, dim3(blocks), dim3(threads), 0, stream, ws + L.cur_s, nom_s, ns, ws + L.cur_u, nom_u, nu2,
-                       (int*)(ws + L.flags), nflag, (int*)(ws + L.count), ncount, (int*)state, nstate, ws + L.trig, T,
-                       (int*)(ws + L.sched), nsched);
+    const StageCall s = stage_call(*pc, layout_of(h, a.batch));
+    const StageSizes z = stage_sizes(h, a.batch, pc->reset_state);
+    hipLaunchKernelGGL(stage_kernel, dim3(z.blocks), dim3(kStageThreads), 0, pc->stream, s.cur_s, s.nom_s, z.ns, s.cur_u, s.nom_u, z.nu,
+                       s.flags, z.nflag, s.count, z.ncount, s.state, z.nstate, s.trig, P.T, s.sched_cnt, z.nsched);
     HIP_TRY(hipGetLastError());
   }
   pc->active = true;
@@ -399,16 +392,19 @@ extern "C" int npa_forward_begin(npa_handle* h, int batch, int n_stride, const f
                                  float* out_d, float* out_min_distance, int32_t* out_iters, float* out_nrmp_points,
                                  void* workspace, size_t workspace_bytes, void* state, size_t state_bytes,
                                  void* stream_, int flags) {
-  return forward_begin_impl(h, batch, n_stride, nom_s, nom_u, ref_s, ref_us, points, velocities, n_points, out_s, out_u, out_d,
-                            out_min_distance, out_iters, out_nrmp_points, workspace, workspace_bytes, state, state_bytes, stream_,
-                            flags, true);
+  npa_forward_call a{};                  // (iter_num is not begin's business: 0)
+  a.h = h; a.batch = batch; a.n_stride = n_stride; a.nom_s = nom_s; a.nom_u = nom_u; a.ref_s = ref_s; a.ref_us = ref_us;
+  a.points = points; a.velocities = velocities; a.n_points = n_points; a.out_s = out_s; a.out_u = out_u; a.out_d = out_d;
+  a.out_min_distance = out_min_distance; a.out_iters = out_iters; a.out_nrmp_points = out_nrmp_points;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.state = state; a.state_bytes = state_bytes; a.stream = stream_;
+  return npa_forward_begin_call(a, flags, true);
 }
 
 // ---- merged launches of a group of forward calls (npa_forward_batch_group, serve_group.hip) --------------------------------
 // n calls qualify when one launch per stage can serve them all: one stream, one batch size, byte-identical kernel parameters,
 // the default selection (geometric keys; exact or bf16 rows alike) and the register-resident interior-point solve, nothing
 // that needs a launch of its own in between.  Everything else keeps the breadth-first call-by-call order.
-extern "C" int npa_group_mergeable(int n, const npa_forward_call* calls) {
+int npa_group_mergeable(int n, const npa_forward_call* calls) {
   if (n < 2 || n > NPA_GROUP_MAX || !calls) return 0;
   static const bool off = getenv("NPA_GROUP_MERGE") != nullptr && atoi(getenv("NPA_GROUP_MERGE")) == 0;
   if (off) return 0;
@@ -457,39 +453,25 @@ struct GroupLock {
 extern "C" int npa_group_begin_merged(int n, const npa_forward_call* calls, int flags, int* begun) {
   *begun = 0;
   for (int c = 0; c < n; ++c) {
-    const npa_forward_call& a = calls[c];
-    const int rc = forward_begin_impl(a.h, a.batch, a.n_stride, a.nom_s, a.nom_u, a.ref_s, a.ref_us, a.points, a.velocities,
-                                      a.n_points, a.out_s, a.out_u, a.out_d, a.out_min_distance, a.out_iters, a.out_nrmp_points,
-                                      a.workspace, a.workspace_bytes, a.state, a.state_bytes, a.stream, flags, false);
+    const int rc = npa_forward_begin_call(calls[c], flags, false);
     if (rc != NPA_OK) return rc;
     *begun = c + 1;
   }
   GroupLock group_lock(n, calls);
   npa_handle* h0 = calls[0].h;
-  const DevParams& P = h0->P;
-  const int T = P.T, batch = calls[0].batch;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h0), h0->P.K);
+  const int batch = calls[0].batch;
+  const ScratchLayout L = layout_of(h0, batch);
   StageGroup G;
   memset(&G, 0, sizeof(G));
-  for (int c = 0; c < n; ++c) {
-    const PendingCall& pc = calls[c].h->pc;
-    G.c[c] = StageCall{pc.ws + L.cur_s, pc.nom_s, pc.ws + L.cur_u, pc.nom_u, (int*)(pc.ws + L.flags), (int*)(pc.ws + L.count),
-                       (int*)pc.state, pc.ws + L.trig, (int*)(pc.ws + L.sched)};
-  }
-  const size_t ns = (size_t)batch * 3 * (T + 1), nu2 = (size_t)batch * 2 * T;
-  const size_t nflag = (size_t)batch * 4, ncount = (size_t)batch * (T + 1);
-  const size_t nstate = h0->pc.reset_state ? npa_state_bytes(h0, batch) / 4 : 0;
-  const size_t nsched = npa_sched_cnt_ints(P.K);
-  const size_t work = std::max(std::max(std::max(ns, nu2), nsched), std::max(std::max(nflag, ncount), nstate));
-  const int threads = 256;
-  const int blocks = (int)std::min<size_t>((work + threads - 1) / threads, 512);
-  hipLaunchKernelGGL(stage_group_kernel, dim3(blocks, n), dim3(threads), 0, h0->pc.stream, G, ns, nu2, nflag, ncount, nstate, T,
-                     nsched);
+  for (int c = 0; c < n; ++c) G.c[c] = stage_call(calls[c].h->pc, L);
+  const StageSizes z = stage_sizes(h0, batch, h0->pc.reset_state);
+  hipLaunchKernelGGL(stage_group_kernel, dim3(z.blocks, n), dim3(kStageThreads), 0, h0->pc.stream, G, z.ns, z.nu, z.nflag, z.ncount,
+                     z.nstate, h0->P.T, z.nsched);
   HIP_TRY(hipGetLastError());
   return NPA_OK;
 }
 
-// (diagnostics, not in the header: merged QP launches issued by this process so far -- the tests check that the merged path ran)
+// (diagnostics, exported through launch.h: merged QP launches issued by this process so far -- the tests check that the merged path ran)
 static std::atomic<unsigned long long> g_merged_launches{0};
 extern "C" unsigned long long npa_dbg_group_merged_launches(void) { return g_merged_launches.load(); }
 
@@ -499,8 +481,8 @@ extern "C" int npa_group_iter_merged(int n, const npa_forward_call* calls, int k
   npa_handle* h0 = calls[0].h;
   const DevParams& P = h0->P;
   if (k < 0 || k >= P.K) return fail(NPA_E_ARG, "npa_forward_batch_group: iteration index out of range");
-  const int T = P.T, batch = calls[0].batch;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h0), h0->P.K);
+  const int batch = calls[0].batch;
+  const ScratchLayout L = layout_of(h0, batch);
   hipStream_t stream = h0->pc.stream;
   for (int c = 0; c < n; ++c)
     if (!calls[c].h->pc.active) return fail(NPA_E_ARG, "npa_forward_batch_group: a call of the group is not in progress");
@@ -510,30 +492,17 @@ extern "C" int npa_group_iter_merged(int n, const npa_forward_call* calls, int k
     int n_stride_max = 1;
     for (int c = 0; c < n; ++c) {
       npa_handle* h = calls[c].h;
-      const PendingCall& pc = h->pc;
-      float* ws = pc.ws;
-      G.c[c] = SelGeoCall{h->wpack, ws + L.cur_s, pc.points, pc.velocities, pc.n_points, (const int*)(ws + L.flags),
-                          ws + L.mu, ws + L.lam, ws + L.pts, ws + L.dist, (int*)(ws + L.count), h->sel_stats_dev, ws + L.trig,
-                          h->rows_bf16 ? nullptr : h->audit_dev, pc.n_stride, h->launch_seq++};
-      if (pc.n_stride > n_stride_max) n_stride_max = pc.n_stride;
+      G.c[c] = sel_call(h, h->pc, L);
+      G.c[c].audit_seed = h->launch_seq++;
+      if (h->pc.n_stride > n_stride_max) n_stride_max = h->pc.n_stride;
     }
     EventPair* evs = next_event(h0, h0->ev_sel, h0->n_sel);
-    HIP_TRY(npa_launch_select_geo_group(P, G, n, batch, k == 0 ? 0 : 1, n_stride_max, 0, h0->audit_thresh,
-                                        h0->margin_scale, h0->cal.keys_bf16 ? 2 : 0, stream, evs ? evs->a : nullptr,
-                                        evs ? evs->b : nullptr));
+    HIP_TRY(npa_launch_select_geo_group(P, G, n, batch, k == 0 ? 0 : 1, n_stride_max, 0, h0->audit_thresh, h0->margin_scale,
+                                        rows_tier(h0), stream, evs ? evs->a : nullptr, evs ? evs->b : nullptr));
   }
   QpGroup Q;
   memset(&Q, 0, sizeof(Q));
-  for (int c = 0; c < n; ++c) {
-    npa_handle* h = calls[c].h;
-    const PendingCall& pc = h->pc;
-    float* ws = pc.ws;
-    float *cur_s = ws + L.cur_s, *cur_u = ws + L.cur_u;
-    Q.c[c] = QpCall{cur_s, cur_u, pc.ref_s, pc.ref_us, ws + L.mu, ws + L.lam, ws + L.pts, ws + L.dist, (const int*)(ws + L.count),
-                    cur_s, cur_u, ws + L.cur_d, pc.out_s, pc.out_u, pc.out_d, pc.out_md, pc.out_iters, pc.out_np,
-                    (int*)(ws + L.flags), pc.state, (double*)(ws + L.qp_info), h->qp_warm ? (double*)(ws + L.warm) : nullptr,
-                    pc.dune ? ws + L.trig : nullptr, pc.theta, sched_ptrs(h, &h->pc, L)};
-  }
+  for (int c = 0; c < n; ++c) Q.c[c] = qp_call(calls[c].h, &calls[c].h->pc, L);
   EventPair* ev = next_event(h0, h0->ev_qp, h0->n_qp);
   HIP_TRY(npa_launch_qp_group(P, Q, n, batch, stream, ev ? ev->a : nullptr, ev ? ev->b : nullptr));
   g_merged_launches.fetch_add(1);
@@ -547,44 +516,32 @@ extern "C" int npa_forward_iter(npa_handle* h, int k) {
   if (!pc->active) return fail(NPA_E_ARG, "npa_forward_iter: no forward in progress on this handle");
   const DevParams& P = h->P;
   if (k < 0 || k >= P.K) return fail(NPA_E_ARG, "npa_forward_iter: iteration index out of range");
-  const int T = P.T, batch = pc->batch;
+  const int batch = pc->batch;
   const bool geo = h->key_terms == 4;
-  const ScratchLayout L = npa_scratch_layout(batch, T, mdim(P), P.E, kstride(h), h->P.K);
-  float* ws = pc->ws;
-  float *cur_s = ws + L.cur_s, *cur_u = ws + L.cur_u, *cur_d = ws + L.cur_d;
-  float *mu = ws + L.mu, *lam = ws + L.lam, *pts = ws + L.pts, *dist = ws + L.dist;
-  int* count = (int*)(ws + L.count);
-  int* flags = (int*)(ws + L.flags);
-  double* qp_info = (double*)(ws + L.qp_info);
-  unsigned* gkeys = (unsigned*)(ws + L.keys);
+  const ScratchLayout L = layout_of(h, batch);
   hipStream_t stream = pc->stream;
   if (pc->dune) {
     // slice 0 does not depend on the iterate (s(0) is pinned, robot.py:234): after the first iteration of a forward
     // call only slices 1..T are redone
     const int t0 = k == 0 ? 0 : 1;
+    SelGeoCall sel = sel_call(h, *pc, L);
+    unsigned* gkeys = (unsigned*)(pc->ws + L.keys);
     if (!geo) {
       EventPair* ev = next_event(h, h->ev_dune, h->n_dune);
-      HIP_TRY(npa_launch_encode(P, h->wpack, batch, 0, t0, pc->n_stride, cur_s, pc->points, pc->velocities,
-                                pc->n_points, flags, gkeys, ws + L.trig, h->n_cu, 5, h->key_terms, stream,
-                                ev ? ev->a : nullptr, ev ? ev->b : nullptr));
+      HIP_TRY(npa_launch_encode(P, sel, batch, t0, gkeys, h->n_cu, 5, h->key_terms, stream, ev ? ev->a : nullptr, ev ? ev->b : nullptr));
     }
     EventPair* evs = next_event(h, h->ev_sel, h->n_sel);
-    if (geo && !h->select_v1)
-      HIP_TRY(npa_launch_select_geo(P, h->wpack, batch, 0, t0, pc->n_stride, cur_s, pc->points, pc->velocities, pc->n_points,
-                                    flags, ws + L.trig, mu, lam, pts, dist, count, h->sel_stats_dev, 0,
-                                    h->rows_bf16 ? nullptr : h->audit_dev, h->audit_thresh, h->launch_seq++, h->margin_scale,
-                                    h->rows_bf16 ? 1 : (h->cal.keys_bf16 ? 2 : 0), stream, evs ? evs->a : nullptr, evs ? evs->b : nullptr));
-    else
-      HIP_TRY(npa_launch_select(P, h->wpack, batch, 0, t0, pc->n_stride, cur_s, pc->points, pc->velocities,
-                                pc->n_points, flags, gkeys, ws + L.trig, mu, lam, pts, dist, count, h->key_terms, h->key_e0,
-                                h->sel_stats_dev, 0, stream, evs ? evs->a : nullptr, evs ? evs->b : nullptr));
+    if (geo && !h->select_v1) {
+      sel.audit_seed = h->launch_seq++;
+      HIP_TRY(npa_launch_select_geo(P, sel, batch, t0, 0, h->audit_thresh, h->margin_scale, rows_tier(h), stream,
+                                    evs ? evs->a : nullptr, evs ? evs->b : nullptr));
+    } else {
+      HIP_TRY(npa_launch_select(P, sel, batch, t0, gkeys, h->key_terms, h->key_e0, 0, stream, evs ? evs->a : nullptr,
+                                evs ? evs->b : nullptr));
+    }
   }
   EventPair* ev = next_event(h, h->ev_qp, h->n_qp);
-  HIP_TRY(npa_launch_qp(P, batch, 0, cur_s, cur_u, pc->ref_s, pc->ref_us, mu, lam, pts, dist, count, cur_s, cur_u,
-                        cur_d, pc->out_s, pc->out_u, pc->out_d, pc->out_md, pc->out_iters, pc->out_np, flags,
-                        pc->state, qp_info, h->qp_warm ? (double*)(ws + L.warm) : nullptr, pc->dune ? ws + L.trig : nullptr,
-                        nullptr, nullptr, nullptr, stream,
-                        ev ? ev->a : nullptr, ev ? ev->b : nullptr, pc->theta, sched_ptrs(h, pc, L)));
+  HIP_TRY(npa_launch_qp(P, qp_call(h, pc, L), batch, QpBackward{}, stream, ev ? ev->a : nullptr, ev ? ev->b : nullptr));
   if (h->cal.key_auto && pc->dune && k == P.K - 1)
     HIP_TRY(hipMemcpyAsync(h->sel_stats_host, h->sel_stats_dev, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
   return NPA_OK;
@@ -596,14 +553,6 @@ extern "C" int npa_forward_end(npa_handle* h) {
   PendingCall* pc = &h->pc;
   if (!pc->active) return fail(NPA_E_ARG, "npa_forward_end: no forward in progress on this handle");
   pc->active = false;
-  return NPA_OK;
-}
-
-// (diagnostics, not in the header: the four words of the selection's statistics since the handle was created; synchronises the device)
-extern "C" int npa_dbg_select_stats(npa_handle* h, unsigned out[4]) {
-  if (!h || !out || !h->sel_stats_dev) return NPA_E_ARG;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, h->sel_stats_dev, 4 * sizeof(unsigned), hipMemcpyDeviceToHost));
   return NPA_OK;
 }
 
@@ -654,10 +603,6 @@ extern "C" int npa_nominal_ref_states(int batch, int receding, int kinematics, d
   return NPA_OK;
 }
 
-extern "C" hipError_t npa_launch_progress(int batch, const double* state, const double* path, const int* curve_off,
-                                          const int* curve_len, int* point_index, double close_threshold, int ind_range,
-                                          double arrive_threshold, int arrive_index_threshold, float* min_dis,
-                                          int* arrived, hipStream_t stream);
 extern "C" int npa_path_progress(int batch, const double* state, const double* path, const int32_t* curve_off,
                                  const int32_t* curve_len, int32_t* point_index, double close_threshold, int ind_range,
                                  double arrive_threshold, int arrive_index_threshold, float* min_dis, int32_t* arrived,
@@ -681,17 +626,6 @@ extern "C" int npa_scan_to_points(int batch, int beam_stride, const double* rang
 }
 
 // ---- the bookkeeping of a device-resident closed loop (cycle.hip) ------------------------------------
-extern "C" hipError_t npa_launch_cycle_switch(int batch, int loop, const double* state, const int* curve_arrived,
-                                              const int* curve_off, const int* curve_len, const int* robot_first,
-                                              int* curve_index, int* cur_off, int* cur_len, int* point_index, int* arrived,
-                                              npa_scan_params* params_a, npa_scan_params* params_b, hipStream_t stream);
-extern "C" hipError_t npa_launch_cycle_act(int batch, int T, int kin, int first_cycle, int cycle, const float* opt_u,
-                                           const float* min_distance, float threshold, const int* arrived, const int* collided,
-                                           const float* override_row, const int* n_points, float* cur_vel, float* action,
-                                           uint8_t* stop, int* frozen, float* log_actions, uint8_t* log_stop,
-                                           float* log_controls, int* log_n_points, hipStream_t stream);
-extern "C" hipError_t npa_launch_cycle_commit(int batch, int cycle, const double* state, const double* clearance, int* collided,
-                                              double* log_states, double* log_clearance, hipStream_t stream);
 
 extern "C" int npa_cycle_progress(int batch, const double* state, const double* path, const int32_t* curve_off,
                                   const int32_t* curve_len, const int32_t* robot_first, int loop, double close_threshold,
@@ -731,12 +665,6 @@ extern "C" int npa_cycle_commit(int batch, int cycle, const double* state, const
   return NPA_OK;
 }
 
-extern "C" hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, double min_radius, const double* state,
-                                              int* arrived, const int* collided, double* path, const int* curve_off,
-                                              int* curve_len, const int* robot_first, const int* row_capacity,
-                                              const double* goals, int g_stride, const int* n_goals, int* goal_index,
-                                              const double* interval, int* curve_index, int* cur_off, int* cur_len,
-                                              int* point_index, float* cur_vel, int* status, int* log_goal, hipStream_t stream);
 
 extern "C" int npa_cycle_retask(int batch, int receding, int cycle, int style, double min_radius, const double* state,
                                 int32_t* arrived, const int32_t* collided, double* path, const int32_t* curve_off,
@@ -797,9 +725,6 @@ extern "C" int npa_ingest_unpack(int batch, int receding, int n_stride, int with
 }
 
 // ---- exact clearance of a plan against the full cloud (csrc/clearance.hip) ----
-extern "C" hipError_t npa_launch_clearance(const DevParams& P, int batch, int n_stride, const float* traj, const float* points,
-                                           const float* velocities, const int* n_points, float threshold, float* clearance,
-                                           int* nearest, float* min_clearance, int* first_violation, hipStream_t stream);
 extern "C" int npa_plan_clearance(npa_handle* h, int batch, int n_stride, const float* traj_s, const float* points,
                                   const float* velocities, const int32_t* n_points, float threshold, float* clearance,
                                   int32_t* nearest, float* min_clearance, int32_t* first_violation, void* stream) {
@@ -817,8 +742,6 @@ extern "C" int npa_plan_clearance(npa_handle* h, int batch, int n_stride, const 
   return NPA_OK;
 }
 
-extern "C" hipError_t npa_launch_labels(int E, const double* G, const double* h, long long n, const double* points,
-                                        float* mu, float* dist, hipStream_t stream);
 extern "C" int npa_dune_labels(int edge_num, const double* G, const double* h, int64_t n, const double* points,
                                float* mu, float* dist, void* stream) {
   if (!G || !h || n < 0 || (n > 0 && (!points || !mu || !dist))) return fail(NPA_E_ARG, "npa_dune_labels: bad argument");

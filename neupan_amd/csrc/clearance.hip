@@ -15,7 +15,7 @@
 
 #include <cmath>
 
-#include "pan_common.h"
+#include "launch.h"
 
 namespace {
 
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(CLR_THREADS) void clearance_kernel(
 
 }  // namespace
 
-extern "C" hipError_t npa_launch_clearance(const DevParams& P, int batch, int n_stride, const float* traj, const float* points,
+hipError_t npa_launch_clearance(const DevParams& P, int batch, int n_stride, const float* traj, const float* points,
                                            const float* velocities, const int* n_points, float threshold, float* clearance,
                                            int* nearest, float* min_clearance, int* first_violation, hipStream_t stream) {
   if (P.E < 3 || P.E > NPA_MAX_E || P.T + 1 > CLR_STEPS) return hipErrorInvalidValue;

@@ -1,8 +1,8 @@
 // create.hip -- npa_create / npa_destroy: configuration -> DevParams, the shared weight pack and its calibration, the per-handle
 // buffers, the create-time self-test; and the introspection / setter exports of what creation leaves in a handle.
-// Host-side only.  Shares state with c_api.hip (the forward path) through handle.h alone.
+// Host-side only.  Shares state with c_api.hip (the forward path) through handle.h alone; what it calls in other units: launch.h.
 #include "handle.h"
-#include "pack_image.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -10,17 +10,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
-
-extern "C" hipError_t npa_launch_key_calib(const DevParams& P, const float* wpack, int key_terms, int nside, float half,
-                                           unsigned* out, hipStream_t stream);
-extern "C" hipError_t npa_launch_geo_table(const DevParams& P, float* wpack, float* nodes, int n_cu, hipStream_t stream);
-extern "C" hipError_t npa_launch_ktab_calib(const DevParams& P, const float* wpack, int nside, float half, float inner, float cx, float cy,
-                                            unsigned* out, int n_cu, hipStream_t stream);
-extern "C" hipError_t npa_launch_geo_calib(const DevParams& P, const float* wpack, int nside, float half, float inner,
-                                           float shift, unsigned* out, int n_cu, hipStream_t stream);
-extern "C" hipError_t npa_launch_k16_calib(const DevParams& P, const float* wpack, int nside, float half, float inner, unsigned* out,
-                                           int n_cu, hipStream_t stream);
-extern "C" size_t npa_qp_shmem_bytes(int T, int M);
 
 static std::mutex g_pack_mu;                                   // held across a creation's calibration: same-key creates queue up
 static std::map<std::string, std::weak_ptr<SharedPack>> g_packs;
@@ -425,7 +414,7 @@ static int params_from_config(const npa_config* cfg, const npa_dune_weights* w, 
   return NPA_OK;
 }
 
-// (diagnostics, not in the header: the device-free part of npa_create -- the pack's host image, the DevParams bytes as they
+// (diagnostics, exported through launch.h: the device-free part of npa_create -- the pack's host image, the DevParams bytes as they
 // stand before any calibration, geo_valid and the image's named offsets WP_W1, WP_WL, WP_VEC, WP_W6, WP_B6, WP_BF, WP_WLS,
 // WP_WB16, WP_TABH, WP_W116, WP_WL16, WP_VEC16, WP_TOTAL, in floats.  Every output may be null; *params_size = sizeof(DevParams).
 // Touches no device.)
@@ -462,7 +451,7 @@ static hipError_t audit_block_reset(npa_handle* h) {
 }
 
 static hipError_t alloc_handle_buffers(npa_handle* h) {
-  // word 0: overflow tiles of the selection (key policy); words 1 .. 3 spare (npa_dbg_select_stats)
+  // word 0: overflow tiles of the selection (key policy); words 1 .. 3 spare
   hipError_t e = hipMalloc(&h->sel_stats_dev, 4 * sizeof(unsigned));
   if (e == hipSuccess) e = hipMemset(h->sel_stats_dev, 0, 4 * sizeof(unsigned));
   if (e == hipSuccess) e = hipHostMalloc(&h->sel_stats_host, sizeof(unsigned), hipHostMallocDefault);

@@ -10,13 +10,7 @@
 #include <cmath>
 
 #include "handle.h"
-
-extern "C" hipError_t npa_launch_curve_batch(int batch, int style, const double* start, const double* goal, const double* interval,
-                                             double min_radius, int capacity, const int* mask, double* rows_out, int* n_rows,
-                                             hipStream_t stream);
-
-extern "C" hipError_t npa_launch_route_relax(const uint8_t* blocked, int nx, int ny, int n_fields, uint32_t* fields, int sweeps,
-                                             uint32_t sweep_base, uint32_t* changed, hipStream_t stream);
+#include "launch.h"
 
 namespace {
 

@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/neupan_amd.h"
+#include "launch.h"
 #include "curves.h"
 
 namespace {
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(RT_TILE* RT_TILE) void route_sweep_kernel(RouteArgs
 
 }  // namespace
 
-extern "C" hipError_t npa_launch_route_relax(const uint8_t* blocked, int nx, int ny, int n_fields, uint32_t* fields, int sweeps,
+hipError_t npa_launch_route_relax(const uint8_t* blocked, int nx, int ny, int n_fields, uint32_t* fields, int sweeps,
                                              uint32_t sweep_base, uint32_t* changed, hipStream_t stream) {
   RouteArgs a = {blocked, fields, changed, nx, ny, sweep_base};
   const dim3 grid((nx + RT_TILE - 1) / RT_TILE, (ny + RT_TILE - 1) / RT_TILE, n_fields);
@@ -249,7 +249,7 @@ extern "C" hipError_t npa_launch_route_relax(const uint8_t* blocked, int nx, int
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_curve_batch(int batch, int style, const double* start, const double* goal, const double* interval,
+hipError_t npa_launch_curve_batch(int batch, int style, const double* start, const double* goal, const double* interval,
                                              double min_radius, int capacity, const int* mask, double* rows_out, int* n_rows,
                                              hipStream_t stream) {
   CurveWaveArgs a = {};
@@ -259,7 +259,7 @@ extern "C" hipError_t npa_launch_curve_batch(int batch, int style, const double*
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, double min_radius, const double* state,
+hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, double min_radius, const double* state,
                                               int* arrived, const int* collided, double* path, const int* curve_off,
                                               int* curve_len, const int* robot_first, const int* row_capacity,
                                               const double* goals, int g_stride, const int* n_goals, int* goal_index,
@@ -272,7 +272,7 @@ extern "C" hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int s
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_cycle_switch(int batch, int loop, const double* state, const int* curve_arrived,
+hipError_t npa_launch_cycle_switch(int batch, int loop, const double* state, const int* curve_arrived,
                                               const int* curve_off, const int* curve_len, const int* robot_first,
                                               int* curve_index, int* cur_off, int* cur_len, int* point_index, int* arrived,
                                               npa_scan_params* params_a, npa_scan_params* params_b, hipStream_t stream) {
@@ -282,7 +282,7 @@ extern "C" hipError_t npa_launch_cycle_switch(int batch, int loop, const double*
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_cycle_act(int batch, int T, int kin, int first_cycle, int cycle, const float* opt_u,
+hipError_t npa_launch_cycle_act(int batch, int T, int kin, int first_cycle, int cycle, const float* opt_u,
                                            const float* min_distance, float threshold, const int* arrived, const int* collided,
                                            const float* override_row, const int* n_points, float* cur_vel, float* action,
                                            uint8_t* stop, int* frozen, float* log_actions, uint8_t* log_stop,
@@ -293,7 +293,7 @@ extern "C" hipError_t npa_launch_cycle_act(int batch, int T, int kin, int first_
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_cycle_commit(int batch, int cycle, const double* state, const double* clearance, int* collided,
+hipError_t npa_launch_cycle_commit(int batch, int cycle, const double* state, const double* clearance, int* collided,
                                               double* log_states, double* log_clearance, hipStream_t stream) {
   hipLaunchKernelGGL(cycle_commit_kernel, dim3((batch + CY_THREADS - 1) / CY_THREADS), dim3(CY_THREADS), 0, stream, batch, cycle,
                      state, clearance, collided, log_states, log_clearance);

@@ -31,7 +31,7 @@
 //   * on gfx950 the fp32-input MFMA and fp32 VALU work serialise on the SIMD (PMC:
 //     SQ_VALU_MFMA_COEXEC_CYCLES = 0), so the VALU instruction count per tile matters as much as
 //     the 65 MFMAs.
-#include "pan_common.h"
+#include "launch.h"
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <cstdlib>
@@ -48,16 +48,13 @@ static int tiles_per_slice(const DevParams& P, int n_stride) {
   return (n_use_max + 31) / 32;
 }
 
-extern "C" hipError_t npa_launch_encode(const DevParams& P, const float* wpack, int batch, int scene0, int t0,
-                                        int n_stride, const float* cur_s, const float* points, const float* vel,
-                                        const int* n_points, const int* flags, unsigned* gkeys, const float* trig,
-                                        int n_cu, int blocks_per_cu, int key_terms, hipStream_t stream,
-                                        hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t npa_launch_encode(const DevParams& P, const SelGeoCall& c, int batch, int t0, unsigned* gkeys, int n_cu, int blocks_per_cu,
+                             int key_terms, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
   // key_terms: 0 = exact fp32 encoder for the keys, 3 = fp16x2 split products, 1 = single fp16 products
   // ev_start / ev_stop (may be null) are attached to the dispatch itself (hipExtLaunchKernelGGL): no
   // separate marker packets on the stream, which cost ~5 us each between back-to-back launches
   const int nsl = P.T + 1 - t0;
-  const int tps = tiles_per_slice(P, n_stride);
+  const int tps = tiles_per_slice(P, c.n_stride);
   if (tps * 32 > P.key_stride) return hipErrorInvalidValue;
   const long long tiles = (long long)batch * nsl * tps;
   if (tiles >= (1ll << 31)) return hipErrorInvalidValue;
@@ -78,8 +75,8 @@ extern "C" hipError_t npa_launch_encode(const DevParams& P, const float* wpack, 
   const int chunk = chunk_env < 1 ? 1 : chunk_env;
 #define LAUNCH1(EE, SP, WV)                                                                                         \
   hipExtLaunchKernelGGL((dune_kernel<EE, SP, WV>), dim3(blocks), dim3(64 * WV), shmem, stream, ev_start, ev_stop, 0, \
-                        P, wpack, n_stride, cur_s, points, vel, n_points, flags, gkeys, tps * 32, scene0, batch, t0, \
-                        chunk, trig)
+                        P, c.wpack, c.n_stride, c.cur_s, c.points, c.vel, c.n_points, c.flags, gkeys, tps * 32, 0, batch, t0, \
+                        chunk, c.trig)
 #define LAUNCH(EE)                                                                                                  \
   do {                                                                                                              \
     if (single) LAUNCH1(EE, 1, DUNE_WAVES);                                                                         \
@@ -107,18 +104,14 @@ extern "C" hipError_t npa_launch_encode(const DevParams& P, const float* wpack, 
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_select(const DevParams& P, const float* wpack, int batch, int scene0, int t0,
-                                        int n_stride, const float* cur_s, const float* points, const float* vel,
-                                        const int* n_points, const int* flags, const unsigned* gkeys,
-                                        const float* trig, float* mu_sorted, float* lam_sorted, float* pts_sorted,
-                                        float* dist_sorted, int* count, int key_terms, float e0, unsigned* stats,
-                                        int debug, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t npa_launch_select(const DevParams& P, const SelGeoCall& c, int batch, int t0, const unsigned* gkeys, int key_terms, float e0,
+                             int debug, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
   // ev_start / ev_stop (may be null) ride on the dispatch (hipExtLaunchKernelGGL): no marker packets on the stream
   // debug != 0: count[] also carries the number of candidates and the overflow flag (tests/tools/geo_check.py)
   // key_terms: 0 = exact network keys in gkeys, 1 / 3 = reduced-precision network keys in gkeys (candidates within
   // the margin e0 (1 + |d|) are re-ranked), 4 = geometric keys computed by select_kernel itself (gkeys unused)
   const int nsl = P.T + 1 - t0;
-  const int tps = tiles_per_slice(P, n_stride);
+  const int tps = tiles_per_slice(P, c.n_stride);
   const int dbg = debug ? 2 : 1;
   const bool geo = key_terms == 4;
   const int approx = key_terms == 0 ? 0 : dbg;
@@ -137,8 +130,8 @@ extern "C" hipError_t npa_launch_select(const DevParams& P, const float* wpack, 
       big_lds.done(dev_);                                                                                           \
     }                                                                                                               \
     hipExtLaunchKernelGGL((select_kernel<EE, GG>), dim3(nsl, batch), dim3(64), shmem, stream, ev_start, ev_stop, 0, P,    \
-                          wpack, n_stride, cur_s, points, vel, n_points, flags, gkeys, tps * 32, mu_sorted, lam_sorted, \
-                          pts_sorted, dist_sorted, count, scene0, t0, approx, e0, stats, trig);                      \
+                          c.wpack, c.n_stride, c.cur_s, c.points, c.vel, c.n_points, c.flags, gkeys, tps * 32, c.mu_sorted,   \
+                          c.lam_sorted, c.pts_sorted, c.dist_sorted, c.count, 0, t0, approx, e0, c.stats, c.trig);     \
   } while (0)
 #ifdef NPA_EXPERIMENTS
 #define LAUNCH(EE)                                                                                                  \
@@ -167,17 +160,12 @@ extern "C" hipError_t npa_launch_select(const DevParams& P, const float* wpack, 
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_select_geo(const DevParams& P, const float* wpack, int batch, int scene0, int t0,
-                                            int n_stride, const float* cur_s, const float* points, const float* vel,
-                                            const int* n_points, const int* flags, const float* trig, float* mu_sorted,
-                                            float* lam_sorted, float* pts_sorted, float* dist_sorted, int* count,
-                                            unsigned* stats, int debug, unsigned* audit, unsigned audit_thresh,
-                                            unsigned audit_seed, float margin_scale, int rows_bf16, hipStream_t stream,
-                                            hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t npa_launch_select_geo(const DevParams& P, const SelGeoCall& c, int batch, int t0, int debug, unsigned audit_thresh,
+                                 float margin_scale, int rows_bf16, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
   // select_geo_kernel: one wave per (scene, slice); the grid is padded to a multiple of 8 scenes so that the XCD-aware
   // block -> (scene, slice) map covers every scene (the surplus workgroups return at once)
   const int nsl = P.T + 1 - t0;
-  int n_use_max = n_stride < P.dune_max_num ? n_stride : P.dune_max_num;
+  int n_use_max = c.n_stride < P.dune_max_num ? c.n_stride : P.dune_max_num;
   if (n_use_max < 1) n_use_max = 1;
   const size_t n_pad = ((size_t)n_use_max + SEL2_TRIP - 1) / SEL2_TRIP * SEL2_TRIP;
   const size_t key_area = std::max<size_t>(n_pad * sizeof(unsigned), SEL_CAP * (NPA_MAX_E + 5 + 2) * sizeof(float));
@@ -194,9 +182,10 @@ extern "C" hipError_t npa_launch_select_geo(const DevParams& P, const float* wpa
       if (e_ != hipSuccess) return e_;                                                                              \
       big_lds.done(dev_);                                                                                           \
     }                                                                                                               \
-    hipExtLaunchKernelGGL((select_geo_kernel<EE, BB, KK>), dim3(blocks), dim3(64), shmem, stream, ev_start, ev_stop, 0, P, wpack,  \
-                          n_stride, cur_s, points, vel, n_points, flags, mu_sorted, lam_sorted, pts_sorted, dist_sorted, \
-                          count, scene0, t0, nsl, batch, debug, stats, trig, audit, audit_thresh, audit_seed, margin_scale); \
+    hipExtLaunchKernelGGL((select_geo_kernel<EE, BB, KK>), dim3(blocks), dim3(64), shmem, stream, ev_start, ev_stop, 0, P, c.wpack, \
+                          c.n_stride, c.cur_s, c.points, c.vel, c.n_points, c.flags, c.mu_sorted, c.lam_sorted, c.pts_sorted,    \
+                          c.dist_sorted, c.count, 0, t0, nsl, batch, debug, c.stats, c.trig, c.audit, audit_thresh, c.audit_seed, \
+                          margin_scale);                                                                            \
   } while (0)
   // rows_bf16: 0 = exact; 1 = the reduced-precision tier of the ROWS; 2 = the bf16 tier of the KEYS (rows exact).  Both tiers are
   // instantiated for the two polygon sizes the benchmark configurations use.
@@ -228,7 +217,7 @@ extern "C" hipError_t npa_launch_select_geo(const DevParams& P, const float* wpa
 
 // select_geo_kernel for a group of n forward calls that share the configuration, the batch size and the stream (c_api.hip
 // checks that): ONE launch, grid (blocks of one call, n).  n_stride_max sizes the LDS key area.
-extern "C" hipError_t npa_launch_select_geo_group(const DevParams& P, const SelGeoGroup& G, int n, int batch, int t0, int n_stride_max,
+hipError_t npa_launch_select_geo_group(const DevParams& P, const SelGeoGroup& G, int n, int batch, int t0, int n_stride_max,
                                                   int debug, unsigned audit_thresh, float margin_scale, int rows_bf16,
                                                   hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop) {
   if (n < 1 || n > NPA_GROUP_MAX) return hipErrorInvalidValue;
@@ -262,7 +251,7 @@ extern "C" hipError_t npa_launch_select_geo_group(const DevParams& P, const SelG
 #undef LAUNCHG
   return hipGetLastError();
 }
-extern "C" int npa_select_geo_group_supported(int E) { return E == 4 || E == 8; }
+int npa_select_geo_group_supported(int E) { return E == 4 || E == 8; }
 
 // ---- geometric-key calibration (npa_create) ----------------------------------------------------------
 // f(p) = network distance - geometric distance is a smooth function of the robot-frame position and a property of
@@ -318,7 +307,7 @@ __global__ __launch_bounds__(256) void geo_calib_kernel(DevParams P, const float
     if (tab[i]) atomicMax(&out[i], tab[i]);
 }
 
-extern "C" hipError_t npa_launch_geo_calib(const DevParams& P, const float* wpack, int nside, float half, float inner,
+hipError_t npa_launch_geo_calib(const DevParams& P, const float* wpack, int nside, float half, float inner,
                                            float shift, unsigned* out, int n_cu, hipStream_t stream) {
   const size_t shmem = (11 * 32 + 8 * 32 + 8 + 2 * NPA_GEO_BANDS) * sizeof(float);
   const int blocks = n_cu * 4;
@@ -377,7 +366,7 @@ __global__ __launch_bounds__(256) void k16_calib_kernel(DevParams P, const float
   for (int i = tid; i < NPA_GEO_BANDS; i += blockDim.x)
     if (tab[i]) atomicMax(&out[i], tab[i]);
 }
-extern "C" hipError_t npa_launch_k16_calib(const DevParams& P, const float* wpack, int nside, float half, float inner, unsigned* out,
+hipError_t npa_launch_k16_calib(const DevParams& P, const float* wpack, int nside, float half, float inner, unsigned* out,
                                            int n_cu, hipStream_t stream) {
   const size_t shmem = (11 * 32 + 8 * 32 + 8 + NPA_GEO_BANDS) * sizeof(float);
   const int blocks = n_cu * 4;
@@ -429,7 +418,7 @@ __global__ void geo_table_pack_kernel(const float* __restrict__ nodes, float* __
   hi.h[0] = (_Float16)nl[(iy + 1) * nside + ix]; hi.h[1] = (_Float16)nl[(iy + 1) * nside + ix + 1];
   reinterpret_cast<uint2*>(wpack + WP_TAB)[c] = make_uint2(lo.u, hi.u);
 }
-extern "C" hipError_t npa_launch_geo_table(const DevParams& P, float* wpack, float* nodes, int n_cu, hipStream_t stream) {
+hipError_t npa_launch_geo_table(const DevParams& P, float* wpack, float* nodes, int n_cu, hipStream_t stream) {
   const size_t shmem = (11 * 32 + 8 * 32 + 8) * sizeof(float);
   const int blocks = n_cu * 4;
   // (built for the polygon sizes the filter is built for: select_geo_body.inc, TABF)
@@ -484,7 +473,7 @@ __global__ __launch_bounds__(256) void ktab_calib_kernel(DevParams P, const floa
   for (int i = tid; i < NPA_GEO_BANDS; i += blockDim.x)
     if (tab[i]) atomicMax(&out[i], tab[i]);
 }
-extern "C" hipError_t npa_launch_ktab_calib(const DevParams& P, const float* wpack, int nside, float half, float inner, float cx, float cy,
+hipError_t npa_launch_ktab_calib(const DevParams& P, const float* wpack, int nside, float half, float inner, float cx, float cy,
                                             unsigned* out, int n_cu, hipStream_t stream) {
   const size_t shmem = (11 * 32 + 8 * 32 + 8 + NPA_GEO_BANDS) * sizeof(float);
   const int blocks = n_cu * 4;
@@ -539,7 +528,7 @@ __global__ __launch_bounds__(256) void key_calib_kernel(DevParams P, const float
   if (hf == 0 && n < total) atomicMax(out, __float_as_uint(rel));
 }
 
-extern "C" hipError_t npa_launch_key_calib(const DevParams& P, const float* wpack, int key_terms, int nside, float half,
+hipError_t npa_launch_key_calib(const DevParams& P, const float* wpack, int key_terms, int nside, float half,
                                            unsigned* out, hipStream_t stream) {
   const int tiles = (nside * nside + 31) / 32, blocks = (tiles + 3) / 4;
   const float lo = -half, step = 2.0f * half / (float)(nside - 1);
@@ -565,7 +554,7 @@ __global__ void trig_kernel(const float* __restrict__ cur_s, int nscene, int T, 
   trig[2 * (size_t)i] = c;
   trig[2 * (size_t)i + 1] = s;
 }
-extern "C" hipError_t npa_launch_trig(const float* cur_s, int batch, int T, float* trig, hipStream_t stream) {
+hipError_t npa_launch_trig(const float* cur_s, int batch, int T, float* trig, hipStream_t stream) {
   const int n = batch * (T + 1);
   hipLaunchKernelGGL(trig_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cur_s, batch, T, trig);
   return hipGetLastError();

@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/neupan_amd.h"
+#include "launch.h"
 
 namespace {
 
@@ -83,7 +83,7 @@ __global__ void label_kernel(Polygon Q, long long n, const double* __restrict__ 
 }  // namespace
 
 // G [E][2], h [E]: host arrays, consecutive counter-clockwise edges (gen_inequal_from_vertex order)
-extern "C" hipError_t npa_launch_labels(int E, const double* G, const double* h, long long n, const double* points,
+hipError_t npa_launch_labels(int E, const double* G, const double* h, long long n, const double* points,
                                         float* mu, float* dist, hipStream_t stream) {
   Polygon Q;
   Q.E = E;

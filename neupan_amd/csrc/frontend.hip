@@ -10,7 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/neupan_amd.h"
+#include "launch.h"
 
 namespace {
 
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(
 
 }  // namespace
 
-extern "C" hipError_t npa_launch_nominal(int batch, int T, int kin, double dt, double L, const double* state,
+hipError_t npa_launch_nominal(int batch, int T, int kin, double dt, double L, const double* state,
                                          const float* vel, const double* ref_speed, const double* path,
                                          const int* curve_off, const int* curve_len, const int* point_index,
                                          const double* interval, float* nom_s, float* nom_u, float* ref_s,
@@ -238,7 +238,7 @@ extern "C" hipError_t npa_launch_nominal(int batch, int T, int kin, double dt, d
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_progress(int batch, const double* state, const double* path, const int* curve_off,
+hipError_t npa_launch_progress(int batch, const double* state, const double* path, const int* curve_off,
                                           const int* curve_len, int* point_index, double close_threshold, int ind_range,
                                           double arrive_threshold, int arrive_index_threshold, float* min_dis,
                                           int* arrived, hipStream_t stream) {
@@ -249,7 +249,7 @@ extern "C" hipError_t npa_launch_progress(int batch, const double* state, const 
   return hipGetLastError();
 }
 
-extern "C" hipError_t npa_launch_scan(int batch, int beam_stride, const double* ranges, const double* beam_vel,
+hipError_t npa_launch_scan(int batch, int beam_stride, const double* ranges, const double* beam_vel,
                                       const int* n_beams, const npa_scan_params* params, int mode, int out_stride,
                                       float* points, float* velocities, int* count, hipStream_t stream) {
   hipLaunchKernelGGL(scan_kernel, dim3(batch), dim3(SCAN_THREADS), 0, stream, beam_stride, ranges, beam_vel, n_beams,

@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/neupan_amd.h"
+#include "launch.h"
 
 namespace {
 
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(INGEST_THREADS) void ingest_unpack_kernel(
 }  // namespace
 
 // out[0..n), n <= 8: byte offsets of n_points, cloud_off, nom_s, nom_u, ref_s, ref_us, the cloud section; worst-case bytes.
-extern "C" int npa_ingest_offsets(int batch, int T, int n_stride, int with_vel, size_t* out, int n) {
+int npa_ingest_offsets(int batch, int T, int n_stride, int with_vel, size_t* out, int n) {
   // (cloud_off is an int32 word offset: the cloud section must stay below 2^31 words)
   if ((size_t)batch * (size_t)n_stride * (with_vel ? 4 : 2) >= ((size_t)1 << 31)) return -1;
   const IngestLayout L = ingest_layout(batch, T, n_stride, with_vel);
@@ -99,7 +99,7 @@ extern "C" int npa_ingest_offsets(int batch, int T, int n_stride, int with_vel, 
   return 0;
 }
 
-extern "C" hipError_t npa_launch_ingest_unpack(int batch, int T, int n_stride, int with_vel, const void* record,
+hipError_t npa_launch_ingest_unpack(int batch, int T, int n_stride, int with_vel, const void* record,
                                                size_t record_bytes, float* nom_s, float* nom_u, float* ref_s, float* ref_us,
                                                float* points, float* velocities, int* n_points, int* status,
                                                hipStream_t stream) {

@@ -29,7 +29,7 @@
 // leading dimensions (conflict-free row-per-lane access), cross-lane broadcast is v_readlane,
 // wave reductions are DPP (quad_perm / row_mirror) + 4 readlanes, and every division in a
 // serial loop is replaced by a reciprocal computed once per iteration.
-#include "pan_common.h"
+#include "launch.h"
 #include <hip/hip_ext.h>
 #include <cstdlib>
 #include <type_traits>
@@ -57,20 +57,16 @@ extern "C" size_t npa_qp_shmem_bytes_path(int T, int M, int fast) {
   return (bytes + 15) & ~(size_t)15;
 }
 
-extern "C" size_t npa_qp_shmem_bytes(int T, int M) { return npa_qp_shmem_bytes_path(T, M, 0); }
+size_t npa_qp_shmem_bytes(int T, int M) { return npa_qp_shmem_bytes_path(T, M, 0); }
 
-extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, const float* cur_s_in,
-                                    const float* cur_u_in, const float* ref_s, const float* ref_us,
-                                    const float* mu_sorted, const float* lam_sorted, const float* pts_sorted,
-                                    const float* dist_sorted, const int* count, float* cur_s_out, float* cur_u_out,
-                                    float* cur_d_out, float* out_s, float* out_u, float* out_d,
-                                    float* out_min_distance, int* out_iters, float* out_nrmp_points, int* flags,
-                                    float* state, double* qp_info, double* warm, float* trig_out, float* dbg_abc,
-                                    float* dbg_f, double* dbg_x,
-                                    hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, const float* theta,
-                                    QpSched sched) {
-  // (the dispatch-order block describes a launch over the whole batch of a forward call: a partial launch gets none)
-  if (scene0 != 0) sched = QpSched{nullptr, nullptr, nullptr, nullptr, nullptr};
+// the kernel's argument list from a launcher's (c, batch, extra); every launch covers the scenes 0 .. batch - 1 of its call
+#define QP_KERNEL_ARGS                                                                                                          \
+  P, c.cur_s_in, c.cur_u_in, c.ref_s, c.ref_us, c.mu_sorted, c.lam_sorted, c.pts_sorted, c.dist_sorted, c.count, c.cur_s_out,   \
+      c.cur_u_out, c.cur_d_out, c.out_s, c.out_u, c.out_d, c.out_min_distance, c.out_iters, c.out_nrmp_points, c.flags, c.state, \
+      c.qp_info, c.warm, 0, batch, extra, c.trig_out, c.theta, c.sched
+
+hipError_t npa_launch_qp(const DevParams& P, const QpCall& c, int batch, const QpBackward& extra, hipStream_t stream,
+                         hipEvent_t ev_start, hipEvent_t ev_stop) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;     // tests: the generic (LDS) instantiation for every (T, M)
   const bool fast = qp_fast_path(P.T, P.M) && !force_generic;
   const size_t shmem = npa_qp_shmem_bytes_path(P.T, P.M, fast ? 1 : 0);      // one scene (wave) per workgroup, see the kernel
@@ -85,11 +81,7 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
   }
 #define QP_LAUNCH(...)                                                                                           \
   hipExtLaunchKernelGGL((nrmp_qp_kernel<__VA_ARGS__>), dim3(nblocks), dim3(QP_THREADS), shmem, stream, ev_start, ev_stop, 0, \
-                        P, cur_s_in, cur_u_in, ref_s, ref_us, mu_sorted, lam_sorted, pts_sorted, dist_sorted, count,  \
-                        cur_s_out, cur_u_out, cur_d_out, out_s, out_u, out_d, out_min_distance, out_iters,            \
-                        out_nrmp_points, flags, state, qp_info, warm, scene0, batch,                                 \
-                        QpBackward{nullptr, nullptr, nullptr, nullptr, nullptr, dbg_abc, dbg_f, dbg_x}, trig_out, theta,   \
-                        sched)
+                        QP_KERNEL_ARGS)
   if (fast && P.T == 10) QP_LAUNCH(10, 10);
   else if (fast && P.T == 20) QP_LAUNCH(20, 10, false, true);
   else QP_LAUNCH(0, 0);
@@ -99,11 +91,11 @@ extern "C" hipError_t npa_launch_qp(const DevParams& P, int batch, int scene0, c
 
 // nrmp_qp_kernel for a group of n forward calls that share the configuration, the batch size and the stream: ONE launch,
 // grid (batch, n).  The register-resident instantiations only (c_api.hip keeps everything else call by call).
-extern "C" int npa_qp_group_supported(int T, int M) {
+int npa_qp_group_supported(int T, int M) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;
   return !force_generic && M == 10 && (T == 10 || T == 20) ? 1 : 0;
 }
-extern "C" hipError_t npa_launch_qp_group(const DevParams& P, const QpGroup& G, int n, int batch, hipStream_t stream,
+hipError_t npa_launch_qp_group(const DevParams& P, const QpGroup& G, int n, int batch, hipStream_t stream,
                                           hipEvent_t ev_start, hipEvent_t ev_stop) {
   if (n < 1 || n > NPA_GROUP_MAX || !npa_qp_group_supported(P.T, P.M)) return hipErrorInvalidValue;
   const size_t shmem = npa_qp_shmem_bytes_path(P.T, P.M, 1);
@@ -122,12 +114,7 @@ extern "C" hipError_t npa_launch_qp_group(const DevParams& P, const QpGroup& G, 
 }
 
 // forward solve + gradient w.r.t. the adjust parameters (generic kernel, one scene per workgroup)
-extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, const float* nom_s, const float* nom_u,
-                                             const float* ref_s, const float* ref_us, const float* mu_sorted,
-                                             const float* lam_sorted, const float* pts_sorted, const int* count,
-                                             float* out_s, float* out_u, float* out_d, const float* grad_s,
-                                             const float* grad_u, const float* grad_d, float* grad_theta,
-                                             float* grad_nom_s, double* qp_info, hipStream_t stream, const float* theta) {
+hipError_t npa_launch_qp_backward(const DevParams& P, const QpCall& c, int batch, const QpBackward& extra, hipStream_t stream) {
   static const bool force_generic = getenv("NPA_QP_GENERIC") != nullptr;
   const bool fast = qp_fast_path(P.T, P.M) && !force_generic;
   const size_t wave_bytes = npa_qp_shmem_bytes_path(P.T, P.M, fast ? 1 : 0);
@@ -141,16 +128,12 @@ extern "C" hipError_t npa_launch_qp_backward(const DevParams& P, int batch, cons
   }
   // (the register-resident instantiations since round 3: the gradient pass reads the multiplier directions of the d rows
   // from their owner lanes; NPA_QP_GENERIC=1 keeps the LDS kernel)
-#define QPB_LAUNCH(...)                                                                                                \
-  hipLaunchKernelGGL((nrmp_qp_kernel<__VA_ARGS__>), dim3(batch), dim3(QP_THREADS), wave_bytes, stream, P, nom_s, nom_u, ref_s, \
-                     ref_us, mu_sorted, lam_sorted, pts_sorted, (const float*)nullptr, count, out_s, out_u, out_d,        \
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr,  \
-                     (int*)nullptr, (float*)nullptr, qp_info, (double*)nullptr, 0, batch,                                 \
-                     QpBackward{grad_s, grad_u, grad_d, grad_theta, grad_nom_s, nullptr, nullptr, nullptr}, (float*)nullptr, theta, \
-                     QpSched{nullptr, nullptr, nullptr, nullptr, nullptr})
+#define QPB_LAUNCH(...) \
+  hipLaunchKernelGGL((nrmp_qp_kernel<__VA_ARGS__>), dim3(batch), dim3(QP_THREADS), wave_bytes, stream, QP_KERNEL_ARGS)
   if (fast && P.T == 10) QPB_LAUNCH(10, 10, true);
   else if (fast && P.T == 20) QPB_LAUNCH(20, 10, true, true);
   else QPB_LAUNCH(0, 0, true);
 #undef QPB_LAUNCH
+#undef QP_KERNEL_ARGS
   return hipGetLastError();
 }

@@ -363,20 +363,7 @@ __device__ __forceinline__ void qp_sched_file(int* cnt, int* list, int* ticket, 
 // BWD: after convergence, one more solve with the Newton matrix of the final iterate and the upstream
 // gradient as right-hand side gives dL/d(q_s, p_u, eta, d_max, d_min) (oracle/nrmp_backward.py states
 // the derivation; reference: the adjust parameters are differentiable through cvxpylayers,
-// nrmp.py:79-95, :144).  Instantiated for the generic path only, so the forward kernels are untouched.
-struct QpBackward {
-  const float* grad_s;      // [B][3][T+1]  dL/d opt_s
-  const float* grad_u;      // [B][2][T]    dL/d opt_u
-  const float* grad_d;      // [B][T]       dL/d opt_d (may be null)
-  float* grad_theta;        // [B][8]       q_s[0..2], p_u, eta, d_max, d_min, (status)
-  float* grad_nom_s;        // [B][3][T+1]  dL/d(proximal centre) = bk Phi v, column 0 = 0 (may be null)
-  // parameter export (npa_nrmp_params): when set, the kernel writes the linearisation and the hinge coefficients it
-  // built -- [B][T][11] A02 A12 B00 B01 B10 B11 B20 B21 C0 C1 C2, then [B][T][M][3] fa0 fa1 fb, fp32 as the
-  // reference holds them -- and returns before the solve
-  float* dbg_abc;
-  float* dbg_f;
-  double* dbg_x;            // [B][2T + T]: the fp64 solution (u_0x, u_0y, ..., then d) before the cast to fp32, or null
-};
+// nrmp.py:79-95, :144).  Instantiated for the generic path only, so the forward kernels are untouched.  (QpBackward: pan_common.h)
 
 // Pair p of the u / d rows: rows 2p and 2p + 1 are  +c'x <= bp  and  -c'x <= bm  with c'x = x[ia] - sb x[ib] over the
 // vector x = (u, d) (xu / xd and dxu / dxd are contiguous in LDS).  p < 2T: speed of u_p; p < 4T - 2: rate
@@ -429,7 +416,7 @@ void nrmp_qp_kernel(
   // every iteration of the solve.
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= nscene) return;
-  // (dispatch order, forward solves only: the launcher passes the block with scene0 == 0 alone)
+  // (dispatch order, forward solves only; scene0 is 0 in every launch: each covers the whole batch of its call)
   int b_ = blockIdx.x;
   if constexpr (!BWD) b_ = qp_sched_pick(sched.in_cnt, sched.in_list, blockIdx.x, nscene, lane);
   const int b = b_ + scene0;

@@ -1,6 +1,6 @@
-// pack_image.hip -- polygon geometry and the host image of the weight pack (pack_image.h).  No kernel, no HIP runtime call: the
+// pack_image.hip -- polygon geometry and the host image of the weight pack (declared in launch.h).  No kernel, no HIP runtime call: the
 // suffix only keeps the build uniform.
-#include "pack_image.h"
+#include "launch.h"
 
 #include <algorithm>
 #include <cmath>

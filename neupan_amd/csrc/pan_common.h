@@ -76,6 +76,21 @@ struct QpCall {
   QpSched sched;              // this call's dispatch-order block for this launch
 };
 struct QpGroup { QpCall c[NPA_GROUP_MAX]; };
+// What a single-call QP launch takes besides its QpCall (launch.h: npa_launch_qp, npa_launch_qp_backward); null throughout in the
+// forward path.  The gradient pass (BWD instantiations, nrmp_qp_device.h) reads and writes the first five.
+struct QpBackward {
+  const float* grad_s;      // [B][3][T+1]  dL/d opt_s
+  const float* grad_u;      // [B][2][T]    dL/d opt_u
+  const float* grad_d;      // [B][T]       dL/d opt_d (may be null)
+  float* grad_theta;        // [B][8]       q_s[0..2], p_u, eta, d_max, d_min, (status)
+  float* grad_nom_s;        // [B][3][T+1]  dL/d(proximal centre) = bk Phi v, column 0 = 0 (may be null)
+  // parameter export (npa_nrmp_params): when set, the kernel writes the linearisation and the hinge coefficients it
+  // built -- [B][T][11] A02 A12 B00 B01 B10 B11 B20 B21 C0 C1 C2, then [B][T][M][3] fa0 fa1 fb, fp32 as the
+  // reference holds them -- and returns before the solve
+  float* dbg_abc;
+  float* dbg_f;
+  double* dbg_x;            // [B][2T + T]: the fp64 solution (u_0x, u_0y, ..., then d) before the cast to fp32, or null
+};
 struct StageCall {
   float* cur_s; const float* nom_s; float* cur_u; const float* nom_u; int* flags; int* count; int* state; float* trig;
   int* sched_cnt;             // the class counters of the call's QP launches (every row is cleared)

@@ -11,11 +11,7 @@
 // nrmp_qp_group_kernel): the same kernels' statements, the same results bitwise, 1 + 2K launches for the whole group.  A launch
 // is a barrier over its scenes; with G x 256 scenes behind it the wave slots its stragglers leave idle are refilled from the
 // same launch, and the group needs one hardware queue instead of G.  Calls on different streams keep the breadth-first order.
-#include "../../include/neupan_amd.h"
-
-extern "C" int npa_group_mergeable(int n, const npa_forward_call* calls);
-extern "C" int npa_group_begin_merged(int n, const npa_forward_call* calls, int flags, int* begun);
-extern "C" int npa_group_iter_merged(int n, const npa_forward_call* calls, int k);
+#include "launch.h"
 
 extern "C" int npa_forward_batch_group(int n, const npa_forward_call* calls, int flags) {
   if (n < 1 || !calls) return NPA_E_ARG;
@@ -75,10 +71,7 @@ extern "C" int npa_forward_batch_group(int n, const npa_forward_call* calls, int
   }
   int begun = 0, rc = NPA_OK;
   for (; begun < n && rc == NPA_OK; ++begun) {
-    const npa_forward_call& a = calls[begun];
-    rc = npa_forward_begin(a.h, a.batch, a.n_stride, a.nom_s, a.nom_u, a.ref_s, a.ref_us, a.points, a.velocities, a.n_points,
-                           a.out_s, a.out_u, a.out_d, a.out_min_distance, a.out_iters, a.out_nrmp_points, a.workspace,
-                           a.workspace_bytes, a.state, a.state_bytes, a.stream, flags);
+    rc = npa_forward_begin_call(calls[begun], flags, true);
     if (rc != NPA_OK) break;                                          // (calls[begun] itself did not begin)
   }
   for (int k = 0; k < kmax && rc == NPA_OK; ++k)

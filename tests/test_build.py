@@ -1,5 +1,6 @@
 """No GPU: the build contract of every row of neupan_amd.build.LIBRARIES -- what each library declares, binds and exports, what
-it is built from and how, when it is rebuilt, and that a row lists every file its sources include."""
+it is built from and how, when it is rebuilt, that a row lists every file its sources include, and that the units of a row reach
+each other through csrc/launch.h alone."""
 import itertools
 import os
 import re
@@ -15,13 +16,50 @@ BINDINGS = {"main": _lib, "train": _lib_train, "grid": _lib_grid}
 # the exports of the two small libraries by name; the main header's are too many to repeat here
 NAMES = {"train": {"npa_dune_train_last_error", "npa_dune_train_param_count", "npa_dune_train_steps"},
          "grid": {"npa_grid_scan", "npa_grid_clearance", "npa_grid_last_error"}}
+# what the main library exports besides its header's names: the diagnostics that tests/ and tests/tools/ read through ctypes,
+# declared under default visibility at the end of csrc/launch.h
+HELPERS = {"npa_qp_shmem_bytes_path", "npa_group_begin_merged", "npa_group_iter_merged", "npa_dbg_group_merged_launches",
+           "npa_dbg_pack_image", "npa_dbg_sel_prof"}
+SEL_PROF_ONLY = {"npa_dbg_sel_prof"}            # defined in the -DNPA_SEL_PROF variant alone (tests/tools/select_phase_cycles.py)
+
+
+def code(path):
+    """the file without its comments"""
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S))
 
 
 def declared(name):
-    """the npa_* functions the row's own header declares (comments taken out first)"""
-    txt = open(os.path.join(ROOT, "include", b.LIBRARIES[name].headers[0])).read()
-    txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
-    return set(re.findall(r"\b(npa_\w+)\s*\(", txt))
+    """the npa_* functions the row's own header declares"""
+    return set(re.findall(r"\b(npa_\w+)\s*\(", code(os.path.join(ROOT, "include", b.LIBRARIES[name].headers[0]))))
+
+
+def file_scope(path):
+    """the file's text outside every function and class body (a body becomes `{}`): no comments, no preprocessor lines, string
+    and character literals emptied; the braces of `namespace ... {` and `extern "C" {` are not bodies"""
+    txt = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", "", code(path), flags=re.M)
+    txt = txt.replace('extern "C"', "extern C")
+    txt = re.sub(r"'(?:\\.|[^'\\\n])'", "' '", re.sub(r'"(?:\\.|[^"\\\n])*"', '""', txt))
+    out, stack, start = [], [], 0                     # stack: True for a body; start: where the current statement began
+    for i, ch in enumerate(txt):
+        inside = any(stack)
+        if ch == "{":
+            head = txt[start:i]
+            stack.append(not re.search(r"(?:\bnamespace\b[\w\s:]*|\bextern C\s*)$", head))
+            if not inside:
+                out.append("{" if stack[-1] else " ")
+            start = i + 1
+        elif ch == "}":
+            body = stack.pop()
+            if not any(stack):
+                out.append("}" if body else " ")
+            start = i + 1
+        else:
+            if ch == ";":
+                start = i + 1
+            if not inside:
+                out.append(ch)
+    assert not stack, path
+    return "".join(out).replace("extern C", 'extern "C"')
 
 
 def test_the_table_is_what_it_was():
@@ -41,17 +79,86 @@ def test_the_table_is_what_it_was():
 
 @pytest.mark.parametrize("name", ROWS)
 def test_symbols_declared_bound_and_exported(name):
-    """header == SYMBOLS == what the loaded library gives a prototype; the dynamic exports are these names -- for the main
-    library these and the npa_* helpers its translation units call each other through, which no header declares"""
+    """header == SYMBOLS == what the loaded library gives a prototype; the dynamic exports are these names and nothing else --
+    for the main library these and HELPERS, by name"""
     names, mod, row = declared(name), BINDINGS[name], b.LIBRARIES[name]
     b.build_library(name, force=False, verbose=False)
     assert names == set(mod.SYMBOLS) == NAMES.get(name, names) and len(names) >= (12 if name == "main" else 3)
     out = subprocess.run(["nm", "-D", "--defined-only", row.lib], stdout=subprocess.PIPE, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("npa_")}
-    assert exported >= names if name == "main" else exported == names, exported ^ names
+    want = names | (HELPERS - SEL_PROF_ONLY) if name == "main" else names
+    assert exported == want, exported ^ want
     lib = mod.load()
     for n in names:
         assert getattr(lib, n).argtypes is not None, n
+
+
+def test_the_helpers_are_the_default_visibility_block_of_launch_h():
+    txt = code(os.path.join(b.CSRC, "launch.h"))
+    inner, block = txt.split("#pragma GCC visibility push(default)")
+    block, rest = block.split("#pragma GCC visibility pop")
+    assert set(re.findall(r"\b(npa_\w+)\s*\(", block)) == HELPERS and 'extern "C"' in block
+    assert 'extern "C"' not in inner and "npa_" not in rest
+    assert "-fvisibility=hidden" in b.FLAGS
+    for row in b.LIBRARIES.values():                 # the exports: between push(default) and pop of the row's own header
+        hdr = code(os.path.join(ROOT, "include", row.headers[0]))
+        assert hdr.count("#pragma GCC visibility push(default)") == 1 and hdr.count("#pragma GCC visibility pop") == 1
+        before, after = hdr.split("#pragma GCC visibility push(default)")[0], hdr.split("#pragma GCC visibility pop")[1]
+        assert not re.search(r"\bnpa_\w+\s*\(", before + after), row.headers[0]
+
+
+def prototypes(scope_text):
+    """the npa_* functions declared without a body in a file_scope() text (a `static` forward declaration is not one: the unit
+    that holds it also holds the definition, and the compiler compares the two)"""
+    return [m.group(2) for m in re.finditer(r"([^;{}]*?)\b(npa_\w+)\s*\([^;{}]*\)\s*;", scope_text) if "static" not in m.group(1).split()]
+
+
+def test_no_unit_writes_a_prototype():
+    """a function another unit defines is declared in a header: no .hip file of any row holds a prototype without a body"""
+    for row in b.LIBRARIES.values():
+        for src in row.sources:
+            path = os.path.join(b.CSRC, src)
+            assert not re.findall(r'^\s*extern "C"[^;{]*\)\s*;', code(path), flags=re.M), src
+            assert not prototypes(file_scope(path)), src
+
+
+def test_file_scope_sees_prototypes_and_only_them():
+    """(the helper of the test above, on a text that has every case)"""
+    import tempfile
+    text = ('#define M(x) do { x; } while (0)\nnamespace {\nint npa_a(int);  // one\nstatic int f() { return npa_b(1); }\n}\n'
+            'extern "C" {\nint npa_c(void);\n}\nextern "C" int npa_d(int x) { if (x) { npa_e(x); } return 0; }\n'
+            'struct S { int npa_f(int); };\nconst char* s = "npa_g(1);";\nhipError_t npa_h(const float* a,\n    int b);\n'
+            'static int npa_i(int);\n')
+    with tempfile.NamedTemporaryFile("w", suffix=".hip") as f:
+        f.write(text)
+        f.flush()
+        assert prototypes(file_scope(f.name)) == ["npa_a", "npa_c", "npa_h"]
+
+
+def test_every_cross_unit_function_is_declared_once_in_launch_h():
+    """every non-static npa_* function that one unit of the main library defines and another names is declared in csrc/launch.h
+    or in the public header -- and launch.h declares nothing twice and nothing that no unit defines"""
+    row = b.LIBRARIES["main"]
+    assert "launch.h" in row.includes
+    scope = {src: file_scope(os.path.join(b.CSRC, src)) for src in row.sources}
+    text = {src: code(os.path.join(b.CSRC, src)) for src in row.sources}
+    defined = {}
+    for src, txt in scope.items():
+        for m in re.finditer(r"([^;{}]*?)\b(npa_\w+)\s*\([^;{}]*\)\s*\{\}", txt):
+            if not set(m.group(1).split()) & {"static", "__global__", "__device__"}:
+                defined.setdefault(m.group(2), set()).add(src)
+    assert len(defined) > 60 and all(len(v) == 1 for v in defined.values()), {k: v for k, v in defined.items() if len(v) > 1}
+    in_launch = re.findall(r"\b(npa_\w+)\s*\(", code(os.path.join(b.CSRC, "launch.h")))
+    assert len(in_launch) == len(set(in_launch)), sorted(n for n in set(in_launch) if in_launch.count(n) > 1)
+    assert set(in_launch) - SEL_PROF_ONLY <= set(defined), set(in_launch) - set(defined)
+    known = set(in_launch) | declared("main")
+    crossing = {n for n, (src,) in ((n, tuple(v)) for n, v in defined.items())
+                if any(re.search(r"\b%s\b" % n, t) for other, t in text.items() if other != src)}
+    assert len(crossing) >= 30 and crossing <= known, sorted(crossing - known)
+    # every unit that defines or names one of launch.h's functions includes the header itself
+    for src, t in text.items():
+        if any(re.search(r"\b%s\b" % n, t) for n in in_launch):
+            assert re.search(r'^[ \t]*#[ \t]*include[ \t]*"launch.h"', t, flags=re.M), src
 
 
 def test_symbol_tables_are_pairwise_disjoint():
@@ -127,7 +234,8 @@ def test_a_row_lists_every_file_its_sources_include(name):
                                             ("csrc/handle.h", {"main"}), ("csrc/dune_train.hip", {"train"}),
                                             ("csrc/aset_reduce.h", set()), ("_obj/dune.o", set()),
                                             ("../include/neupan_amd_grid.h", {"grid"}),
-                                            ("../include/neupan_amd.h", {"main", "train", "grid"})])
+                                            ("../include/neupan_amd.h", {"main", "train", "grid"}),
+                                            ("csrc/launch.h", {"main"})])
 def test_needs_build_follows_the_row_and_nothing_else(touched, stale, monkeypatch):
     """a library is stale when a file of ITS row is newer -- not whatever lies in csrc/ -- or when it is missing (times and
     existence are faked: the tree is not touched)"""

@@ -1,7 +1,7 @@
 // Stand-alone host program around csrc/pack_image.hip (polygon geometry, the weight pack's host image): a box, the 8-edge hull
 // and a polygon that is none, with weights from a fixed generator.  Meant to be built with a host sanitizer (README.md here);
 // exits 0 when every case gives the expected geo_valid / geo_rect and an image without NaN.
-#include "../../../neupan_amd/csrc/pack_image.h"
+#include "../../../neupan_amd/csrc/launch.h"
 
 #include <cmath>
 #include <cstdio>
