@@ -739,6 +739,59 @@ int npa_curve_batch(int batch, int style, const double *start, const double *goa
 int npa_route_relax(const uint8_t *blocked, int nx, int ny, int n_fields, uint32_t *fields, int sweeps,
                     uint32_t sweep_base, uint32_t *changed, void *stream);
 
+/* ---- routed curves: a path down a goal field, as `line` curves between its turns (csrc/cycle.hip, csrc/curves.hip) -------
+ *
+ * The way a robot takes through the map to a goal whose field has converged: route.trace's chain, route.waypoints' positions
+ * and planner.generate_curve("line", ...)'s rows (neupan_amd/route.py, neupan_amd/planner.py), in ONE kernel with one wave per
+ * robot, route_wave_kernel, without the host: no workspace, no atomics, no LDS, nothing allocated, no cap on the turns.  This
+ * comment is the specification (tests/route_wave_ref.py restates it in plain Python).
+ *
+ * Inputs per robot: a start pose (x, y, theta), a goal (x, y, theta), the index f of the goal's field in fields
+ *   [n_fields][ny][nx] uint32 (DEVICE; converged, seeded with 0 in the goal's cell only: GoalFields.fields), the map's frame
+ *   x0, y0, resolution (cell (i, j) covers [x0 + i res, x0 + (i + 1) res) x [y0 + j res, y0 + (j + 1) res)), an interval.
+ * Start cell: i = floor((x - x0) / res), j = floor((y - y0) / res), each one rounded fp64 operation per step (no contraction).
+ * Chain: from a cell of value v > 0 the walk goes to the first neighbour in the order E, W, N, S, NE, NW, SE, SW that lies
+ *   inside the array, is not NPA_ROUTE_BLOCKED, for a diagonal has both axis cells beside it inside and not BLOCKED, and holds
+ *   exactly v - 5 (axis) or v - 7 (diagonal); it ends at value 0.  Lanes 0 .. 7 load one neighbour each, one ballot is the free
+ *   mask, a second the allowed moves, its lowest bit the move.  Every step lowers v: the walk ends on any input.
+ * Way-points: the start's (x, y); the centre (x0 + (i + 0.5) res, y0 + (j + 0.5) res) of every cell whose move out differs
+ *   from the move in; the goal's own (x, y).
+ * Rows: between consecutive way-points a segment whose two ends are equal in both coordinates is skipped; any other is the
+ *   NPA_CURVE_LINE curve of the block above at `interval` without its goal row (rows 0 .. n - 1; lane l writes rows l, l + 64,
+ *   ...).  The last row is (goal x, goal y, h, 1): h = the psi of the last segment that was not skipped, the goal's theta if all
+ *   were.  rows = the sum of the segments' n, plus 1.
+ * Nothing is written unless the whole path fits: the walk runs twice, counting and then writing.
+ * No route: f outside [0, n_fields); a start cell outside the array (a pose that is not finite is outside); a start value of
+ *   NPA_ROUTE_BLOCKED or NPA_ROUTE_UNREACHED; a step with no allowed move (the field is not converged).
+ * No curve: a segment outside the curve specification (interval not > 0, a goal that is not finite, 2^30 steps or more), or a
+ *   path of 2^31 rows or more.
+ *
+ * npa_route_curve_batch (one launch): B routed paths.  field_of [B] int32, start, goal [B][3] f64, interval [B] f64, mask [B]
+ *   int32 (nullable), rows_out [B][capacity][4] f64, n_rows [B] int32, all DEVICE.  n_rows[b] = rows when 1 <= rows <= capacity
+ *   (the rows are written); -rows when rows > capacity (nothing is written); 0 when there is no route; -2^31 when there is no
+ *   curve (the count no capacity holds: a caller that maps n_rows < 0 to "does not fit" gives npa_cycle_retask_routed's status).
+ *   mask[b] == 0: rows and n_rows[b] untouched, as npa_curve_batch.
+ * npa_cycle_retask_routed (one launch, runs where npa_cycle_retask runs; the cycle block below describes that call and its
+ *   arguments): the same gate (arrived, not collided, 0 <= goal_index < n_goals), and the path from state[b] to
+ *   goals[b][goal_index[b]] down field field_of[b][goal_index[b]] (field_of [B][g_stride] int32) in place of the curve.  It fits:
+ *   the same writes and retask_status[b] = 1.  It does not fit row_capacity[b], or no curve: retask_status[b] = 2.  No route:
+ *   retask_status[b] = 3.  For 2 and 3 nothing else of the robot is written: it stays arrived and the goal is not consumed.
+ *   log_goal as npa_cycle_retask.
+ * NPA_E_ARG (before anything touches a device): a null required pointer; batch, capacity or g_stride < 1; nx or ny < 1;
+ *   n_fields outside 1 .. 65535; a resolution that is not finite and > 0, an x0 or y0 that is not finite; receding outside
+ *   [1, NPA_MAX_T]; cycle < 0.  NPA_E_UNSUPPORTED: nx ny > NPA_ROUTE_MAX_CELLS. */
+int npa_route_curve_batch(int batch, const uint32_t *fields, int n_fields, int nx, int ny, double x0, double y0,
+                          double resolution, const int32_t *field_of, const double *start, const double *goal,
+                          const double *interval, int capacity, const int32_t *mask, double *rows_out, int32_t *n_rows,
+                          void *stream);
+int npa_cycle_retask_routed(int batch, int receding, int cycle, const double *state, int32_t *arrived,
+                            const int32_t *collided, double *path, const int32_t *curve_off, int32_t *curve_len,
+                            const int32_t *robot_first, const int32_t *row_capacity, const double *goals, int g_stride,
+                            const int32_t *n_goals, int32_t *goal_index, const double *interval, int32_t *curve_index,
+                            int32_t *cur_off, int32_t *cur_len, int32_t *point_index, float *cur_vel,
+                            int32_t *retask_status, int32_t *log_goal, const uint32_t *fields, int n_fields, int nx,
+                            int ny, double x0, double y0, double resolution, const int32_t *field_of, void *stream);
+
 /* ---- the bookkeeping of a device-resident closed loop (csrc/cycle.hip) -----------------------------------------------
  *
  * What the host does between the kernels of a control cycle, as three calls (and a fourth for fleets whose robots have goal

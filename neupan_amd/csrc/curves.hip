@@ -4,6 +4,8 @@
 //                                        the kernel npa_cycle_retask runs -- one copy of the curve's device code in the library
 //   npa_route_relax                      the goal fields of a map (the header's "goal fields" block): the checks and the launches
 //                                        of route_sweep_kernel (cycle.hip)
+//   npa_route_curve_batch,               routed curves (the header's block of that name): the checks and the launch of
+//   npa_cycle_retask_routed              route_wave_kernel (cycle.hip), B plain paths or the re-task of a cycle
 // The curve itself is curves.h, compiled for both sides.
 #include "curves.h"
 
@@ -88,4 +90,52 @@ extern "C" int npa_route_relax(const uint8_t* blocked, int nx, int ny, int n_fie
   if (what) return fail(code, what);
   HIP_TRY(npa_launch_route_relax(blocked, nx, ny, n_fields, fields, sweeps, sweep_base, changed, (hipStream_t)stream));
   return NPA_OK;
+}
+
+// The routed curves of include/neupan_amd.h: both exports check and launch route_wave_kernel (cycle.hip).  `sound`: the
+// caller's own test (its pointers, batch, capacity / g_stride, receding, cycle); the fields and the frame are tested here.
+namespace {
+__attribute__((noinline, minsize)) int route_wave_call(const char* who, bool sound, int batch, const RouteFrame& m, const int* field_of,
+                                                       const double* start, const double* goals, const double* interval, int capacity,
+                                                       const int* mask, double* rows, int* n_rows, const RetaskTable* t, void* stream) {
+  const char* what = nullptr;
+  int code = NPA_E_ARG;
+  if (!sound || !m.fields || !field_of) what = ": bad argument";
+  else if (m.nx < 1 || m.ny < 1) what = ": nx, ny must be >= 1";
+  else if (m.n_fields < 1 || m.n_fields > 65535) what = ": n_fields outside 1..65535";
+  else if (!(m.resolution > 0.0) || !std::isfinite(m.resolution) || !std::isfinite(m.x0) || !std::isfinite(m.y0))
+    what = ": the resolution must be finite and > 0, x0 and y0 finite";
+  else if ((int64_t)m.nx * m.ny > NPA_ROUTE_MAX_CELLS) {
+    what = ": more than NPA_ROUTE_MAX_CELLS cells";
+    code = NPA_E_UNSUPPORTED;
+  }
+  if (what) return fail(code, std::string(who) + what);
+  HIP_TRY(npa_launch_route_wave(batch, m, field_of, start, goals, interval, capacity, mask, rows, n_rows, t, (hipStream_t)stream));
+  return NPA_OK;
+}
+}  // namespace
+
+extern "C" int npa_route_curve_batch(int batch, const uint32_t* fields, int n_fields, int nx, int ny, double x0, double y0,
+                                     double resolution, const int32_t* field_of, const double* start, const double* goal,
+                                     const double* interval, int capacity, const int32_t* mask, double* rows_out, int32_t* n_rows,
+                                     void* stream) {
+  const bool sound = batch >= 1 && capacity >= 1 && start && goal && interval && rows_out && n_rows;
+  return route_wave_call("npa_route_curve_batch", sound, batch, {fields, n_fields, nx, ny, x0, y0, resolution}, field_of, start, goal,
+                         interval, capacity, mask, rows_out, n_rows, nullptr, stream);
+}
+
+extern "C" int npa_cycle_retask_routed(int batch, int receding, int cycle, const double* state, int32_t* arrived,
+                                       const int32_t* collided, double* path, const int32_t* curve_off, int32_t* curve_len,
+                                       const int32_t* robot_first, const int32_t* row_capacity, const double* goals, int g_stride,
+                                       const int32_t* n_goals, int32_t* goal_index, const double* interval, int32_t* curve_index,
+                                       int32_t* cur_off, int32_t* cur_len, int32_t* point_index, float* cur_vel,
+                                       int32_t* retask_status, int32_t* log_goal, const uint32_t* fields, int n_fields, int nx,
+                                       int ny, double x0, double y0, double resolution, const int32_t* field_of, void* stream) {
+  const bool sound = batch >= 1 && cycle >= 0 && g_stride >= 1 && receding >= 1 && receding <= NPA_MAX_T && state && arrived &&
+                     collided && path && curve_off && curve_len && robot_first && row_capacity && goals && n_goals && goal_index &&
+                     interval && curve_index && cur_off && cur_len && point_index && cur_vel && retask_status;
+  const RetaskTable t = {receding, cycle, g_stride, arrived, collided, curve_off, robot_first, row_capacity, n_goals, curve_len,
+                         goal_index, curve_index, cur_off, cur_len, point_index, cur_vel, log_goal};
+  return route_wave_call("npa_cycle_retask_routed", sound, batch, {fields, n_fields, nx, ny, x0, y0, resolution}, field_of, state, goals,
+                         interval, 0, nullptr, path, retask_status, &t, stream);
 }

@@ -4,9 +4,11 @@
 //   cycle_commit_kernel  the collision latch and the cycle's log rows behind the plant step
 //   curve_wave_kernel    an arrived robot's next goal: a new curve into its region of the table       neupan.py:288-294, :314-318
 //                        (and, for npa_curve_batch, plain curves: csrc/curves.hip)
+//   route_wave_kernel    curve_wave_kernel's routed sibling: the next goal's path down its goal field, `line` curves between the
+//                        turns of the chain (npa_cycle_retask_routed; for npa_route_curve_batch, plain paths: csrc/curves.hip)
 //   route_sweep_kernel   not part of the cycle: one relaxation sweep of the goal fields behind npa_route_relax (csrc/curves.hip),
 //                        here because this unit has device code and the product library a size limit
-// One thread per robot (curve_wave_kernel: one wave), no workspace, no atomics; handle-free and stream-ordered like frontend.hip.  Every per-robot decision
+// One thread per robot (curve_wave_kernel, route_wave_kernel: one wave), no workspace, no atomics; handle-free and stream-ordered like frontend.hip.  Every per-robot decision
 // is a select and every loop bound is a launch argument: the kernels only choose and copy, so a loop built from them gives
 // the bits of the host-paced loop (FleetPlanner.forward + run_closed_loop) whose rules they restate.
 #include <hip/hip_runtime.h>
@@ -179,6 +181,158 @@ __global__ __launch_bounds__(npa_curve::kWave) void curve_wave_kernel(CurveWaveA
   if (word) *word = value;
 }
 
+// The arguments of route_wave_kernel, one struct as CurveWaveArgs and in its order; what differs: no style and no radius, the
+// fields and the map's frame, field_of [B][g_stride] beside the goals.  retask == 0: npa_route_curve_batch, != 0:
+// npa_cycle_retask_routed.
+struct RouteWaveArgs {
+  int retask, batch, T, cycle, g_stride, capacity, nx, ny, n_fields;
+  const int *mask, *collided, *n_goals, *robot_first, *curve_off, *row_capacity, *field_of;
+  int *goal_index, *arrived, *log_goal;
+  const uint32_t* fields;
+  double x0, y0, res;
+  const double *start, *goals, *interval;
+  double* rows;
+  int *n_rows, *curve_len, *curve_index, *cur_off, *cur_len, *point_index;
+  float* cur_vel;
+};
+
+constexpr int RW_NO_ROUTE = 0, RW_NO_CURVE = -2147483647 - 1;    // what route_wave returns besides a row count (the second is what
+                                                                 // npa_route_curve_batch stores: more rows than any capacity)
+
+// move k of E, W, N, S, NE, NW, SE, SW (route.MOVES): its step and its cost
+__device__ __forceinline__ int move_di(int k) { return k < 4 ? (k == 0 ? 1 : (k == 1 ? -1 : 0)) : ((k & 1) ? -1 : 1); }
+__device__ __forceinline__ int move_dj(int k) { return k < 4 ? (k == 2 ? 1 : (k == 3 ? -1 : 0)) : (k < 6 ? 1 : -1); }
+__device__ __forceinline__ uint32_t move_cost(int k) { return k < 4 ? 5u : 7u; }
+
+// One wave, one routed path (include/neupan_amd.h, "routed curves"): the chain from the start's cell down field f, a `line`
+// curve between the way-points.  Everything the walk decides is the whole wave's: the cell, its value and the move are the same
+// in every lane (the move is the lowest bit of a ballot), so the loops are uniform and only the row stores are per lane.  The
+// walk runs twice, counting and then writing, in ONE loop body: nothing is kept between the passes but the row count.  Returns
+// the rows of the path (written iff <= capacity), RW_NO_ROUTE or RW_NO_CURVE (a segment outside the curve specification).
+__device__ __forceinline__ int route_wave(const RouteWaveArgs& a, int f, const double* start, const double* goal, double interval,
+                                          int capacity, double* rows, int lane) {
+#pragma clang fp contract(off)
+  const double sx = start[0], sy = start[1], gx = goal[0], gy = goal[1], gth = goal[2];
+  if (f < 0 || f >= a.n_fields) return RW_NO_ROUTE;
+  const double fi = floor((sx - a.x0) / a.res), fj = floor((sy - a.y0) / a.res);       // route.cells_of
+  if (!(fi >= 0.0 && fi < (double)a.nx && fj >= 0.0 && fj < (double)a.ny)) return RW_NO_ROUTE;      // (a NaN is outside)
+  const uint32_t* field = a.fields + (size_t)f * ((size_t)a.nx * a.ny);
+  const int i0 = (int)fi, j0 = (int)fj;
+  const uint32_t v0 = field[j0 * a.nx + i0];                                             // (nx ny <= NPA_ROUTE_MAX_CELLS: an int)
+  if (v0 >= NPA_ROUTE_UNREACHED) return RW_NO_ROUTE;
+  // lane k < 8 looks at neighbour k; the two axis moves beside it (an axis move is beside itself) are bits of the free mask
+  const int k = lane & 7, di = move_di(k), dj = move_dj(k);
+  const uint32_t cost = move_cost(k);
+  const int side_i = k < 4 ? k : (k & 1), side_j = k < 4 ? k : (k < 6 ? 2 : 3);
+  long long count = 0;
+  double h = gth;
+#pragma nounroll
+  for (int pass = 0; pass < 2; ++pass) {
+    int i = i0, j = j0, prev = -1;
+    uint32_t v = v0;
+    double wx = sx, wy = sy;                                   // the way-point behind the walk
+    count = 0;
+    h = gth;
+    for (;;) {
+      int move = -1;
+      double tx = gx, ty = gy;
+      if (v != 0) {
+        const int ni = i + di, nj = j + dj;
+        uint32_t nv = NPA_ROUTE_BLOCKED;
+        if (lane < 8 && ni >= 0 && ni < a.nx && nj >= 0 && nj < a.ny) nv = field[nj * a.nx + ni];
+        const unsigned long long open = __ballot(nv != NPA_ROUTE_BLOCKED);
+        // (v - cost is below UNREACHED, so a neighbour that holds it is free, and a lane above 7 holds BLOCKED)
+        const bool ok = ((open >> side_i) & (open >> side_j) & 1ull) != 0 && v >= cost && nv == v - cost;
+        const unsigned long long allowed = __ballot(ok);
+        if (allowed == 0) return RW_NO_ROUTE;                  // (not a converged field)
+        move = __builtin_ctzll(allowed);
+        tx = a.x0 + ((double)i + 0.5) * a.res;                 // route.centres_of
+        ty = a.y0 + ((double)j + 0.5) * a.res;
+      }
+      if (v == 0 || (prev >= 0 && move != prev)) {             // a way-point: the goal, or a cell at which the chain turns
+        if (!(wx == tx && wy == ty)) {
+          const double from[3] = {wx, wy, 0.0}, to[3] = {tx, ty, 0.0};
+          npa_curve::Curve c;
+          npa_curve::curve_plan(NPA_CURVE_LINE, from, to, interval, 0.0, c);
+          if (c.rows < 1) return RW_NO_CURVE;
+          if (pass)
+            for (int r = lane; r < c.n; r += npa_curve::kWave) {          // (the segment's goal row is the next one's first)
+              double o[4];
+              npa_curve::curve_row(c, r, o);
+              double* out = rows + (size_t)(count + r) * 4;
+              out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
+            }
+          count += c.n;
+          h = c.psi;
+        }
+        wx = tx; wy = ty;
+      }
+      if (v == 0) break;
+      i += move_di(move); j += move_dj(move);
+      v -= move_cost(move);                                    // (the chosen neighbour's value: every step lowers v)
+      prev = move;
+    }
+    if (count + 1 > 0x7FFFFFFFll) return RW_NO_CURVE;          // (the row count is an int32)
+    if (count + 1 > capacity) return (int)(count + 1);
+  }
+  if (lane == 0) {
+    double* out = rows + (size_t)count * 4;
+    out[0] = gx; out[1] = gy; out[2] = h; out[3] = 1.0;
+  }
+  return (int)(count + 1);
+}
+
+// curve_wave_kernel's routed sibling: the same gate, the same words behind the path, the same two callers' shapes
+// (npa_route_curve_batch, npa_cycle_retask_routed); retask_status 3 is "no route".
+__global__ __launch_bounds__(npa_curve::kWave) void route_wave_kernel(RouteWaveArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int gi = 0, off = 0, cap = a.capacity;
+  size_t row0 = (size_t)b * a.capacity;
+  int* word = lane == 0 ? a.n_rows + b : nullptr;
+  float* vel = nullptr;
+  if (a.retask) {
+    gi = a.goal_index[b];
+    const bool go = a.arrived[b] != 0 && a.collided[b] == 0 && gi >= 0 && gi < a.n_goals[b];
+    int* lg = a.log_goal ? a.log_goal + (size_t)a.cycle * a.batch + b : nullptr;
+    if (!go) {
+      if (lane == 0) {
+        a.n_rows[b] = 0;
+        if (lg) *lg = gi;
+      }
+      return;
+    }
+    const int first = a.robot_first[b];
+    off = a.curve_off[first];
+    cap = a.row_capacity[b];
+    row0 = (size_t)off;
+    word = lane == 1 ? lg : word;                         // WORDS: as curve_wave_kernel's
+    word = lane == 2 ? a.goal_index + b : word;
+    word = lane == 3 ? a.arrived + b : word;
+    word = lane == 4 ? a.point_index + b : word;
+    word = lane == 5 ? a.curve_index + b : word;
+    word = lane == 6 ? a.cur_off + b : word;
+    word = lane == 7 ? a.cur_len + b : word;
+    word = lane == 8 ? a.curve_len + first : word;
+    vel = lane < 2 * a.T ? a.cur_vel + (size_t)b * 2 * a.T + lane : nullptr;
+  } else if (a.mask && a.mask[b] == 0) {
+    return;
+  }
+  const size_t g = (size_t)b * a.g_stride + gi;
+  const int needed = route_wave(a, a.field_of[g], a.start + (size_t)b * 3, a.goals + g * 3, a.interval[b], cap, a.rows + row0 * 4, lane);
+  if (!word && !vel) return;
+  if (!a.retask) {
+    *word = needed > cap ? -needed : needed;              // (lane 0)
+    return;
+  }
+  if (needed < 1 || needed > cap) {                       // the robot stays arrived, the goal is not consumed
+    if (word && lane < 2) *word = lane == 0 ? (needed == RW_NO_ROUTE ? 3 : 2) : gi;
+    return;
+  }
+  if (vel) *vel = 0.f;                                    // reset(): neupan.py:288-294
+  const int value = lane == 0 ? 1 : (lane <= 2 ? gi + 1 : (lane <= 5 ? 0 : (lane == 6 ? off : needed)));
+  if (word) *word = value;
+}
+
 // One sweep of npa_route_relax (include/neupan_amd.h, "goal fields"): a workgroup owns a 16 x 16 tile of one field, relaxes it
 // in LDS against a one-cell halo and stores the cells that fell.  Blocked cells and cells outside the array are BLOCKED in LDS,
 // so the rounds test values only.  No atomics: a cell of `fields` is written by its own thread alone and only ever lower; the
@@ -269,6 +423,25 @@ hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, doubl
                            goal_index, arrived, log_goal, min_radius, state, goals, interval, path, status, curve_len, curve_index,
                            cur_off, cur_len, point_index, cur_vel};
   hipLaunchKernelGGL(curve_wave_kernel, dim3(batch), dim3(npa_curve::kWave), 0, stream, a);
+  return hipGetLastError();
+}
+
+// both routed exports: t == nullptr is npa_route_curve_batch (start, goal, capacity, mask, rows_out, n_rows), else the re-task
+hipError_t npa_launch_route_wave(int batch, const RouteFrame& m, const int* field_of, const double* start, const double* goals,
+                                 const double* interval, int capacity, const int* mask, double* rows, int* n_rows,
+                                 const RetaskTable* t, hipStream_t stream) {
+  RouteWaveArgs a = {};
+  a.batch = batch; a.T = 1; a.g_stride = 1; a.capacity = capacity; a.nx = m.nx; a.ny = m.ny; a.n_fields = m.n_fields;
+  a.mask = mask; a.field_of = field_of; a.fields = m.fields; a.x0 = m.x0; a.y0 = m.y0; a.res = m.resolution;
+  a.start = start; a.goals = goals; a.interval = interval; a.rows = rows; a.n_rows = n_rows;
+  if (t) {
+    a.retask = 1; a.T = t->T; a.cycle = t->cycle; a.g_stride = t->g_stride; a.capacity = 0;
+    a.collided = t->collided; a.n_goals = t->n_goals; a.robot_first = t->robot_first; a.curve_off = t->curve_off;
+    a.row_capacity = t->row_capacity; a.goal_index = t->goal_index; a.arrived = t->arrived; a.log_goal = t->log_goal;
+    a.curve_len = t->curve_len; a.curve_index = t->curve_index; a.cur_off = t->cur_off; a.cur_len = t->cur_len;
+    a.point_index = t->point_index; a.cur_vel = t->cur_vel;
+  }
+  hipLaunchKernelGGL(route_wave_kernel, dim3(batch), dim3(npa_curve::kWave), 0, stream, a);
   return hipGetLastError();
 }
 

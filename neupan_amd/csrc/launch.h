@@ -75,6 +75,26 @@ hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, doubl
                                    const int* row_capacity, const double* goals, int g_stride, const int* n_goals, int* goal_index,
                                    const double* interval, int* curve_index, int* cur_off, int* cur_len, int* point_index,
                                    float* cur_vel, int* status, int* log_goal, hipStream_t stream);
+// route_wave_kernel (the header's "routed curves"): the fields with the map's frame, and -- for the re-task alone -- the arguments
+// of npa_cycle_retask that are not the curve's, by name.  t == nullptr: npa_route_curve_batch (start, goals [B][3], one
+// capacity, mask, rows [B][capacity][4], n_rows); else npa_cycle_retask_routed (start = the state, goals [B][g_stride][3], rows =
+// the curve table, n_rows = the retask_status; capacity and mask are not read).
+struct RouteFrame {
+  const uint32_t* fields;
+  int n_fields, nx, ny;
+  double x0, y0, resolution;
+};
+struct RetaskTable {
+  int T, cycle, g_stride;
+  int* arrived;
+  const int *collided, *curve_off, *robot_first, *row_capacity, *n_goals;
+  int *curve_len, *goal_index, *curve_index, *cur_off, *cur_len, *point_index;
+  float* cur_vel;
+  int* log_goal;
+};
+hipError_t npa_launch_route_wave(int batch, const RouteFrame& m, const int* field_of, const double* start, const double* goals,
+                                 const double* interval, int capacity, const int* mask, double* rows, int* n_rows,
+                                 const RetaskTable* t, hipStream_t stream);
 hipError_t npa_launch_cycle_switch(int batch, int loop, const double* state, const int* curve_arrived, const int* curve_off,
                                    const int* curve_len, const int* robot_first, int* curve_index, int* cur_off, int* cur_len,
                                    int* point_index, int* arrived, npa_scan_params* params_a, npa_scan_params* params_b,

@@ -11,9 +11,14 @@ the occupied cells by the robot's radius, `GoalFields` seeds the fields and call
 Cells: cell (i, j) covers [x0 + i res, x0 + (i + 1) res) x [y0 + j res, y0 + (j + 1) res) and is cells[j, i]; a cell as a
 pair is (i, j).  Moves cost 5 along an axis and 7 along a diagonal, so a field value times res / 5 is metres.
 
-Out of scope: line-of-sight shortcutting of a chain (a path keeps the eight directions of the grid); re-routing inside
-npa_cycle_retask, whose robots own one curve region each (a goal queue's curves still know no walls); agents that plan
-(the world's agents keep their reactive behaviours).
+A goal queue's next leg takes the same way on the device: `route_batch` (npa_route_curve_batch) is chain, way-points and `line`
+rows in one launch, one wave per robot, and `ResidentLoop(goals=..., route=...)` / `run_closed_loop(goals=..., route=...)`
+re-task through it (npa_cycle_retask_routed; world.py).  The fields of a loop's goals stay on the device for the loop's
+lifetime: G ny nx 4 bytes for G distinct goal cells (goals in one cell share a field).
+
+Out of scope: line-of-sight shortcutting of a chain (a path keeps the eight directions of the grid); routed legs of any style
+but `line` (Dubins, Reeds-Shepp); routed goals in `LonLoop` / `train_closed_loop` and in the single-robot `neupan` class;
+agents that plan (the world's agents keep their reactive behaviours).
 """
 from __future__ import annotations
 
@@ -242,6 +247,53 @@ def waypoints(grid, chain, length, starts, goals):
             wp.append(np.array([[p[0]], [p[1]], [th]]))
         out.append(wp)
     return out
+
+
+def route_batch(fields, field_of, starts, goals, interval, capacity, mask=None, out=None, n_rows=None):
+    """B routed paths on the device, one launch (npa_route_curve_batch: include/neupan_amd.h, "routed curves"): per robot the
+    chain of `trace` from the start's cell, the positions of `waypoints` and the rows of planner.generate_curve("line") between
+    them, without the host.  fields: a `GoalFields` (its map's frame is the frame); field_of [B]: the field of robot b's goal;
+    starts, goals [B, 3]; interval: scalar or [B]; capacity: rows per path; mask [B] (optional): entries that are zero leave
+    their rows and their count untouched; out [B, capacity, 4] float64 / n_rows [B] int32: contiguous device tensors to write
+    into (default: new, zero-filled; anything else is a ValueError).  With device tensors of these types for every argument the
+    call converts nothing and reads nothing back: it is the launch.  Returns (rows, n_rows) device tensors, like `curves.generate_batch`: n_rows[b] > 0 rows of
+    path b are valid; -needed: it did not fit and nothing was written (-2^31: a segment outside the curve specification); 0: no
+    route (field_of outside the fields, a start outside the map, in a blocked cell or in a cell no path leads out of)."""
+    lib = _lib.load()
+    dev = fields.fields.device
+    G, ny, nx = fields.fields.shape
+    f64 = lambda a, shape: torch.as_tensor(a, dtype=torch.float64).to(dev).reshape(shape).contiguous()
+    s = f64(starts, (-1, 3))
+    B = s.shape[0]
+    g = f64(goals, (B, 3))
+    itv = interval if isinstance(interval, torch.Tensor) else torch.as_tensor(np.broadcast_to(np.asarray(interval, dtype=np.float64), (B,)).copy())
+    itv = f64(itv, (B,))
+    # (a device tensor is taken as it is: nothing here reads anything back)
+    fo = (field_of if isinstance(field_of, torch.Tensor) else torch.as_tensor(np.asarray(field_of))).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+    capacity = int(capacity)
+    if out is None:
+        out = torch.zeros((B, capacity, 4), dtype=torch.float64, device=dev)
+    if n_rows is None:
+        n_rows = torch.zeros((B,), dtype=torch.int32, device=dev)
+    if tuple(out.shape) != (B, capacity, 4) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float64 [{B}, {capacity}, 4]")
+    if out.device != dev or n_rows.device != dev:
+        raise ValueError(f"out and n_rows must be on the fields' device, {dev}")
+    if tuple(n_rows.shape) != (B,) or n_rows.dtype != torch.int32 or not n_rows.is_contiguous():
+        raise ValueError(f"n_rows must be a contiguous int32 [{B}]")
+    m = None
+    if mask is not None:                             # (converted, so its dtype and layout are ours; its length is the caller's)
+        m = torch.as_tensor(mask)
+        if m.numel() != B:
+            raise ValueError(f"mask must have {B} entries, not {m.numel()}")
+        m = m.to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    x0, y0 = (float(v) for v in fields.grid.origin)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib.npa_route_curve_batch(B, ptr(fields.fields), G, nx, ny, x0, y0, float(fields.grid.resolution), ptr(fo), ptr(s), ptr(g),
+                                        ptr(itv), capacity, ptr(m), ptr(out), ptr(n_rows), stream), "npa_route_curve_batch")
+    return out, n_rows
 
 
 def route_paths(grid, starts, goals, radius, interval, curve_style="line", min_radius=None, sweeps_per_call=64):

@@ -778,14 +778,16 @@ class _HostCycle:
 
 class _HostRetask:
     """The host-paced twin of npa_cycle_retask, behind `_HostCycle.cycle`: it reads the arrival and collision flags, takes the
-    new rows from npa_curve_batch -- the DEVICE generator: libm and the device math library differ in the last bits, and only
+    new rows from npa_curve_batch (with `route=`: from npa_route_curve_batch, and a path that does not fit its robot's region is
+    status 2, no route status 3) -- the DEVICE generator: libm and the device math library differ in the last bits, and only
     the same code gives the two loops the same bits -- and hands them to `fleet.retask`.  Attributes as ResidentLoop's:
     goal_index, retask_status [B] (host int32), log [cycles, B] int32 (device)."""
 
-    def __init__(self, fleet, device, cycles, goals, path_capacity, curve_style, min_radius):
+    def __init__(self, fleet, device, cycles, goals, path_capacity, curve_style, min_radius, routed=None):
         q = _goal_queues(goals, fleet, path_capacity, curve_style, min_radius)
         B = fleet.B
         self.fleet, self.q, self.B = fleet, q, B
+        self.routed = routed                         # (GoalFields, field_of [B, g_stride]) with `route=`: the rows come from route_batch
         self.goals = torch.from_numpy(q["goals"]).to(device)
         self.interval = torch.from_numpy(_bcast(fleet.intervals, B)).to(device)
         self.goal_index, self.retask_status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
@@ -799,10 +801,17 @@ class _HostRetask:
         go = fleet.arrived & ~loop.collided.cpu().numpy() & (gi < q["n_goals"])
         self.retask_status[:] = 0
         if go.any():
-            pick = torch.from_numpy(np.minimum(gi, q["goals"].shape[1] - 1).astype(np.int64)).to(self.goals.device)
+            pick_h = np.minimum(gi, q["goals"].shape[1] - 1).astype(np.int64)
+            pick = torch.from_numpy(pick_h).to(self.goals.device)
             goal = self.goals[torch.arange(self.B, device=pick.device), pick]
-            rows, n_rows = generate_batch(q["style"], loop.st, goal, self.interval, q["min_radius"], capacity=self.rows.shape[1],
-                                          mask=go.astype(np.int32), out=self.rows, n_rows=self.n_rows)
+            if self.routed is None:
+                rows, n_rows = generate_batch(q["style"], loop.st, goal, self.interval, q["min_radius"], capacity=self.rows.shape[1],
+                                              mask=go.astype(np.int32), out=self.rows, n_rows=self.n_rows)
+            else:                                    # npa_cycle_retask_routed's device function: the same bits
+                from .route import route_batch
+                fields, field_of = self.routed
+                rows, n_rows = route_batch(fields, field_of[np.arange(self.B), pick_h], loop.st, goal, self.interval,
+                                           self.rows.shape[1], mask=go.astype(np.int32), out=self.rows, n_rows=self.n_rows)
             n_h = n_rows.cpu().numpy()
             loop.arrive = loop.arrive.clone()
             for b in np.nonzero(go)[0]:
@@ -812,13 +821,13 @@ class _HostRetask:
                     gi[b] += 1
                     self.retask_status[b] = 1
                     loop.arrive[b] = False
-                else:
-                    self.retask_status[b] = 2
+                else:                                # (routed: 0 is "no route"; -needed and "no curve" are below 0)
+                    self.retask_status[b] = 3 if self.routed is not None and n == 0 else 2
         self.log[cyc] = torch.from_numpy(gi.copy()).to(self.log.device)
 
 
 def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=False, certify=False, peers=False,
-                    max_points=None, actions=None, goals=None, path_capacity=None, curve_style="line", min_radius=None):
+                    max_points=None, actions=None, goals=None, path_capacity=None, curve_style="line", min_radius=None, route=None):
     """example/run_exp.py's loop for the B robots of `fleet` (a FleetPlanner whose paths are set) in `world`:
 
         scan (LidarWorld.scan) -> scan_to_point[_velocity]_batch -> fleet.forward -> LidarWorld.step
@@ -841,9 +850,11 @@ def run_closed_loop(fleet, world, states, cycles, scan=None, point_velocities=Fa
     `goals` (one list of (x, y, theta) per robot; with path_capacity, curve_style, min_radius as ResidentLoop takes them): a
     robot that has arrived and has not collided is given the curve from its pose to its next goal at the end of the cycle
     (`_HostRetask`: the reference's reset() + update_initial_path_from_goal); the result then also has goal [cycles, B] int32
-    (the number of goals consumed after each cycle), goal_index and retask_status [B] int32."""
+    (the number of goals consumed after each cycle), goal_index and retask_status [B] int32.  `route` (with goals; as
+    ResidentLoop takes it): the legs lead through the world's map."""
+    routed = _route_fields(route, world, goals, curve_style)
     loop = _HostCycle(fleet, world, states, cycles, scan, point_velocities, peers, max_points)
-    tasks = None if goals is None else _HostRetask(fleet, world.device, cycles, goals, path_capacity, curve_style, min_radius)
+    tasks = None if goals is None else _HostRetask(fleet, world.device, cycles, goals, path_capacity, curve_style, min_radius, routed)
     override = None if actions is None else torch.as_tensor(actions).to(device=world.device, dtype=torch.float32)
     for cyc in range(cycles):
         info, _, _ = loop.cycle(cyc, None if override is None else override[cyc], certify)
@@ -881,6 +892,43 @@ def _goal_queues(goals, fleet, path_capacity, curve_style, min_radius):
             table[b, :len(q)] = np.asarray(q, dtype=np.float64).reshape(len(q), -1)[:, :3]
     cap = np.array([max(c[0].shape[0], int(path_capacity or 0)) for c in fleet.curve_lists], dtype=np.int32)
     return dict(goals=table, n_goals=np.array([len(q) for q in goals], dtype=np.int32), capacity=cap, style=style, min_radius=rho)
+
+
+def _route_fields(route, world, goals, curve_style):
+    """`route=` of the loops: None, or dict(radius [m], sweeps_per_call=64).  Returns None, or (the `route.GoalFields` of the
+    distinct goal CELLS of all queues over the world's map inflated by `radius` -- a field is seeded in its goal's cell, so goals
+    that share a cell share a field --, field_of [B, g_stride] int32 (host): the field of goals[b][k]; 0 where a queue is
+    shorter).  ValueError: no goals, no map in the world, no radius, more than 65535 distinct goal cells, and what GoalFields
+    raises (a goal outside the map or in a blocked cell: named by the first goal in that cell, counted in the order in which the
+    cells first appear); NotImplementedError: a curve_style other than 'line'."""
+    if route is None:
+        return None
+    if goals is None:
+        raise ValueError("route: a routed loop needs goals (route= says how a goal queue's legs are made)")
+    if not isinstance(route, dict) or "radius" not in route or set(route) - {"radius", "sweeps_per_call"}:
+        raise ValueError("route: dict(radius=..., sweeps_per_call=64)")
+    if world.grid is None:
+        raise ValueError("route: the world has no map (LidarWorld.set_map); without one the curves of goals= need no route")
+    if curve_style != "line":
+        raise NotImplementedError(f"route: routed legs are 'line' curves between the turns of the chain, not {curve_style!r}")
+    from .route import GoalFields, cells_of
+    stride = max(1, max((len(q) for q in goals), default=0))
+    flat = [tuple(float(v) for v in np.asarray(g, dtype=np.float64).reshape(-1)[:2]) for q in goals for g in q]
+    if not flat:
+        raise ValueError("route: every goal queue is empty")
+    cells = [tuple(c) for c in cells_of(world.grid, np.asarray(flat)).tolist()]
+    first = {}                                       # cell -> the first goal in it, in the order in which the cells first appear
+    for c, g in zip(cells, flat):
+        first.setdefault(c, g)
+    if len(first) > 65535:
+        raise ValueError(f"route: {len(first)} distinct goal cells, more than the 65535 fields of one launch")
+    index = {c: k for k, c in enumerate(first)}
+    field_of = np.zeros((len(goals), stride), dtype=np.int32)
+    it = iter(cells)
+    for b, q in enumerate(goals):
+        for k in range(len(q)):
+            field_of[b, k] = index[next(it)]
+    return GoalFields(world.grid, np.asarray(list(first.values())), float(route["radius"]), int(route.get("sweeps_per_call", 64))), field_of
 
 
 def curve_table(curve_lists, capacity=None):
@@ -922,7 +970,7 @@ class ResidentLoop:
         -> npa_forward_batch_flags [-> npa_plan_clearance]                                                    (_plan_step)
         -> npa_cycle_act (warm start, stop, action, override, freeze)
         [-> npa_world_behave, when the world has agents] -> npa_world_step -> npa_cycle_commit (collision latch, log rows)
-        [-> npa_cycle_retask, when the loop has goals]                                                        (_tail_step)
+        [-> npa_cycle_retask, when the loop has goals; with `route`: npa_cycle_retask_routed]                 (_tail_step)
     and, when the world has a map (`LidarWorld.set_map`), npa_grid_scan behind the scan and npa_grid_clearance between
     npa_world_step and npa_cycle_commit (include/neupan_amd_grid.h): the map the world has when the loop is made, held for the
     loop's lifetime; without a map neither is issued,
@@ -935,6 +983,14 @@ class ResidentLoop:
     path_capacity) rows.  A curve that does not fit leaves the robot arrived (retask_status 2).  Every robot's initial path must
     then be a single curve.  Without goals the table and the launches are what they were; attributes goal_index, retask_status
     [B] int32 (None without goals), and `run` adds logs["goal"] [cycles, B] int32: the goals consumed after each cycle.
+
+    With `route` = dict(radius=..., sweeps_per_call=64) beside `goals` the legs lead through the world's map (it needs one:
+    `set_map`; curve_style 'line'): the distinct goal cells of all queues get one cost-to-goal field each over the map
+    inflated by `radius` [m] (`route.GoalFields`, made here, once: G ny nx 4 bytes on the device for G cells, attribute
+    route_fields; a goal outside the map or in a blocked cell is its ValueError), and the launch is npa_cycle_retask_routed: the
+    chain from the robot's cell down its goal's field, `line` curves between its turns (include/neupan_amd.h, "routed curves").
+    retask_status 2: the path does not fit the robot's region; 3: no route from where the robot stands (outside the map, in an
+    inflated cell, cut off); either leaves the robot arrived.  Without `route` nothing changes, neither launches nor buffers.
 
     With `scan["noise"]` the scan slot holds npa_world_scan_noisy with draw = draw0 + cycles_done, a host scalar at issue time;
     the count runs on over runs (and over `LonLoop.reset`: episodes see different noise).  Without it the launch is npa_world_scan.
@@ -955,7 +1011,8 @@ class ResidentLoop:
     out (the plan's dict as PAN.forward_batch returns it), plan_clearance (with certify: PAN.plan_clearance's dict)."""
 
     def __init__(self, fleet, world, states, scan=None, point_velocities=False, certify=False, peers=False, max_points=None,
-                 goals=None, path_capacity=None, curve_style="line", min_radius=None):
+                 goals=None, path_capacity=None, curve_style="line", min_radius=None, route=None):
+        routed = _route_fields(route, world, goals, curve_style)
         if getattr(fleet, "B", 0) < 1:
             raise ValueError("ResidentLoop: the fleet has no paths (set_paths first)")
         if fleet.cur_vel is not None:
@@ -1102,6 +1159,7 @@ class ResidentLoop:
         self._commit = (_ptr(st), _ptr(self.clearance), _ptr(self.collided))
         # ---- the next goal of a robot that has arrived, behind the commit (without goals: no launch, no buffer)
         self._retask, self._log_goal, self.goal_index, self.retask_status = None, None, None, None
+        self._routed, self.route_fields = None, None
         if goals is not None:
             q = self._goals
             self.goal_index, self.retask_status = zeros((B,), torch.int32), zeros((B,), torch.int32)
@@ -1111,6 +1169,14 @@ class ResidentLoop:
                             _ptr(self.goal_index), _ptr(itv), _ptr(self.curve_index), _ptr(self.cur_off), _ptr(self.cur_len),
                             _ptr(self.point_index), _ptr(self.cur_vel), _ptr(self.retask_status))
             self._held = self._held + held
+            if routed is not None:                   # the routed re-task: the same arguments, then the fields, the frame, field_of
+                fields, field_of = routed
+                fo = i32(field_of)
+                _, ny, nx = fields.fields.shape
+                self._routed = (_ptr(fields.fields), fields.fields.shape[0], nx, ny, float(world.grid.origin[0]),
+                                float(world.grid.origin[1]), float(world.grid.resolution), _ptr(fo))
+                self.route_fields = fields
+                self._held = self._held + (fields.fields, fo)
         # ---- the agents' choice, between act and step (a world without agents: no launch, no buffer)
         self._behave, self.prev_states = None, None
         if world.has_agents:
@@ -1181,10 +1247,15 @@ class ResidentLoop:
         if rc:
             check(rc, "npa_cycle_commit")
         if self._retask is not None:                     # (the goal log is a run's: `run` sets its address, `cycle` has none)
-            style, rho = self._retask[:2]
-            rc = lib.npa_cycle_retask(self.B, self.T, row, style, rho, *self._retask[2:], self._log_goal, stream)
-            if rc:
-                check(rc, "npa_cycle_retask")
+            if self._routed is not None:
+                rc = lib.npa_cycle_retask_routed(self.B, self.T, row, *self._retask[2:], self._log_goal, *self._routed, stream)
+                if rc:
+                    check(rc, "npa_cycle_retask_routed")
+            else:
+                style, rho = self._retask[:2]
+                rc = lib.npa_cycle_retask(self.B, self.T, row, style, rho, *self._retask[2:], self._log_goal, stream)
+                if rc:
+                    check(rc, "npa_cycle_retask")
 
     def _finish_step(self):
         """the host's bookkeeping behind a cycle: what the planner reports as its last call, the counters, the audit"""
