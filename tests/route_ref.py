@@ -42,7 +42,68 @@ def dijkstra(blocked, seeds):
     return out
 
 
+def dijkstra_moves(blocked, seeds):
+    """dijkstra ordered by (cost, moves): returns (field, moves [ny, nx] int64) -- moves[j, i] is the least number of moves among
+    the cheapest move sequences from a seed to (i, j), -1 where the cell is blocked or unreached.  (cost, moves) adds along a
+    sequence and is ordered lexicographically, so the heap argument is Dijkstra's.)  The header's claim about k sweeps short
+    of convergence is about exactly these cells: moves <= k."""
+    occ = np.asarray(blocked) != 0
+    ny, nx = occ.shape
+    rows = occ.tolist()
+    free = lambda i, j: 0 <= i < nx and 0 <= j < ny and not rows[j][i]
+    best = {}
+    heap = [(int(v), 0, i, j) for (i, j), v in seeds.items()]
+    heapq.heapify(heap)
+    while heap:
+        v, m, i, j = heapq.heappop(heap)
+        if (i, j) in best:
+            continue
+        best[(i, j)] = (v, m)
+        for di, dj, c in MOVES:
+            a, b = i + di, j + dj
+            if (a, b) in best or not free(a, b):
+                continue
+            if di and dj and not (free(i + di, j) and free(i, j + dj)):
+                continue
+            heapq.heappush(heap, (v + c, m + 1, a, b))
+    out = np.full((ny, nx), UNREACHED, dtype=np.uint32)
+    out[occ] = BLOCKED
+    moves = np.full((ny, nx), -1, dtype=np.int64)
+    for (i, j), (v, m) in best.items():
+        out[j, i], moves[j, i] = v, m
+    return out, moves
+
+
 # ---------------------------------------------------------------------------------------------------- the maps
+def random_map(nx, ny, seed, share=0.2):
+    """nx x ny, `share` of the cells blocked, seeded"""
+    return (np.random.default_rng(seed).random((ny, nx)) < share).astype(np.uint8)
+
+
+def pillars():
+    """24 x 24 of single-cell pillars, 22 % of the cells, with the goal cell (12, 12) freed: starts all round the goal, chains
+    that squeeze past corners, and many cells with several allowed moves"""
+    occ = (np.random.default_rng(0).random((24, 24)) < 0.22).astype(np.uint8)
+    occ[12, 12] = 0
+    return occ
+
+
+# (nx, ny, seed, goal cell) of the maps that end on, one past and one short of the 16-cell tile; the goals of the first three
+# are corner cells of the map.  The seeds are the first at which the field reaches over 70 % of the cells and leaves some out
+TILE_EDGE_MAPS = ((16, 16, 2, (15, 15)), (17, 16, 1, (16, 0)), (16, 17, 2, (0, 16)), (15, 33, 1, (7, 20)), (32, 16, 1, (16, 8)))
+
+
+def tile_edge_map(nx, ny, seed, goal):
+    occ = random_map(nx, ny, seed)
+    occ[goal[1], goal[0]] = 0
+    return occ
+
+
+# the seeds of the large-seed runs over an open 9 x 7 map: every value above 2^31, and values on both sides of it
+BIG_SEED = 2 ** 32 - 7 * 2 ** 26 - 1
+BIG_SEEDS = ({(4, 3): BIG_SEED}, {(0, 0): 2 ** 31 - 3, (8, 6): 2 ** 31 - 23})
+
+
 def inner_wall():
     """37 x 21 (neither a multiple of the 16-cell tile): a wall with a gap near the top, a stub from the bottom"""
     occ = np.zeros((21, 37), dtype=np.uint8)

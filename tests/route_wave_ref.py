@@ -172,6 +172,87 @@ class Scene:
 
 _SCENES = {}
 
+# ---- the cases of tests/test_route_edges_gpu.py (tests/test_route_wave.py asserts what is claimed of them here)
+EDGE_ORIGIN, EDGE_RES, EDGE_INTERVAL = (-2.3, 4.1), 0.3, 0.23                  # the frame of "open21" and "pillars"
+# the frames whose start cells rounding decides: 1 / 0.1 and 1 / 0.7 are not exact, 1 / 0.25 is (that frame has the edges)
+ROUNDING_FRAMES = {"round_tenth": ((-3.7, 1.3), 0.1), "round_seven": ((0.0, 0.0), 0.7), "round_far": ((2.0 ** 20, -2.0 ** 21), 0.25)}
+# (frame, axis, coordinate, cell by floor((x - x0) / res), cell by floor((x - x0) * (1 / res))): the first is the cell
+ROUNDING_TRIPLES = (("round_tenth", 0, -2.8000000000000003, 8, 9), ("round_tenth", 1, 2.0, 6, 7),
+                    ("round_seven", 0, 3.4999999999999996, 5, 4), ("round_seven", 0, 7 * 0.7, 7, 6), ("round_seven", 0, 6.999999999999999, 10, 9),
+                    ("round_seven", 1, 3.4999999999999996, 5, 4), ("round_seven", 1, 7 * 0.7, 7, 6), ("round_seven", 1, 6.999999999999999, 10, 9))
+
+
+def rounded_starts(name):
+    """(x, y, what) of the starts of a frame of ROUNDING_FRAMES on a 12 x 12 map: its triples on their axis (the other coordinate
+    mid-cell, where the chain's first turn depends on the cell) and two of them together; a start at x0, at y0, on the far edges x0 + nx res and y0 + ny res and one ulp below
+    them; -0.0 where the origin is 0; +inf and -inf"""
+    (x0, y0), res = ROUNDING_FRAMES[name]
+    mid = (x0 + 4.4 * res, y0 + 2.6 * res)
+    out = []
+    mine = [t for t in ROUNDING_TRIPLES if t[0] == name]
+    for _, axis, v, _, _ in mine:
+        out.append((v, mid[1], f"x = {v!r}") if axis == 0 else (x0 + 10.4 * res, v, f"y = {v!r}"))
+    xs, ys = [t[2] for t in mine if t[1] == 0], [t[2] for t in mine if t[1] == 1]
+    if xs and ys:
+        out.append((xs[0], ys[0], "both axes"))
+    far = (x0 + 12 * res, y0 + 12 * res)
+    out += [(x0, mid[1], "x0"), (mid[0], y0, "y0"), (x0, y0, "the origin"), (far[0], mid[1], "x0 + nx res"), (mid[0], far[1], "y0 + ny res"),
+            (math.nextafter(far[0], -math.inf), mid[1], "one ulp below x0 + nx res"),
+            (mid[0], math.nextafter(far[1], -math.inf), "one ulp below y0 + ny res"),
+            (math.nextafter(x0, -math.inf), mid[1], "one ulp below x0"),
+            (math.inf, mid[1], "+inf"), (mid[0], -math.inf, "-inf"), (-math.inf, math.inf, "both infinite")]
+    if x0 == 0.0 and y0 == 0.0:
+        out += [(-0.0, mid[1], "x = -0.0"), (mid[0], -0.0, "y = -0.0"), (-0.0, -0.0, "both -0.0")]
+    return out
+
+
+LONG_K = (62.5, 63.5, 64.5, 127.5, 128.5, 191.5, 192.5)      # D / interval of the one-segment path of "23x1"
+LONG_ROWS = (64, 65, 66, 129, 130, 193, 194)                  # its n_rows: segments of 63, 64, 65, 128, 129, 192, 193 rows
+LONG_D = 9.650129532809391
+LONG_TURN_INTERVAL, LONG_TURN_SEGMENTS = 0.05, (30, 156, 60, 156, 30, 15)
+
+
+def long_cases():
+    """"23x1"'s case at intervals that put its one segment on either side of one, two and three trips of the 64-lane row loop"""
+    f, start, goal, _ = scene("23x1").cases[0]
+    return [(f, start, goal, LONG_D / k) for k in LONG_K]
+
+
+def long_turn_case():
+    """"inner_wall"'s first case at a small interval: segments of LONG_TURN_SEGMENTS rows -- the second, third and later ones
+    take their second trip at a row count above 0"""
+    f, start, goal, _ = scene("inner_wall").cases[0]
+    return (f, start, goal, LONG_TURN_INTERVAL)
+
+
+def segment_rows(result, interval):
+    """the n of every segment of a result of `route` that was not skipped"""
+    return [line_plan(0.0, 0.0, D, 0.0, interval)[0] for D, _ in result["segments"]]
+
+
+def coincidence_cases():
+    """[(what, case)] over "inner_wall" (its cell centres are exact): way-points that coincide with the poses"""
+    s = scene("inner_wall")
+    f, start, goal, itv = s.cases[0]
+    base = s.route(f, start, goal, itv)
+    last = s.centre(base["turns"][-1])
+    # a start cell whose chain turns in the very next cell, and one whose chain never turns
+    turn1 = straight = None
+    for j in range(s.blocked.shape[0]):
+        for i in range(s.blocked.shape[1]):
+            w = walk(s.fields[0], (i, j))
+            if w is None or len(w[1]) < 2:
+                continue
+            if turn1 is None and w[1][0] != w[1][1]:
+                turn1 = (i, j)
+            if straight is None and len(set(w[1])) == 1 and len(w[1]) >= 3:
+                straight = (i, j)
+    g = s.centre(s.goal_cells[0])
+    return [("the goal on the last turn cell's centre", (f, start, (*last, 0.8), itv)),
+            ("the start on its own cell's centre, a turn in the next cell", (f, (*s.centre(turn1), 0.3), goal, itv)),
+            ("start and goal on the centres of their cells, no turn: one segment", (f, (*s.centre(straight), 0.3), (*g, -0.6), itv)),
+            ("the start on the goal cell's centre, which is the goal: the only way-point", (f, (*g, 0.3), (*g, -0.6), itv))]
+
 
 def scene(name):
     """the scenes of the tests by name, made once.  A case is (field, start pose, goal pose, interval)."""
@@ -202,6 +283,32 @@ def scene(name):
     elif name == "narrow":
         s = Scene(narrow_serpentine(), (0.0, 0.0), 1.0, [(0, 0)])
         s.cases = [(0, (0.5, 40.5, 0.0), (0.5, 0.5, 0.0), 1.0)]
+    elif name in ("open21", "pillars"):
+        # one robot in every cell the field reaches, at (i + 0.37, j + 0.61) res from the origin; the goal off its cell's centre.
+        # pillars holds a second field (the cell farthest from the first goal) for the re-task test
+        occ, g = (np.zeros((21, 21), dtype=np.uint8), (10, 10)) if name == "open21" else (rr.pillars(), (12, 12))
+        s = Scene(occ, EDGE_ORIGIN, EDGE_RES, [g])
+        if name == "pillars":
+            f0 = np.where(s.fields[0] < rr.UNREACHED, s.fields[0], 0)
+            j, i = np.unravel_index(int(np.argmax(f0)), f0.shape)
+            s = Scene(occ, EDGE_ORIGIN, EDGE_RES, [g, (int(i), int(j))])
+        gx, gy = s.centre(g)
+        js, is_ = np.nonzero(s.fields[0] < rr.UNREACHED)
+        s.cases = [(0, (EDGE_ORIGIN[0] + (i + 0.37) * EDGE_RES, EDGE_ORIGIN[1] + (j + 0.61) * EDGE_RES, 0.1), (gx + 0.04, gy - 0.07, 0.9),
+                    EDGE_INTERVAL) for i, j in zip(is_.tolist(), js.tolist())]
+    elif name in ROUNDING_FRAMES:
+        # small open maps whose frames decide a start's cell by rounding (rounded_starts); the goal cell (3, 8)
+        origin, res = ROUNDING_FRAMES[name]
+        s = Scene(np.zeros((12, 12), dtype=np.uint8), origin, res, [(3, 8)])
+        gx, gy = s.centre((3, 8))
+        s.cases = [(0, (x, y, 0.2), (gx + 0.11 * res, gy - 0.23 * res, -0.4), 0.37 * res) for x, y, _ in rounded_starts(name)]
+    elif name == "five_fields":
+        # the inner wall's 777 cells under five fields; robot b goes down field b % 5 from a cell of its own
+        goals = [(3, 2), (30, 18), (20, 0), (36, 20), (0, 12)]
+        s = Scene(rr.inner_wall(), (-3.0, 2.0), 0.5, goals)
+        free = [(i, j) for j in range(0, 21, 4) for i in range(1, 37, 5) if not s.blocked[j, i]]
+        s.cases = [(b % 5, (s.centre(c)[0] + 0.07, s.centre(c)[1] - 0.11, 0.0), (s.centre(goals[b % 5])[0] - 0.13, s.centre(goals[b % 5])[1] + 0.06,
+                                                                                0.5), 0.31) for b, c in enumerate(free)]
     elif name in ("pocket", "corner_pair"):
         occ, g = rr.MAPS[name]
         s = Scene(occ, (0.0, 0.0), 0.25, [g])

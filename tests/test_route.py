@@ -271,3 +271,33 @@ def test_goals_the_fields_cannot_have_are_refused_by_name():
             route.GoalFields(grid, [ok], 0.0, seeds=[seed])
     with pytest.raises(NeupanAmdError, match="no CPU fallback"):
         route.GoalFields(grid, [ok], 0.5)                            # (a sound request on a CPU map: the relaxation is HIP only)
+
+
+# ---------------------------------------------------------------------------------------------------- the cases of the edge tests
+def test_the_cases_of_the_raw_relaxation_are_what_they_claim():
+    """tests/test_route_edges_gpu.py runs these on the device; what it relies on is asserted here from the restatement"""
+    open_map = np.zeros((7, 9), dtype=np.uint8)
+    one, two = (rr.dijkstra(open_map, seeds).astype(np.int64) for seeds in rr.BIG_SEEDS)
+    assert rr.BIG_SEED == 2 ** 32 - 7 * 2 ** 26 - 1 and one.min() == rr.BIG_SEED > 2 ** 31 and one.max() < rr.UNREACHED
+    assert (one - rr.BIG_SEED == rr.dijkstra(open_map, {(4, 3): 0})).all()          # seed plus distance everywhere
+    assert two.min() == 2 ** 31 - 23 and (two < 2 ** 31).sum() >= 8 and (two > 2 ** 31).sum() >= 8      # values on both sides of 2^31
+    assert two[6, 8] == 2 ** 31 - 23 and two[0, 0] == 2 ** 31 - 3                    # (each seed governs its own corner)
+    # (cost, moves): the same field, and for every k of the test both cells that are final after k sweeps and cells that are not
+    occ, goal = rr.MAPS["serpentine"]
+    f, moves = rr.dijkstra_moves(occ, {goal: 0})
+    assert (f == rr.field("serpentine")).all() and moves[goal[1], goal[0]] == 0 and ((moves >= 0) == (f < rr.UNREACHED)).all()
+    for k in (1, 2, 5, 17):
+        assert ((moves >= 0) & (moves <= k)).sum() > 1 and (moves > k).any(), k
+    small, m = rr.dijkstra_moves(np.zeros((3, 4), dtype=np.uint8), {(0, 0): 0})
+    assert small.tolist() == [[0, 5, 10, 15], [5, 7, 12, 17], [10, 12, 14, 19]] and m.tolist() == [[0, 1, 2, 3], [1, 1, 2, 3], [2, 2, 2, 3]]
+    # the tile-edge maps: 20 % blocked, the goal free, most cells reached and some not, a goal in a corner of the map
+    sizes = [(nx, ny) for nx, ny, _, _ in rr.TILE_EDGE_MAPS]
+    assert sizes == [(16, 16), (17, 16), (16, 17), (15, 33), (32, 16)]
+    for nx, ny, seed, g in rr.TILE_EDGE_MAPS:
+        o = rr.tile_edge_map(nx, ny, seed, g)
+        d = rr.dijkstra(o, {g: 0})
+        assert o.shape == (ny, nx) and 0.1 < o.mean() < 0.3 and (d < rr.UNREACHED).sum() > 0.7 * nx * ny and (d == rr.UNREACHED).any()
+    assert rr.TILE_EDGE_MAPS[0][3] == (15, 15)
+    # the pillar map
+    p = rr.pillars()
+    assert p.shape == (24, 24) and p[12, 12] == 0 and p.sum() == 115

@@ -1,7 +1,9 @@
 """No GPU: routed curves (include/neupan_amd.h "routed curves": npa_route_curve_batch, npa_cycle_retask_routed) -- what the two
 exports refuse, the plain-Python restatement (tests/route_wave_ref.py) against what `route_paths` already does on CPU tensors
 (`trace` + `waypoints` + `generate_curve("line")`), the kernel's resources, and the `route=` arguments the loops refuse before
-they touch a device.  The kernel itself is compared with the restatement on the device: tests/test_route_wave_gpu.py."""
+they touch a device.  The kernel itself is compared with the restatement on the device: tests/test_route_wave_gpu.py; and
+tests/test_route_edges_gpu.py runs cases whose figures -- segment rows, first moves, turn pairs, cells that rounding decides
+-- are asserted here from the restatement, so that a later edit of a case cannot quietly empty it."""
 import ctypes as C
 import os
 import sys
@@ -127,6 +129,118 @@ def test_the_restatement_says_no_route_and_no_curve():
         assert s.route(0, ok, goal, interval)["n_rows"] == rw.NO_CURVE, interval
     assert s.route(0, ok, (goal[0], NAN, 0.0), 0.3)["n_rows"] == rw.NO_CURVE
     assert [rw.status_of(n, 5) for n in (1, 5, 6, -6, rw.NO_CURVE, rw.NO_ROUTE)] == [1, 1, 2, 2, 2, 3]
+
+
+# ---------------------------------------------------------------------------------------------------- the cases of the edge tests
+def moves_of(chain):
+    return [[(m[0], m[1]) for m in rw.MOVES].index((b[0] - a[0], b[1] - a[1])) for a, b in zip(chain, chain[1:])]
+
+
+def test_the_long_segments_are_as_long_as_claimed():
+    """tests/test_route_edges_gpu.py: the one segment of "23x1" on either side of one, two and three trips of the row loop, and a
+    path whose later segments take a second trip"""
+    s = rw.scene("23x1")
+    got = [s.route(*c) for c in rw.long_cases()]
+    for r in got:
+        rw.assert_counts_are_decided(r)
+        assert len(r["segments"]) == 1 and r["segments"][0][0] == rw.LONG_D == 9.650129532809391 and not r["turns"]
+    assert [rw.segment_rows(r, c[3]) for r, c in zip(got, rw.long_cases())] == [[63], [64], [65], [128], [129], [192], [193]]
+    assert tuple(r["n_rows"] for r in got) == rw.LONG_ROWS == (64, 65, 66, 129, 130, 193, 194)
+    case = rw.long_turn_case()
+    r = rw.scene("inner_wall").route(*case)
+    rw.assert_counts_are_decided(r)
+    assert tuple(rw.segment_rows(r, case[3])) == rw.LONG_TURN_SEGMENTS == (30, 156, 60, 156, 30, 15) and r["n_rows"] == 448
+
+
+@pytest.mark.parametrize("name, robots, pairs", [("open21", 441, 8), ("pillars", 461, 24)])
+def test_the_fleets_start_with_every_move_and_turn_every_way(name, robots, pairs):
+    s = rw.scene(name)
+    assert s.origin == (-2.3, 4.1) and s.res == 0.3 and s.goal_cells[0] == ((10, 10) if name == "open21" else (12, 12))
+    assert len(s.cases) == robots == int((s.fields[0] < rr.UNREACHED).sum())
+    first, turn, tied = set(), set(), 0
+    for f, start, goal, interval in s.cases:
+        r = s.route(f, start, goal, interval)
+        rw.assert_counts_are_decided(r)
+        assert interval == 0.23 and r["n_rows"] >= 2
+        i, j = r["chain"][0]
+        assert start[:2] == (s.origin[0] + (i + 0.37) * s.res, s.origin[1] + (j + 0.61) * s.res)
+        mv = moves_of(r["chain"])
+        first.update(mv[:1])
+        turn.update((a, b) for a, b in zip(mv, mv[1:]) if a != b)
+        v = int(s.fields[0][j, i])                   # (more than one neighbour holds v - cost: the lowest bit decides)
+        tied += sum(0 <= i + di < s.blocked.shape[1] and 0 <= j + dj < s.blocked.shape[0] and int(s.fields[0][j + dj, i + di]) == v - c
+                    for di, dj, c in rw.MOVES) > 1
+    gx, gy = s.centre(s.goal_cells[0])
+    assert s.cases[0][2][:2] != (gx, gy)                             # (the goal lies off the centre of its cell)
+    assert first == set(range(8)) and len(turn) >= pairs and tied > robots // 4, (sorted(first), len(turn), tied)
+
+
+def test_the_rounded_starts_are_decided_by_rounding():
+    """for every triple the cell by one rounded division differs from the cell by the reciprocal, and the restatement takes the
+    first; the edge starts are inside or outside as the division says"""
+    import math
+    assert len(rw.ROUNDING_TRIPLES) >= 8 and {t[1] for t in rw.ROUNDING_TRIPLES} == {0, 1}
+    for name, axis, v, by_division, by_reciprocal in rw.ROUNDING_TRIPLES:
+        origin, res = rw.ROUNDING_FRAMES[name]
+        assert math.floor((v - origin[axis]) / res) == by_division != by_reciprocal == math.floor((v - origin[axis]) * (1.0 / res))
+        assert 0 <= by_division < 12 and 0 <= by_reciprocal < 12
+    assert 7 * 0.7 in [t[2] for t in rw.ROUNDING_TRIPLES] and ("round_tenth", 1, 2.0, 6, 7) in rw.ROUNDING_TRIPLES
+    assert rw.ROUNDING_FRAMES["round_far"] == ((2.0 ** 20, -2.0 ** 21), 0.25) and rw.ROUNDING_FRAMES["round_tenth"] == ((-3.7, 1.3), 0.1)
+    for name in rw.ROUNDING_FRAMES:
+        s = rw.scene(name)
+        starts = rw.rounded_starts(name)
+        assert len(s.cases) == len(starts)
+        got = {what: (rw.start_cell(*s.origin, s.res, x, y), s.route(*c)) for c, (x, y, what) in zip(s.cases, starts)}
+        for what, (cell, r) in got.items():
+            rw.assert_counts_are_decided(r)
+            inside = cell is not None and 0 <= cell[0] < 12 and 0 <= cell[1] < 12
+            assert (r["n_rows"] >= 2) == inside and (inside or r["n_rows"] == rw.NO_ROUTE), (name, what)
+            if inside:
+                assert r["chain"][0] == cell
+        for what in ("+inf", "-inf", "both infinite", "one ulp below x0"):
+            assert got[what][1]["n_rows"] == rw.NO_ROUTE
+        assert got["x0"][0][0] == 0 and got["y0"][0][1] == 0 and got["the origin"][0] == (0, 0)
+        assert got["one ulp below x0 + nx res"][0][0] == 11 and got["one ulp below y0 + ny res"][0][1] == 11
+        if name == "round_far":                                      # (exact arithmetic: the far edges are outside)
+            assert got["x0 + nx res"][1]["n_rows"] == got["y0 + ny res"][1]["n_rows"] == rw.NO_ROUTE
+        if name == "round_seven":
+            assert got["x = -0.0"][0] == (0, 2) and got["both -0.0"][0] == (0, 0)
+        for t in (t for t in rw.ROUNDING_TRIPLES if t[0] == name):   # the path depends on the cell: the other cell's differs
+            what = ("x = " if t[1] == 0 else "y = ") + repr(t[2])
+            cell, r = got[what]
+            other = (t[4], cell[1]) if t[1] == 0 else (cell[0], t[4])
+            c = s.cases[[w for _, _, w in starts].index(what)]
+            walked = rw.walk(s.fields[0], other)
+            turns = [walked[0][k] for k in range(1, len(walked[1])) if walked[1][k] != walked[1][k - 1]]
+            assert cell[t[1]] == t[3] and turns != r["turns"], (name, what)
+
+
+def test_the_coincidences_coincide():
+    s = rw.scene("inner_wall")
+    cases = rw.coincidence_cases()
+    got = [s.route(*c) for _, c in cases]
+    for r in got:
+        rw.assert_counts_are_decided(r)
+    base = s.route(*s.cases[0])
+    # the goal on the last turn cell's centre: one segment fewer than way-point pairs, h is the segment before's psi
+    assert got[0]["points"][-1] == got[0]["points"][-2] and len(got[0]["segments"]) == len(got[0]["points"]) - 2
+    assert got[0]["rows"][-1, 2] == got[0]["rows"][-2, 2] != 0.8 and got[0]["n_rows"] < base["n_rows"]
+    # the start on its own cell's centre, the first way-point the next cell's centre: one cell's step apart
+    (sx, sy), (wx, wy) = got[1]["points"][:2]
+    assert got[1]["turns"][0] == got[1]["chain"][1] and max(abs(wx - sx), abs(wy - sy)) == s.res
+    assert not got[2]["turns"] and len(got[2]["segments"]) == 1 and got[2]["n_rows"] > 2
+    assert got[3]["n_rows"] == 1 and not got[3]["segments"] and got[3]["rows"][0].tolist() == [*cases[3][1][2], 1.0]
+
+
+def test_the_five_fields_are_five_and_the_map_has_777_cells():
+    s = rw.scene("five_fields")
+    assert s.blocked.size == 777 and len(s.fields) == 5 and len({f.tobytes() for f in s.fields}) == 5
+    assert len(s.cases) > 16 and {c[0] for c in s.cases} == set(range(5))
+    for c in s.cases:
+        r = s.route(*c)
+        rw.assert_counts_are_decided(r)
+        assert r["n_rows"] >= 2
+    assert s.route(5, *s.cases[0][1:])["n_rows"] == s.route(-1, *s.cases[0][1:])["n_rows"] == rw.NO_ROUTE
 
 
 # ---------------------------------------------------------------------------------------------------- route= of the loops
