@@ -109,10 +109,16 @@ def curve(style, start, goal, interval, rho=0.0):
         rows = np.stack([start[0] + f * dx, start[1] + f * dy, np.full(n, th), np.ones(n)], axis=1)
         return np.vstack([rows, [goal[0], goal[1], th, 1.0]]), L, None
     word, seg, psi, alpha = shortest(start, goal, rho)
+    rows, L = word_rows(word, seg, psi, alpha, start, goal, interval, rho)
+    return rows, L, word
+
+
+def word_rows(word, seg, psi, alpha, start, goal, interval, rho):
+    """(rows [n + 1, 4], L) of `word` with the segment lengths `seg`; word None (the same pose) or L == 0: the goal pose"""
     total = sum(seg)
     L = rho * total
     if word is None or L == 0.0:
-        return np.array([[goal[0], goal[1], goal[2], 1.0]]), 0.0, word
+        return np.array([[goal[0], goal[1], goal[2], 1.0]]), 0.0
     n = steps(L, interval)
     c, s = math.cos(psi), math.sin(psi)
     rows = []
@@ -120,7 +126,37 @@ def curve(style, start, goal, interval, rho=0.0):
         x, y, h = integrate(word, seg, (0.0, 0.0, alpha), i * total / n)
         rows.append([start[0] + rho * (c * x - s * y), start[1] + rho * (s * x + c * y), start[2] + (h - alpha), 1.0])
     rows.append([goal[0], goal[1], goal[2], 1.0])
-    return np.array(rows), L, word
+    return np.array(rows), L
+
+
+def feasible_words(start, goal, rho):
+    """({word: (t, p, q)}, psi, alpha) of a pose pair; an empty dict: the same pose"""
+    dx, dy = goal[0] - start[0], goal[1] - start[1]
+    D, psi = math.hypot(dx, dy), math.atan2(dy, dx)
+    alpha, beta = mod2pi(start[2] - psi), mod2pi(goal[2] - psi)
+    if D == 0.0 and alpha == beta:
+        return {}, psi, alpha
+    return words(alpha, beta, D / rho), psi, alpha
+
+
+def curve_of_word(word, start, goal, interval, rho):
+    """(rows [n + 1, 4], L) of the Dubins curve along ONE named word, sampled as `curve` samples the shortest; None where the
+    word is infeasible (or the poses are the same, where there is no word)"""
+    start, goal = [float(v) for v in start], [float(v) for v in goal]
+    every, psi, alpha = feasible_words(start, goal, rho)
+    if word not in every:
+        return None
+    return word_rows(word, every[word], psi, alpha, start, goal, interval, rho)
+
+
+def tied_words(start, goal, rho, rel=1e-9):
+    """the feasible words whose t + p + q is within `rel` (relative) of the shortest's, in the order of WORDS: one word where
+    the choice is decided, several where the last bits of sincos / atan2 / acos decide it; none for the same pose"""
+    every, _, _ = feasible_words([float(v) for v in start], [float(v) for v in goal], rho)
+    if not every:
+        return []
+    best = min(sum(seg) for seg in every.values())
+    return [w for w, seg in every.items() if sum(seg) <= best * (1.0 + rel)]
 
 
 # ---------------------------------------------------------------------------------------------------- shared by the tests
@@ -157,11 +193,13 @@ def host_curve(lib, style, s, g, itv, rho):
     return rows
 
 
-def assert_rows_match(rows, want, what):
+def assert_rows_match(rows, want, what, scale=None):
     """the comparison the GPU tests share: equal counts, x / y within 64 ulp of the largest coordinate magnitude, theta within
-    1e-12 rad (the curves are a dozen operations of a few ulp each), gear exactly 1"""
+    1e-12 rad (the curves are a dozen operations of a few ulp each), gear exactly 1.  `scale`: the magnitude whose ulp is the
+    yardstick instead (a long curve of a large radius: the arc carry's error grows with rho (t + p + q), not with the
+    coordinates)"""
     assert rows.shape == want.shape, (what, rows.shape, want.shape)
-    tol = 64 * np.spacing(np.abs(want[:, :2]).max())
+    tol = 64 * np.spacing(np.abs(want[:, :2]).max() if scale is None else float(scale))
     assert np.abs(rows[:, :2] - want[:, :2]).max() <= tol, (what, np.abs(rows[:, :2] - want[:, :2]).max(), tol)
     assert np.abs(rows[:, 2] - want[:, 2]).max() <= 1e-12, (what, np.abs(rows[:, 2] - want[:, 2]).max())
     assert (rows[:, 3] == 1.0).all()
