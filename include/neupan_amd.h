@@ -779,7 +779,31 @@ int npa_route_relax(const uint8_t *blocked, int nx, int ny, int n_fields, uint32
  *   log_goal as npa_cycle_retask.
  * NPA_E_ARG (before anything touches a device): a null required pointer; batch, capacity or g_stride < 1; nx or ny < 1;
  *   n_fields outside 1 .. 65535; a resolution that is not finite and > 0, an x0 or y0 that is not finite; receding outside
- *   [1, NPA_MAX_T]; cycle < 0.  NPA_E_UNSUPPORTED: nx ny > NPA_ROUTE_MAX_CELLS. */
+ *   [1, NPA_MAX_T]; cycle < 0.  NPA_E_UNSUPPORTED: nx ny > NPA_ROUTE_MAX_CELLS.
+ *
+ * Line-of-sight shortcutting: npa_route_curve_batch_los and npa_cycle_retask_routed_los.  The argument lists, refusals,
+ *   statuses and counts of the exports they stand beside, the same kernel (a launch argument), and every rule above but the
+ *   way-points: those of the chain are CANDIDATES, and a candidate the anchor sees is left out.  tests/route_los_ref.py restates
+ *   it.
+ * Visibility of two cells a = (i0, j0), b = (i1, j1) inside the array: no cell whose closed box meets the closed segment
+ *   between the two cell centres holds NPA_ROUTE_BLOCKED (NPA_ROUTE_UNREACHED does not block).  Those cells in integers: dx =
+ *   i1 - i0, dy = j1 - j0, the axes' roles swapped if |dy| > |dx|; ax = |dx|, ay = |dy|, sx, sy the signs.  Column c = 0 .. ax
+ *   of the major axis holds the minor offsets m = max(lo, 0) .. min(hi, ay) with
+ *       lo = ceil(((2c - 1) ay - ax) / (2 ax)),   hi = floor(((2c + 1) ay + ax) / (2 ax))
+ *   (ax == 0: the one cell), the cell (i0 + sx c, j0 + sy m) or its transpose when swapped; every product is below 2^29
+ *   because nx ny <= NPA_ROUTE_MAX_CELLS.  32-bit integers, no math library.  A segment through a cell corner takes both cells
+ *   beside the corner -- the diagonal rule of the fields --, so a straight run of a chain is always visible; the relation is
+ *   symmetric in a and b.  Lane l takes columns l, l + 64, ... and loads its two or three cells; one ballot decides.
+ * Shortcutting: the candidates are the way-points above in their order -- the cell of every turn of the chain, then the
+ *   goal's cell.  The anchor is the start (its cell stands for it in the test).  While the candidate's cell is visible from
+ *   the anchor's cell it is remembered as `last`.  At the first candidate that is not visible the segment anchor -> `last` is
+ *   emitted, `last` becomes the anchor and the candidate becomes `last` (the chain's next turn after the new anchor: a straight
+ *   run, visible).  At the goal: anchor -> `last` if the goal's cell is not visible, then the segment to the goal's own (x, y).
+ *   Segment points are the start's (x, y), cell centres and the goal's (x, y); rows, skipped segments, h, "nothing is written
+ *   unless the whole path fits", the two passes, no route and no curve are as above.  No list of turns is kept: anchor and
+ *   `last` are two cells.
+ * Only cell CENTRES are tested: the start and the goal lie up to half a cell off theirs, and a segment clears the inflated
+ *   cells, not a swept disc -- the radius the caller inflated the map by must carry both (half a cell's diagonal more). */
 int npa_route_curve_batch(int batch, const uint32_t *fields, int n_fields, int nx, int ny, double x0, double y0,
                           double resolution, const int32_t *field_of, const double *start, const double *goal,
                           const double *interval, int capacity, const int32_t *mask, double *rows_out, int32_t *n_rows,
@@ -791,6 +815,17 @@ int npa_cycle_retask_routed(int batch, int receding, int cycle, const double *st
                             int32_t *cur_off, int32_t *cur_len, int32_t *point_index, float *cur_vel,
                             int32_t *retask_status, int32_t *log_goal, const uint32_t *fields, int n_fields, int nx,
                             int ny, double x0, double y0, double resolution, const int32_t *field_of, void *stream);
+int npa_route_curve_batch_los(int batch, const uint32_t *fields, int n_fields, int nx, int ny, double x0, double y0,
+                              double resolution, const int32_t *field_of, const double *start, const double *goal,
+                              const double *interval, int capacity, const int32_t *mask, double *rows_out, int32_t *n_rows,
+                              void *stream);
+int npa_cycle_retask_routed_los(int batch, int receding, int cycle, const double *state, int32_t *arrived,
+                                const int32_t *collided, double *path, const int32_t *curve_off, int32_t *curve_len,
+                                const int32_t *robot_first, const int32_t *row_capacity, const double *goals, int g_stride,
+                                const int32_t *n_goals, int32_t *goal_index, const double *interval, int32_t *curve_index,
+                                int32_t *cur_off, int32_t *cur_len, int32_t *point_index, float *cur_vel,
+                                int32_t *retask_status, int32_t *log_goal, const uint32_t *fields, int n_fields, int nx,
+                                int ny, double x0, double y0, double resolution, const int32_t *field_of, void *stream);
 
 /* ---- the bookkeeping of a device-resident closed loop (csrc/cycle.hip) -----------------------------------------------
  *

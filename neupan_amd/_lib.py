@@ -110,6 +110,9 @@ SYMBOLS = {
     "npa_route_curve_batch": (_I, [_I, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "npa_cycle_retask_routed": (_I, [_I, _I, _I] + [_P] * 9 + [_I] + [_P] * 10 + [_P, _I, _I, _I, C.c_double, C.c_double, C.c_double,
                                                                                  _P, _P]),
+    "npa_route_curve_batch_los": (_I, [_I, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "npa_cycle_retask_routed_los": (_I, [_I, _I, _I] + [_P] * 9 + [_I] + [_P] * 10 + [_P, _I, _I, _I, C.c_double, C.c_double,
+                                                                                     C.c_double, _P, _P]),
     "npa_lon_loss": (_I, [_I, _I, _I] + [_P] * 7 + [C.c_float, C.c_double, _I, C.c_float, C.c_float] + [_P] * 11 + [_P]),
     "npa_lon_chain": (_I, [_I, _I, _I] + [_P] * 8 + [_P]),
     "npa_lon_adam": (_I, [_I, _I, _I] + [_P] * 6 + [C.c_float] * 7 + [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P]),

@@ -5,7 +5,8 @@
 //   npa_route_relax                      the goal fields of a map (the header's "goal fields" block): the checks and the launches
 //                                        of route_sweep_kernel (cycle.hip)
 //   npa_route_curve_batch,               routed curves (the header's block of that name): the checks and the launch of
-//   npa_cycle_retask_routed              route_wave_kernel (cycle.hip), B plain paths or the re-task of a cycle
+//   npa_cycle_retask_routed              route_wave_kernel (cycle.hip), B plain paths or the re-task of a cycle; each with a
+//                                        `_los` form that shortcuts the way-points by line of sight
 // The curve itself is curves.h, compiled for both sides.
 #include "curves.h"
 
@@ -92,7 +93,7 @@ extern "C" int npa_route_relax(const uint8_t* blocked, int nx, int ny, int n_fie
   return NPA_OK;
 }
 
-// The routed curves of include/neupan_amd.h: both exports check and launch route_wave_kernel (cycle.hip).  `sound`: the
+// The routed curves of include/neupan_amd.h: all four exports check and launch route_wave_kernel (cycle.hip).  `sound`: the
 // caller's own test (its pointers, batch, capacity / g_stride, receding, cycle); the fields and the frame are tested here.
 namespace {
 __attribute__((noinline, minsize)) int route_wave_call(const char* who, bool sound, int batch, const RouteFrame& m, const int* field_of,
@@ -115,27 +116,63 @@ __attribute__((noinline, minsize)) int route_wave_call(const char* who, bool sou
 }
 }  // namespace
 
-extern "C" int npa_route_curve_batch(int batch, const uint32_t* fields, int n_fields, int nx, int ny, double x0, double y0,
-                                     double resolution, const int32_t* field_of, const double* start, const double* goal,
-                                     const double* interval, int capacity, const int32_t* mask, double* rows_out, int32_t* n_rows,
-                                     void* stream) {
+// each export beside its `_los` form (line-of-sight shortcutting: RouteFrame::shortcut): one body, two thunks
+namespace {
+__attribute__((noinline, minsize)) int route_batch_call(const char* who, int shortcut, int batch, const uint32_t* fields, int n_fields, int nx,
+                                                        int ny, double x0, double y0, double resolution, const int32_t* field_of,
+                                                        const double* start, const double* goal, const double* interval, int capacity,
+                                                        const int32_t* mask, double* rows_out, int32_t* n_rows, void* stream) {
   const bool sound = batch >= 1 && capacity >= 1 && start && goal && interval && rows_out && n_rows;
-  return route_wave_call("npa_route_curve_batch", sound, batch, {fields, n_fields, nx, ny, x0, y0, resolution}, field_of, start, goal,
-                         interval, capacity, mask, rows_out, n_rows, nullptr, stream);
+  return route_wave_call(who, sound, batch, {fields, n_fields, nx, ny, x0, y0, resolution, shortcut}, field_of, start, goal, interval,
+                         capacity, mask, rows_out, n_rows, nullptr, stream);
 }
 
-extern "C" int npa_cycle_retask_routed(int batch, int receding, int cycle, const double* state, int32_t* arrived,
-                                       const int32_t* collided, double* path, const int32_t* curve_off, int32_t* curve_len,
-                                       const int32_t* robot_first, const int32_t* row_capacity, const double* goals, int g_stride,
-                                       const int32_t* n_goals, int32_t* goal_index, const double* interval, int32_t* curve_index,
-                                       int32_t* cur_off, int32_t* cur_len, int32_t* point_index, float* cur_vel,
-                                       int32_t* retask_status, int32_t* log_goal, const uint32_t* fields, int n_fields, int nx,
-                                       int ny, double x0, double y0, double resolution, const int32_t* field_of, void* stream) {
+__attribute__((noinline, minsize)) int route_retask_call(const char* who, int shortcut, int batch, int receding, int cycle, const double* state,
+                                                         int32_t* arrived, const int32_t* collided, double* path, const int32_t* curve_off,
+                                                         int32_t* curve_len, const int32_t* robot_first, const int32_t* row_capacity,
+                                                         const double* goals, int g_stride, const int32_t* n_goals, int32_t* goal_index,
+                                                         const double* interval, int32_t* curve_index, int32_t* cur_off, int32_t* cur_len,
+                                                         int32_t* point_index, float* cur_vel, int32_t* retask_status, int32_t* log_goal,
+                                                         const uint32_t* fields, int n_fields, int nx, int ny, double x0, double y0,
+                                                         double resolution, const int32_t* field_of, void* stream) {
   const bool sound = batch >= 1 && cycle >= 0 && g_stride >= 1 && receding >= 1 && receding <= NPA_MAX_T && state && arrived &&
                      collided && path && curve_off && curve_len && robot_first && row_capacity && goals && n_goals && goal_index &&
                      interval && curve_index && cur_off && cur_len && point_index && cur_vel && retask_status;
   const RetaskTable t = {receding, cycle, g_stride, arrived, collided, curve_off, robot_first, row_capacity, n_goals, curve_len,
                          goal_index, curve_index, cur_off, cur_len, point_index, cur_vel, log_goal};
-  return route_wave_call("npa_cycle_retask_routed", sound, batch, {fields, n_fields, nx, ny, x0, y0, resolution}, field_of, state, goals,
-                         interval, 0, nullptr, path, retask_status, &t, stream);
+  return route_wave_call(who, sound, batch, {fields, n_fields, nx, ny, x0, y0, resolution, shortcut}, field_of, state, goals, interval, 0,
+                         nullptr, path, retask_status, &t, stream);
 }
+}  // namespace
+
+#define NPA_ROUTE_BATCH_ARGS                                                                                                      \
+  int batch, const uint32_t *fields, int n_fields, int nx, int ny, double x0, double y0, double resolution, const int32_t *field_of, \
+      const double *start, const double *goal, const double *interval, int capacity, const int32_t *mask, double *rows_out,         \
+      int32_t *n_rows, void *stream
+#define NPA_ROUTE_BATCH_PASS \
+  batch, fields, n_fields, nx, ny, x0, y0, resolution, field_of, start, goal, interval, capacity, mask, rows_out, n_rows, stream
+extern "C" int npa_route_curve_batch(NPA_ROUTE_BATCH_ARGS) { return route_batch_call("npa_route_curve_batch", 0, NPA_ROUTE_BATCH_PASS); }
+extern "C" int npa_route_curve_batch_los(NPA_ROUTE_BATCH_ARGS) {
+  return route_batch_call("npa_route_curve_batch_los", 1, NPA_ROUTE_BATCH_PASS);
+}
+
+#define NPA_ROUTE_RETASK_ARGS                                                                                                       \
+  int batch, int receding, int cycle, const double *state, int32_t *arrived, const int32_t *collided, double *path,                  \
+      const int32_t *curve_off, int32_t *curve_len, const int32_t *robot_first, const int32_t *row_capacity, const double *goals,    \
+      int g_stride, const int32_t *n_goals, int32_t *goal_index, const double *interval, int32_t *curve_index, int32_t *cur_off,     \
+      int32_t *cur_len, int32_t *point_index, float *cur_vel, int32_t *retask_status, int32_t *log_goal, const uint32_t *fields,     \
+      int n_fields, int nx, int ny, double x0, double y0, double resolution, const int32_t *field_of, void *stream
+#define NPA_ROUTE_RETASK_PASS                                                                                                       \
+  batch, receding, cycle, state, arrived, collided, path, curve_off, curve_len, robot_first, row_capacity, goals, g_stride, n_goals, \
+      goal_index, interval, curve_index, cur_off, cur_len, point_index, cur_vel, retask_status, log_goal, fields, n_fields, nx, ny,  \
+      x0, y0, resolution, field_of, stream
+extern "C" int npa_cycle_retask_routed(NPA_ROUTE_RETASK_ARGS) {
+  return route_retask_call("npa_cycle_retask_routed", 0, NPA_ROUTE_RETASK_PASS);
+}
+extern "C" int npa_cycle_retask_routed_los(NPA_ROUTE_RETASK_ARGS) {
+  return route_retask_call("npa_cycle_retask_routed_los", 1, NPA_ROUTE_RETASK_PASS);
+}
+#undef NPA_ROUTE_BATCH_ARGS
+#undef NPA_ROUTE_BATCH_PASS
+#undef NPA_ROUTE_RETASK_ARGS
+#undef NPA_ROUTE_RETASK_PASS

@@ -183,9 +183,9 @@ __global__ __launch_bounds__(npa_curve::kWave) void curve_wave_kernel(CurveWaveA
 
 // The arguments of route_wave_kernel, one struct as CurveWaveArgs and in its order; what differs: no style and no radius, the
 // fields and the map's frame, field_of [B][g_stride] beside the goals.  retask == 0: npa_route_curve_batch, != 0:
-// npa_cycle_retask_routed.
+// npa_cycle_retask_routed.  shortcut != 0: their `_los` forms (the header's "line-of-sight shortcutting").
 struct RouteWaveArgs {
-  int retask, batch, T, cycle, g_stride, capacity, nx, ny, n_fields;
+  int retask, batch, T, cycle, g_stride, capacity, nx, ny, n_fields, shortcut;
   const int *mask, *collided, *n_goals, *robot_first, *curve_off, *row_capacity, *field_of;
   int *goal_index, *arrived, *log_goal;
   const uint32_t* fields;
@@ -204,11 +204,52 @@ __device__ __forceinline__ int move_di(int k) { return k < 4 ? (k == 0 ? 1 : (k 
 __device__ __forceinline__ int move_dj(int k) { return k < 4 ? (k == 2 ? 1 : (k == 3 ? -1 : 0)) : (k < 6 ? 1 : -1); }
 __device__ __forceinline__ uint32_t move_cost(int k) { return k < 4 ? 5u : 7u; }
 
+// The header's "visibility" of cells (i0, j0) and (i1, j1), both inside the array, across the wave: lane l takes columns l,
+// l + 64, ... of the major axis and loads the two or three cells the segment between the centres meets there; ONE ballot of
+// "a cell of mine is BLOCKED" decides, so the answer is the whole wave's.  32-bit integers only.  With N = (2c - 1) ay + ax
+// (>= ax - ay >= 0) and d = 2 ax: the header's lo = ceil(N / d) - 1 and hi = floor((N + 2 ay) / d) = q + (r + 2 ay >= d), since
+// r + 2 ay < 2 d -- one unsigned division per column.  ax == 0 (one cell): d = 1 gives lo = hi = 0.
+__device__ __forceinline__ bool route_visible(const uint32_t* field, int nx, int i0, int j0, int i1, int j1, int lane) {
+  const int di = i1 - i0, dj = j1 - j0, adi = di < 0 ? -di : di, adj = dj < 0 ? -dj : dj;
+  const bool swap = adj > adi;
+  const int ax = swap ? adj : adi, ay = swap ? adi : adj;
+  const int si = (di > 0) - (di < 0), sj = ((dj > 0) - (dj < 0)) * nx;       // a step along x, along y, in words of the field
+  const int major = swap ? sj : si, minor = swap ? si : sj;
+  const uint32_t d = ax ? 2u * (uint32_t)ax : 1u;
+  const int base = j0 * nx + i0;                                              // (nx ny <= NPA_ROUTE_MAX_CELLS: every product below 2^29)
+  bool hit = false;
+#pragma nounroll
+  for (int c0 = 0; c0 <= ax; c0 += npa_curve::kWave) {
+    const int c = c0 + lane;
+    if (c <= ax) {
+      const uint32_t n = (uint32_t)((2 * c - 1) * ay + ax);
+      const uint32_t q = n / d, r = n - q * d;
+      int lo = (int)q - 1 + (r != 0u ? 1 : 0), hi = (int)q + (r + 2u * (uint32_t)ay >= d ? 1 : 0);
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > ay ? ay : hi;
+      for (int m = lo; m <= hi; ++m) hit |= field[base + c * major + m * minor] == NPA_ROUTE_BLOCKED;
+    }
+  }
+  return __ballot(hit) == 0;
+}
+
+// lane l's double of a vector register as a wave-uniform value (two readlanes): how route_wave keeps the uniform doubles it
+// needs rarely -- the two poses, the interval -- out of the scalar registers, which the walk, the visibility test and the curve need
+__device__ __forceinline__ double lane_double(double v, int l) {
+  const long long w = __double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)w, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(w >> 32), l);
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // One wave, one routed path (include/neupan_amd.h, "routed curves"): the chain from the start's cell down field f, a `line`
 // curve between the way-points.  Everything the walk decides is the whole wave's: the cell, its value and the move are the same
 // in every lane (the move is the lowest bit of a ballot), so the loops are uniform and only the row stores are per lane.  The
 // walk runs twice, counting and then writing, in ONE loop body: nothing is kept between the passes but the row count.  Returns
 // the rows of the path (written iff <= capacity), RW_NO_ROUTE or RW_NO_CURVE (a segment outside the curve specification).
+// a.shortcut: a way-point is a candidate -- while it is visible from the anchor's cell (route_visible) it is only remembered as
+// `last`; the first that is not emits the segment to `last`, which becomes the anchor; the goal emits to `last` if it is not
+// visible and then to itself.  Anchor and `last` are four wave-uniform integers: no list of turns.  Without it every
+// candidate is the one emit to itself, with the operations and so the bits this loop had before it knew of shortcuts.
 __device__ __forceinline__ int route_wave(const RouteWaveArgs& a, int f, const double* start, const double* goal, double interval,
                                           int capacity, double* rows, int lane) {
 #pragma clang fp contract(off)
@@ -225,17 +266,22 @@ __device__ __forceinline__ int route_wave(const RouteWaveArgs& a, int f, const d
   const uint32_t cost = move_cost(k);
   const int side_i = k < 4 ? k : (k & 1), side_j = k < 4 ? k : (k < 6 ? 2 : 3);
   long long count = 0;
+  // lane_double's lanes 0 .. 5: sx, sy, gx, gy, gth, the interval
+  const double keep = lane == 0 ? sx : (lane == 1 ? sy : (lane == 2 ? gx : (lane == 3 ? gy : (lane == 4 ? gth : interval))));
   double h = gth;
 #pragma nounroll
   for (int pass = 0; pass < 2; ++pass) {
     int i = i0, j = j0, prev = -1;
+    // the anchor's cell and `last` (shortcut), four wave-uniform integers held in ONE vector register -- lanes 0 .. 3 hold ai, aj,
+    // li, lj -- because the walk has no scalar registers to spare.  (The first candidate ends a straight run from the start's
+    // cell: it is visible, so `last` is set before it is read.)
+    int cells = (lane & 1) ? j0 : i0;
     uint32_t v = v0;
-    double wx = sx, wy = sy;                                   // the way-point behind the walk
+    double wx = lane_double(keep, 0), wy = lane_double(keep, 1);                // the way-point behind the walk
     count = 0;
-    h = gth;
+    h = lane_double(keep, 4);
     for (;;) {
       int move = -1;
-      double tx = gx, ty = gy;
       if (v != 0) {
         const int ni = i + di, nj = j + dj;
         uint32_t nv = NPA_ROUTE_BLOCKED;
@@ -246,26 +292,42 @@ __device__ __forceinline__ int route_wave(const RouteWaveArgs& a, int f, const d
         const unsigned long long allowed = __ballot(ok);
         if (allowed == 0) return RW_NO_ROUTE;                  // (not a converged field)
         move = __builtin_ctzll(allowed);
-        tx = a.x0 + ((double)i + 0.5) * a.res;                 // route.centres_of
-        ty = a.y0 + ((double)j + 0.5) * a.res;
       }
       if (v == 0 || (prev >= 0 && move != prev)) {             // a way-point: the goal, or a cell at which the chain turns
-        if (!(wx == tx && wy == ty)) {
-          const double from[3] = {wx, wy, 0.0}, to[3] = {tx, ty, 0.0};
-          npa_curve::Curve c;
-          npa_curve::curve_plan(NPA_CURVE_LINE, from, to, interval, 0.0, c);
-          if (c.rows < 1) return RW_NO_CURVE;
-          if (pass)
-            for (int r = lane; r < c.n; r += npa_curve::kWave) {          // (the segment's goal row is the next one's first)
-              double o[4];
-              npa_curve::curve_row(c, r, o);
-              double* out = rows + (size_t)(count + r) * 4;
-              out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
-            }
-          count += c.n;
-          h = c.psi;
+        const bool cut = a.shortcut && !route_visible(field, a.nx, __builtin_amdgcn_readlane(cells, 0),
+                                                      __builtin_amdgcn_readlane(cells, 1), i, j, lane);
+#pragma nounroll
+        for (int e = cut ? 0 : 1; e < 2; ++e) {                // e == 0: the emit to `last`; e == 1: to the way-point itself
+          if (e && a.shortcut && v != 0) break;                // (a visible turn, or one that `last` was emitted for: remembered)
+          int ci = i, cj = j;
+          if (!e) {                                            // `last` becomes the anchor
+            ci = __builtin_amdgcn_readlane(cells, 2);
+            cj = __builtin_amdgcn_readlane(cells, 3);
+            cells = lane == 0 ? ci : (lane == 1 ? cj : cells);
+          }
+          double px = lane_double(keep, 2), py = lane_double(keep, 3);      // the goal's own point, or a cell's centre
+          if (!e || v != 0) {
+            px = a.x0 + ((double)ci + 0.5) * a.res;            // route.centres_of
+            py = a.y0 + ((double)cj + 0.5) * a.res;
+          }
+          if (!(wx == px && wy == py)) {
+            const double from[3] = {wx, wy, 0.0}, to[3] = {px, py, 0.0};
+            npa_curve::Curve c;
+            npa_curve::curve_plan(NPA_CURVE_LINE, from, to, lane_double(keep, 5), 0.0, c);
+            if (c.rows < 1) return RW_NO_CURVE;
+            if (pass)
+              for (int r = lane; r < c.n; r += npa_curve::kWave) {          // (the segment's goal row is the next one's first)
+                double o[4];
+                npa_curve::curve_row(c, r, o);
+                double* out = rows + (size_t)(count + r) * 4;
+                out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
+              }
+            count += c.n;
+            h = c.psi;
+          }
+          wx = px; wy = py;
         }
-        wx = tx; wy = ty;
+        cells = lane == 2 ? i : (lane == 3 ? j : cells);
       }
       if (v == 0) break;
       i += move_di(move); j += move_dj(move);
@@ -277,7 +339,7 @@ __device__ __forceinline__ int route_wave(const RouteWaveArgs& a, int f, const d
   }
   if (lane == 0) {
     double* out = rows + (size_t)count * 4;
-    out[0] = gx; out[1] = gy; out[2] = h; out[3] = 1.0;
+    out[0] = lane_double(keep, 2); out[1] = lane_double(keep, 3); out[2] = h; out[3] = 1.0;
   }
   return (int)(count + 1);
 }
@@ -432,6 +494,7 @@ hipError_t npa_launch_route_wave(int batch, const RouteFrame& m, const int* fiel
                                  const RetaskTable* t, hipStream_t stream) {
   RouteWaveArgs a = {};
   a.batch = batch; a.T = 1; a.g_stride = 1; a.capacity = capacity; a.nx = m.nx; a.ny = m.ny; a.n_fields = m.n_fields;
+  a.shortcut = m.shortcut;
   a.mask = mask; a.field_of = field_of; a.fields = m.fields; a.x0 = m.x0; a.y0 = m.y0; a.res = m.resolution;
   a.start = start; a.goals = goals; a.interval = interval; a.rows = rows; a.n_rows = n_rows;
   if (t) {

@@ -78,11 +78,12 @@ hipError_t npa_launch_cycle_retask(int batch, int T, int cycle, int style, doubl
 // route_wave_kernel (the header's "routed curves"): the fields with the map's frame, and -- for the re-task alone -- the arguments
 // of npa_cycle_retask that are not the curve's, by name.  t == nullptr: npa_route_curve_batch (start, goals [B][3], one
 // capacity, mask, rows [B][capacity][4], n_rows); else npa_cycle_retask_routed (start = the state, goals [B][g_stride][3], rows =
-// the curve table, n_rows = the retask_status; capacity and mask are not read).
+// the curve table, n_rows = the retask_status; capacity and mask are not read).  shortcut: 1 from the `_los` exports, else 0.
 struct RouteFrame {
   const uint32_t* fields;
   int n_fields, nx, ny;
   double x0, y0, resolution;
+  int shortcut;
 };
 struct RetaskTable {
   int T, cycle, g_stride;

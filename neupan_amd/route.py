@@ -16,9 +16,19 @@ rows in one launch, one wave per robot, and `ResidentLoop(goals=..., route=...)`
 re-task through it (npa_cycle_retask_routed; world.py).  The fields of a loop's goals stay on the device for the loop's
 lifetime: G ny nx 4 bytes for G distinct goal cells (goals in one cell share a field).
 
-Out of scope: line-of-sight shortcutting of a chain (a path keeps the eight directions of the grid); routed legs of any style
-but `line` (Dubins, Reeds-Shepp); routed goals in `LonLoop` / `train_closed_loop` and in the single-robot `neupan` class;
-agents that plan (the world's agents keep their reactive behaviours).
+Line-of-sight shortcutting (`shortcut=True` of `route_paths`, `route_batch` and the loops' `route=`; `waypoints(blocked=...)`):
+a chain keeps the eight directions of the grid, so its way-points are a staircase of 45-degree turns.  With shortcutting the
+turns and the goal are only CANDIDATES: walking them in order, a candidate whose cell the anchor's cell sees (`visible`: no
+blocked cell's closed box meets the closed segment between the two cell centres -- exact, in integers) is left out; the first
+that is not seen makes the one before it a way-point and the new anchor (include/neupan_amd.h, "routed curves", has the rule;
+npa_route_curve_batch_los and npa_cycle_retask_routed_los are the device's form of it, in the same kernel).  Only cell CENTRES
+are tested: the start and the goal lie up to half a cell off theirs, and a segment is not a swept disc, so `radius` must carry
+that -- half a cell's diagonal beyond the robot's.  Dubins arcs between shortcut way-points (`route_paths(curve_style="dubins",
+shortcut=True)`) are not checked against the map, as they were not between the chain's turns.  Every default is off.
+
+Out of scope: shortcutting between arbitrary chain cells (only turns and the goal are candidates) and an optimal (Theta*) path;
+routed legs of any style but `line` (Dubins, Reeds-Shepp); routed goals in `LonLoop` / `train_closed_loop` and in the
+single-robot `neupan` class; agents that plan (the world's agents keep their reactive behaviours).
 """
 from __future__ import annotations
 
@@ -97,7 +107,9 @@ class GoalFields:
     fields  [G, ny, nx] uint32: the field of goal g; NPA_ROUTE_BLOCKED in blocked cells, NPA_ROUTE_UNREACHED where no path leads
     blocked [ny, nx] uint8: the inflated map
     cells   [G, 2] int64 (host): the goals' cells
-    sweeps  the sweeps issued (a multiple of sweeps_per_call, capped at nx ny + 1; how many were NEEDED depends on timing)"""
+    sweeps  the sweeps issued (a multiple of sweeps_per_call, capped at nx ny + 1; how many were NEEDED depends on timing)
+    shortcut  False; the loops' `route=dict(shortcut=True)` sets it on their fields: their legs go through the `_los` exports"""
+    shortcut = False
 
     def __init__(self, grid, goals, radius, sweeps_per_call=64, seeds=None):
         self.grid = grid
@@ -224,18 +236,79 @@ def trace(fields, field_of, starts):
     return torch.stack(chain, dim=1), length
 
 
-def waypoints(grid, chain, length, starts, goals):
+def span_cells(a, b):
+    """the cells (i, j) whose closed box meets the closed segment between the centres of cells a and b, in exact integers
+    (include/neupan_amd.h, "routed curves": column c of the major axis holds the minor offsets max(lo, 0) .. min(hi, ay))"""
+    (i0, j0), (i1, j1) = (int(a[0]), int(a[1])), (int(b[0]), int(b[1]))
+    dx, dy = i1 - i0, j1 - j0
+    swap = abs(dy) > abs(dx)
+    if swap:
+        dx, dy = dy, dx
+    ax, ay, sx, sy = abs(dx), abs(dy), (dx > 0) - (dx < 0), (dy > 0) - (dy < 0)
+    out = []
+    for c in range(ax + 1):
+        lo, hi = (0, 0) if ax == 0 else (-((ax - (2 * c - 1) * ay) // (2 * ax)), ((2 * c + 1) * ay + ax) // (2 * ax))      # ceil, floor
+        for m in range(max(lo, 0), min(hi, ay) + 1):
+            out.append((i0 + sy * m, j0 + sx * c) if swap else (i0 + sx * c, j0 + sy * m))
+    return out
+
+
+def _blocking(blocked_or_field):
+    """bool [ny, nx] on the host: the cells that block a line of sight -- the non-zero cells of a uint8 / bool map (`inflate`,
+    `GoalFields.blocked`), the NPA_ROUTE_BLOCKED cells of a field (any other integer type; UNREACHED does not block)"""
+    m = blocked_or_field
+    if isinstance(m, torch.Tensor):
+        m = m.detach().cpu()
+        m = m.numpy() if m.dtype in (torch.uint8, torch.bool) else _values(_words(m)).numpy()
+    m = np.asarray(m)
+    if m.ndim != 2:
+        raise ValueError(f"visible: a map or ONE field [ny, nx], not {m.shape}")
+    return m != 0 if m.dtype in (np.uint8, np.bool_) else (m.astype(np.int64) & 0xFFFFFFFF) == BLOCKED
+
+
+def visible(blocked_or_field, a, b):
+    """True iff cell b = (i, j) is visible from cell a over the inflated map (uint8 [ny, nx]) or a field of it ([ny, nx]): no
+    cell of `span_cells(a, b)` is blocked.  Host, exact integers, symmetric in a and b.  ValueError: a cell outside the array."""
+    block = blocked_or_field if isinstance(blocked_or_field, np.ndarray) and blocked_or_field.dtype == np.bool_ else _blocking(blocked_or_field)
+    ny, nx = block.shape
+    for i, j in (a, b):
+        if not (0 <= i < nx and 0 <= j < ny):
+            raise ValueError(f"visible: cell ({i}, {j}) lies outside the {nx} x {ny} array")
+    return not any(block[j, i] for i, j in span_cells(a, b))
+
+
+def shortcut_cells(block, start_cell, candidates):
+    """The greedy walk of line-of-sight shortcutting: `candidates` are the cells of the chain's turns, then the goal's cell;
+    returns the cells that remain interior way-points.  While the anchor's cell (first the start's) sees the candidate it is
+    only remembered as `last`; the first that is not seen makes `last` a way-point and the anchor."""
+    keep, anchor, last = [], tuple(start_cell), None
+    for k, cand in enumerate(candidates):
+        cand = tuple(cand)
+        if not visible(block, anchor, cand):                     # (`last` is set: the first candidate ends a straight run)
+            keep.append(last)
+            anchor = last
+        if k < len(candidates) - 1:
+            last = cand
+    return keep
+
+
+def waypoints(grid, chain, length, starts, goals, blocked=None):
     """The way-points of B chains: per robot a list of (3, 1) poses -- the start pose, the centres of the cells at which its chain
     changes direction, the goal pose with the goal's own x, y and heading.  An interior way-point's heading is that of the
-    segment that leaves it.  starts, goals [B, 3] (x, y, theta)."""
+    segment that leaves it.  starts, goals [B, 3] (x, y, theta).  blocked (optional): the inflated map (`GoalFields.blocked`) or
+    a field -- the turns are then shortcut by line of sight (`shortcut_cells`; the module docstring says what is tested)."""
     ch, ln = chain.cpu().numpy(), length.cpu().numpy()
     s, g = np.asarray(starts, dtype=np.float64).reshape(-1, 3), np.asarray(goals, dtype=np.float64).reshape(-1, 3)
+    block = None if blocked is None else _blocking(blocked)
     out = []
     for b in range(ch.shape[0]):
         c = ch[b, :ln[b]]
         d = np.diff(c, axis=0)
         turn = 1 + np.nonzero((d[1:] != d[:-1]).any(axis=1))[0] if len(d) > 1 else np.zeros(0, dtype=np.int64)
-        pts = [s[b, :2]] + list(centres_of(grid, c[turn])) + [g[b, :2]]
+        mid = c[turn]
+        if block is not None:
+            mid = np.asarray(shortcut_cells(block, c[0], [tuple(x) for x in mid.tolist()] + [tuple(c[-1].tolist())]), dtype=np.int64).reshape(-1, 2)
+        pts = [s[b, :2]] + list(centres_of(grid, mid)) + [g[b, :2]]
         wp = []
         for k, p in enumerate(pts):
             if k == 0:
@@ -249,7 +322,7 @@ def waypoints(grid, chain, length, starts, goals):
     return out
 
 
-def route_batch(fields, field_of, starts, goals, interval, capacity, mask=None, out=None, n_rows=None):
+def route_batch(fields, field_of, starts, goals, interval, capacity, mask=None, out=None, n_rows=None, shortcut=False):
     """B routed paths on the device, one launch (npa_route_curve_batch: include/neupan_amd.h, "routed curves"): per robot the
     chain of `trace` from the start's cell, the positions of `waypoints` and the rows of planner.generate_curve("line") between
     them, without the host.  fields: a `GoalFields` (its map's frame is the frame); field_of [B]: the field of robot b's goal;
@@ -258,7 +331,8 @@ def route_batch(fields, field_of, starts, goals, interval, capacity, mask=None, 
     into (default: new, zero-filled; anything else is a ValueError).  With device tensors of these types for every argument the
     call converts nothing and reads nothing back: it is the launch.  Returns (rows, n_rows) device tensors, like `curves.generate_batch`: n_rows[b] > 0 rows of
     path b are valid; -needed: it did not fit and nothing was written (-2^31: a segment outside the curve specification); 0: no
-    route (field_of outside the fields, a start outside the map, in a blocked cell or in a cell no path leads out of)."""
+    route (field_of outside the fields, a start outside the map, in a blocked cell or in a cell no path leads out of).
+    shortcut=True: npa_route_curve_batch_los -- the same launch with the way-points shortcut by line of sight over the field."""
     lib = _lib.load()
     dev = fields.fields.device
     G, ny, nx = fields.fields.shape
@@ -291,18 +365,20 @@ def route_batch(fields, field_of, starts, goals, interval, capacity, mask=None, 
     x0, y0 = (float(v) for v in fields.grid.origin)
     with torch.cuda.device(dev):
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib.npa_route_curve_batch(B, ptr(fields.fields), G, nx, ny, x0, y0, float(fields.grid.resolution), ptr(fo), ptr(s), ptr(g),
-                                        ptr(itv), capacity, ptr(m), ptr(out), ptr(n_rows), stream), "npa_route_curve_batch")
+        name = "npa_route_curve_batch_los" if shortcut else "npa_route_curve_batch"
+        check(getattr(lib, name)(B, ptr(fields.fields), G, nx, ny, x0, y0, float(fields.grid.resolution), ptr(fo), ptr(s), ptr(g),
+                                 ptr(itv), capacity, ptr(m), ptr(out), ptr(n_rows), stream), name)
     return out, n_rows
 
 
-def route_paths(grid, starts, goals, radius, interval, curve_style="line", min_radius=None, sweeps_per_call=64):
+def route_paths(grid, starts, goals, radius, interval, curve_style="line", min_radius=None, sweeps_per_call=64, shortcut=False):
     """One initial path per robot through the map, in the form `FleetPlanner.set_paths` takes (a list of (4, 1) points x, y,
     theta, gear): the goal's field (equal goals share one), the chain from the robot's cell, its way-points, and between them
     `planner.generate_curve` of `curve_style` ('line', or 'dubins' with min_radius) at `interval` [m].  starts [B, 3];
     goals [B, 2 | 3]: one goal per robot (a missing heading is 0); radius [m]: the clearance the route keeps from occupied
-    cells, at least the robot's radius.  ValueError: what `GoalFields` and `trace` raise.  See the module docstring for what is
-    out of scope."""
+    cells, at least the robot's radius.  shortcut=True: the way-points are shortcut by line of sight over the inflated map
+    (`waypoints(blocked=...)`), for either style.  ValueError: what `GoalFields` and `trace` raise.  See the module docstring for
+    what is out of scope."""
     from .planner import _consistent_angles, generate_curve
     s = np.asarray(starts, dtype=np.float64).reshape(-1, 3)
     g = np.asarray(goals, dtype=np.float64)
@@ -315,7 +391,7 @@ def route_paths(grid, starts, goals, radius, interval, curve_style="line", min_r
     gf = GoalFields(grid, uniq, radius, sweeps_per_call)
     chain, length = trace(gf.fields, field_of.reshape(-1), cells_of(grid, s))
     paths = []
-    for wp in waypoints(grid, chain, length, s, g):
+    for wp in waypoints(grid, chain, length, s, g, gf.blocked if shortcut else None):
         path = generate_curve(curve_style, wp, interval, 0.0 if min_radius is None else min_radius)
         if curve_style == "line":
             _consistent_angles(path)

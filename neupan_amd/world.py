@@ -778,7 +778,7 @@ class _HostCycle:
 
 class _HostRetask:
     """The host-paced twin of npa_cycle_retask, behind `_HostCycle.cycle`: it reads the arrival and collision flags, takes the
-    new rows from npa_curve_batch (with `route=`: from npa_route_curve_batch, and a path that does not fit its robot's region is
+    new rows from npa_curve_batch (with `route=`: from npa_route_curve_batch or its `_los` form, and a path that does not fit its robot's region is
     status 2, no route status 3) -- the DEVICE generator: libm and the device math library differ in the last bits, and only
     the same code gives the two loops the same bits -- and hands them to `fleet.retask`.  Attributes as ResidentLoop's:
     goal_index, retask_status [B] (host int32), log [cycles, B] int32 (device)."""
@@ -811,7 +811,8 @@ class _HostRetask:
                 from .route import route_batch
                 fields, field_of = self.routed
                 rows, n_rows = route_batch(fields, field_of[np.arange(self.B), pick_h], loop.st, goal, self.interval,
-                                           self.rows.shape[1], mask=go.astype(np.int32), out=self.rows, n_rows=self.n_rows)
+                                           self.rows.shape[1], mask=go.astype(np.int32), out=self.rows, n_rows=self.n_rows,
+                                           shortcut=fields.shortcut)
             n_h = n_rows.cpu().numpy()
             loop.arrive = loop.arrive.clone()
             for b in np.nonzero(go)[0]:
@@ -895,7 +896,8 @@ def _goal_queues(goals, fleet, path_capacity, curve_style, min_radius):
 
 
 def _route_fields(route, world, goals, curve_style):
-    """`route=` of the loops: None, or dict(radius [m], sweeps_per_call=64).  Returns None, or (the `route.GoalFields` of the
+    """`route=` of the loops: None, or dict(radius [m], sweeps_per_call=64, shortcut=False).  shortcut: the legs' way-points are
+    shortcut by line of sight (the `_los` exports; route.py), the fields' attribute `shortcut`.  Returns None, or (the `route.GoalFields` of the
     distinct goal CELLS of all queues over the world's map inflated by `radius` -- a field is seeded in its goal's cell, so goals
     that share a cell share a field --, field_of [B, g_stride] int32 (host): the field of goals[b][k]; 0 where a queue is
     shorter).  ValueError: no goals, no map in the world, no radius, more than 65535 distinct goal cells, and what GoalFields
@@ -905,7 +907,7 @@ def _route_fields(route, world, goals, curve_style):
         return None
     if goals is None:
         raise ValueError("route: a routed loop needs goals (route= says how a goal queue's legs are made)")
-    if not isinstance(route, dict) or "radius" not in route or set(route) - {"radius", "sweeps_per_call"}:
+    if not isinstance(route, dict) or "radius" not in route or set(route) - {"radius", "sweeps_per_call", "shortcut"}:
         raise ValueError("route: dict(radius=..., sweeps_per_call=64)")
     if world.grid is None:
         raise ValueError("route: the world has no map (LidarWorld.set_map); without one the curves of goals= need no route")
@@ -928,7 +930,9 @@ def _route_fields(route, world, goals, curve_style):
     for b, q in enumerate(goals):
         for k in range(len(q)):
             field_of[b, k] = index[next(it)]
-    return GoalFields(world.grid, np.asarray(list(first.values())), float(route["radius"]), int(route.get("sweeps_per_call", 64))), field_of
+    fields = GoalFields(world.grid, np.asarray(list(first.values())), float(route["radius"]), int(route.get("sweeps_per_call", 64)))
+    fields.shortcut = bool(route.get("shortcut", False))             # (the loops' choice of export rides on the fields)
+    return fields, field_of
 
 
 def curve_table(curve_lists, capacity=None):
@@ -984,13 +988,14 @@ class ResidentLoop:
     then be a single curve.  Without goals the table and the launches are what they were; attributes goal_index, retask_status
     [B] int32 (None without goals), and `run` adds logs["goal"] [cycles, B] int32: the goals consumed after each cycle.
 
-    With `route` = dict(radius=..., sweeps_per_call=64) beside `goals` the legs lead through the world's map (it needs one:
+    With `route` = dict(radius=..., sweeps_per_call=64, shortcut=False) beside `goals` the legs lead through the world's map (it needs one:
     `set_map`; curve_style 'line'): the distinct goal cells of all queues get one cost-to-goal field each over the map
     inflated by `radius` [m] (`route.GoalFields`, made here, once: G ny nx 4 bytes on the device for G cells, attribute
     route_fields; a goal outside the map or in a blocked cell is its ValueError), and the launch is npa_cycle_retask_routed: the
     chain from the robot's cell down its goal's field, `line` curves between its turns (include/neupan_amd.h, "routed curves").
     retask_status 2: the path does not fit the robot's region; 3: no route from where the robot stands (outside the map, in an
     inflated cell, cut off); either leaves the robot arrived.  Without `route` nothing changes, neither launches nor buffers.
+    shortcut=True: the launch is npa_cycle_retask_routed_los -- turns the robot's cell sees past are left out of the leg (route.py).
 
     With `scan["noise"]` the scan slot holds npa_world_scan_noisy with draw = draw0 + cycles_done, a host scalar at issue time;
     the count runs on over runs (and over `LonLoop.reset`: episodes see different noise).  Without it the launch is npa_world_scan.
@@ -1248,9 +1253,10 @@ class ResidentLoop:
             check(rc, "npa_cycle_commit")
         if self._retask is not None:                     # (the goal log is a run's: `run` sets its address, `cycle` has none)
             if self._routed is not None:
-                rc = lib.npa_cycle_retask_routed(self.B, self.T, row, *self._retask[2:], self._log_goal, *self._routed, stream)
+                name = "npa_cycle_retask_routed_los" if self.route_fields.shortcut else "npa_cycle_retask_routed"
+                rc = getattr(lib, name)(self.B, self.T, row, *self._retask[2:], self._log_goal, *self._routed, stream)
                 if rc:
-                    check(rc, "npa_cycle_retask_routed")
+                    check(rc, name)
             else:
                 style, rho = self._retask[:2]
                 rc = lib.npa_cycle_retask(self.B, self.T, row, style, rho, *self._retask[2:], self._log_goal, stream)
