@@ -41,6 +41,7 @@ struct Knobs {
   // per handle, not part of the key
   bool sel_debug = false, qp_cold = false, qp_generic = false, skip_selftest = false, pack_cache = true;
   bool qp_order = true;            // NPA_QP_ORDER=0: the QP launches hand their scenes out in scene order
+  bool sel_first_tile = true;      // NPA_SEL_FIRST_TILE=0: candidate lists of 17-32 go to one 32-point tile, as before
   double audit_rate = 1.0 / 64.0;  // audit tiles: one slice wave in 64 (NPA_AUDIT_RATE in [0, 1]; 0 = candidates only)
   float margin_scale = 1.f;
 };
@@ -56,6 +57,7 @@ static Knobs read_knobs() {
   k.qp_cold = getenv("NPA_QP_COLD") != nullptr;
   k.qp_generic = getenv("NPA_QP_GENERIC") != nullptr;
   if (const char* env = getenv("NPA_QP_ORDER")) k.qp_order = atoi(env) != 0;
+  if (const char* env = getenv("NPA_SEL_FIRST_TILE")) k.sel_first_tile = atoi(env) != 0;
   k.skip_selftest = getenv("NPA_SKIP_SELFTEST") != nullptr;
   if (const char* env = getenv("NPA_PACK_CACHE")) k.pack_cache = atoi(env) != 0;
   if (const char* env = getenv("NPA_AUDIT_RATE")) { double v = atof(env); if (v >= 0.0 && v <= 1.0) k.audit_rate = v; }
@@ -479,6 +481,8 @@ static int create_handle(npa_handle* h, bool need_w, const npa_dune_weights* w) 
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) h->n_cu = prop.multiProcessorCount;
   if (int rc = acquire_pack(h, image, need_w, knobs)) return rc;
+  // (per handle, not part of the calibration record: handles of one pack may differ in it; merged launches compare DevParams)
+  if (h->P.geo_tab && knobs.sel_first_tile) h->P.geo_tab |= NPA_GEO_TAB_FIRST_TILE;
   if (need_w) {
     if (int rc = hip_status(alloc_handle_buffers(h))) return rc;
     h->audit_thresh = knobs.audit_rate >= 1.0 ? 0xFFFFFFFFu : (unsigned)(knobs.audit_rate * 4294967296.0);

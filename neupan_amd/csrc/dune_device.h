@@ -1266,7 +1266,9 @@ __device__ __forceinline__ unsigned key_pass(const DevParams& P, const SliceFram
 #define SEL_OPAQUE_S(x) do { (x) = __builtin_amdgcn_readfirstlane(x); asm volatile("" : "+s"(x)); } while (0)   // (x is wave-uniform)
 #define SEL_LDS_FRAME (6 * NPA_MAX_E)              // floats of the frame's image in LDS (select_geo_carve.inc; the launchers size it)
 // the stage loop's wave-uniform switches, bits of the scalar `st`
-enum { ST_OVERFLOW = 1, ST_ALL = 2, ST_USE16 = 4, ST_USET = 8, ST_AUD16 = 16, ST_AUDIT_WAVE = 32, ST_HAS_AUDIT = 64, ST_DISTRUST = 128 };
+// (ST_FIRST / ST_SECOND: the list of 17-32 that encodes its 16 nearest-by-g first -- pending / its survivors' tile is running)
+enum { ST_OVERFLOW = 1, ST_ALL = 2, ST_USE16 = 4, ST_USET = 8, ST_AUD16 = 16, ST_AUDIT_WAVE = 32, ST_HAS_AUDIT = 64, ST_DISTRUST = 128,
+       ST_FIRST = 256, ST_SECOND = 512 };
 #define ST_IS(f) ((st & (unsigned)(f)) != 0u)
 #define ST_PUT(f, v) (st = (v) ? (st | (unsigned)(f)) : (st & ~(unsigned)(f)))
 #define SEL2_TRIP 256                            // points per trip of the key pass (4 per lane)

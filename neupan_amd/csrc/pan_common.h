@@ -48,8 +48,10 @@ struct DevParams {
   float rcx, rcy, rhx, rhy;
   int qp_aset;                // always 0, read by nothing: a layout placeholder of the retired active-set launch.  Removing it shifts geo_tab
                               // and the kernarg offsets of the selection kernels; the pack image's layout test pins the slot
-  int geo_tab;                // the weight pack carries the correction table of the geometric key (WP_TAB) and its margins (WP_KTAB)
+  int geo_tab;                // the weight pack carries the correction table of the geometric key (WP_TAB) and its margins (WP_KTAB):
+                              // bit 0; NPA_GEO_TAB_FIRST_TILE: lists of 17-32 encode their 16 nearest-by-g first (select_geo_body.inc)
 };
+#define NPA_GEO_TAB_FIRST_TILE 2                 // (per handle, set at creation unless NPA_SEL_FIRST_TILE=0)
 
 // ---- merged launches of a GROUP of forward calls (npa_forward_batch_group, c_api.hip) --------------------------------
 // The chains of a burst that share a stream, a batch size and a configuration run each stage as ONE launch: blockIdx.y

@@ -205,21 +205,43 @@
   if (ST_IS(ST_USET) && !ST_IS(ST_OVERFLOW)) total = ntot;       // (the list stands in dkey[0 .. ntot); sel[] is rebuilt from the survivors)
   ST_PUT(ST_AUD16, false);                                            // stage 1 checks every survivor's |exact - filter key| against m16
   float m16 = 0.f;
+  // TABF, a list of 17-32 (two thirds of the flagship's slices): ONE 16-point tile first, the rest bounded by what it found.
+  // Stage 0 takes every candidate's table key as it does for the filter (one lane each, one trip) and with it the geometric key
+  // and the table key's LOWER bound tk - m_table[band(tk)]; the list is ordered by geometric key -- the keys broadcast out of
+  // LDS, a rank of 32 subtractions per lane, no lane moves --, and its 16 smallest are encoded exactly (stage 1, first trip).  The
+  // msel-th smallest EXACT distance among them, dM, bounds the msel-th smallest distance of the slice from above: these are 16
+  // points of the slice and msel <= 16.  A candidate behind the first 16 whose lower bound lies strictly above dM has exact >=
+  // that bound > dM: it is not among the msel nearest and cannot tie into them; it is dropped.  The others (mostly none) are
+  // encoded in a second 16-point tile and audited like the filter's survivors.  Any superset of the true msel nearest, ranked
+  // on the exact (distance, index) key, emits the same rows: WHICH 16 points come first decides the cost alone.
+  // (Such a list never overflows: 17 <= ntot <= 32 <= SEL_CAP and msel <= 16 < ntot put it in the first arm of the decision above,
+  // ST_OVERFLOW clear, sel[] filled; ranks below 32 index sel[], s16[] and skey[], which hold SEL_CAP, SEL_CAP and NPA_MAX_M words.
+  // Audit waves never take this path, so ST_SECOND -- set for the survivors' tile and left set to the wave's end, where it moves
+  // the start of the tile loop -- is never set when stage 2 runs.)
+  static_assert(SEL_CAP >= 32 && NPA_MAX_M >= 32, "the first-tile path ranks up to 32 candidates into sel[], s16[] and skey[]");
+  if constexpr (TABF) {
+    if ((P.geo_tab & NPA_GEO_TAB_FIRST_TILE) != 0 && !ST_IS(ST_DISTRUST) && !ST_IS(ST_AUDIT_WAVE) && msel <= 16 && ntot > 16 && ntot <= 32) {
+      ST_PUT(ST_FIRST, true);
+      total = ntot;                                                      // (the list stands in dkey[0 .. ntot), as for the filter)
+    }
+  }
   SELP(4);
 #pragma unroll 1
-  for (int stage = (ST_IS(ST_OVERFLOW) || ST_IS(ST_USET)) ? 0 : 1;;) {
+  for (int stage = (ST_IS(ST_OVERFLOW) || ST_IS(ST_USET) || ST_IS(ST_FIRST)) ? 0 : 1;;) {
     // What the stages derive from the lane number and the slice's sizes (compare masks, clamped counts, the decimation step, the
     // audit tile's stride: most of it for the rare stages) is loop-invariant, so the compiler computed ALL of it in front of this
     // loop and parked it in VGPR lanes: ~100 v_writelane per wave, whichever stage ran.  Behind an empty asm the values are
     // this trip's own: each is derived where it is used.  (Integers only: a pointer through an asm loses its address space.)
     SEL_OPAQUE_V(lane); SEL_OPAQUE_S(n_use); SEL_OPAQUE_S(n_raw); SEL_OPAQUE_S(msel);
     const int cnt = stage == 0 ? total : (stage == 1 ? ncand : (n_use < 32 ? n_use : 32));
-    if (TABF && stage == 0 && ST_IS(ST_USET)) {
+    if (TABF && stage == 0 && (ST_IS(ST_USET) || ST_IS(ST_FIRST))) {
       unsigned* fk = ST_IS(ST_ALL) ? dkey : ckey;
+      const bool first = (__builtin_amdgcn_readfirstlane((int)st) & ST_FIRST) != 0;      // (a scalar branch, not a lane mask)
 #pragma unroll 1
       for (int q0 = 0; q0 < cnt; q0 += 64) {
         const int q = q0 + lane, qc = q < cnt ? q : cnt - 1;
-        const int src = src_index(cand_index(qc), n_raw, n_use);
+        const int iq = cand_index(qc);
+        const int src = src_index(iq, n_raw, n_use);
         SliceFrame Fl;      // (the frame out of LDS, per trip: the key pass's scalars are dead by now, and held across the encoder these are five registers)
         Fl.c = frg[5 * NPA_MAX_E + 0]; Fl.s = frg[5 * NPA_MAX_E + 1];
         Fl.tx = frg[5 * NPA_MAX_E + 2]; Fl.ty = frg[5 * NPA_MAX_E + 3]; Fl.tstep = frg[5 * NPA_MAX_E + 4];
@@ -227,12 +249,48 @@
         slice_point(P, Fl, px_row, vx_row, n_stride, src, gx, gy, p0x, p0y);
         // a point outside the calibrated square (or a NaN): no bound on its distance, it survives whatever the others do
         const float gk = geo_key_karg<E>(sel_kbase, p0x, p0y);
-        const unsigned kc = gk < P.geo_far ? ordered_key(gk + geo_tab_corr(wpack, p0x, p0y)) : NPA_TAB_KEY_FAR;
+        const float tk = gk + geo_tab_corr(wpack, p0x, p0y);
+        // (ordered_key(tk), value for value: the sign's part as a mask behind an empty asm -- as a select it waits behind its compare)
+        int tsg = __float_as_int(tk) >> 31;
+        asm("" : "+v"(tsg));
+        const unsigned tko = tk != tk ? 0xFFFFFFFEu : ~(__float_as_uint(tk) ^ (~(unsigned)tsg >> 1));      // (^ 0x7FFFFFFF, or ^ 0 below zero)
+        const unsigned kc = gk < P.geo_far ? tko : NPA_TAB_KEY_FAR;
         if (q < cnt) fk[q] = kc;                                 // (all: entry q is point q, its geometric key is done with)
+        if (first) {                                             // (one trip: cnt <= 32)
+          // lower bound of the exact distance, by the filter's rules: beyond the calibrated square, a NaN, a band without a
+          // calibration sample -- no bound, the candidate survives whatever dM turns out to be
+          // (npa_geo_band(tk), value for value, as max / shift / min: its selects cost wait states behind their compares)
+          const int tb = max(__float_as_int(tk + 0.25f), 0x3E800000) >> 20;
+          unsigned ti = (unsigned)min(tb + (WP_KTAB - (int)(0x3E800000u >> 20)), WP_KTAB + NPA_GEO_BANDS - 1);
+          asm("" : "+v"(ti));                                    // (an index, like wpack_at's; unsigned: no sign to extend)
+          const float mt = wpack[ti] * margin_scale;
+          // (a band without a sample carries an infinite margin: tk - mt is -inf or NaN there, and neither is above any dM)
+          const float lb = gk < P.geo_far ? tk - mt : -3.0e38f;
+          // the order: g >= 0, its bits order it; the low five give way to the POSITION in the list, so the 32 keys are distinct
+          // and a rank is a count of smaller ones -- a subtraction's sign, nothing through VCC.  (The window pass compacts a trip
+          // of 256 points u-major -- points 0, 4, 8, ... then 1, 5, 9, ... --, so the position is NOT the point's index: keys equal
+          // in all but their last five bits are ordered by where the window pass put them.  Total and the same on every run,
+          // which is all the order has to be: the rows do not depend on which sixteen come first.)
+          const unsigned kb = (__float_as_uint(gk) & 0x7FFFFFE0u) | (unsigned)lane | ((unsigned)((cnt - 1 - q) >> 31) >> 1);      // (behind the list: the largest key)
+          if (lane < 32) s16[32 + lane] = kb;
+          WSYNC();
+          int rk = 0;
+#pragma unroll
+          for (int j = 0; j < 32; ++j) rk -= (int)(s16[32 + j] - kb) >> 31;
+          WSYNC();
+          if (q < cnt) { sel[rk] = iq; s16[rk] = kc; skey[rk] = __float_as_uint(lb); }
+        }
+      }
+      if (first) {
+        WSYNC();
+        ncand = 16;
+        stage = 1;
+        SELP(4);                                                 // (the ordering: with the candidate list's phase)
+        continue;
       }
     } else
 #pragma unroll 1
-    for (int q0 = 0, tw = 32; q0 < cnt; q0 += tw) {
+    for (int q0 = TABF ? (__builtin_amdgcn_readfirstlane((int)st) & ST_SECOND) >> 5 : 0, tw = 32; q0 < cnt; q0 += tw) {     // (ST_SECOND, never set on an audit wave: from 16, the first tile's rows are parked)
       const bool narrow = TILE16 && cnt - q0 <= 16;        // (wave-uniform)
       tw = narrow ? 16 : 32;
       const bool own = lane < tw;                          // tw lanes own the tile's points, the others mirror them
@@ -318,6 +376,52 @@
     if (stage == 0) SELP(5); else if (stage == 1) SELP(6); else SELP(7);     // exact keys of a long list / the candidates' rows / audit tile
     if (stage == 2) break;
     if (stage == 1) {
+      if constexpr (TABF) {
+        if ((__builtin_amdgcn_readfirstlane((int)st) & ST_FIRST) != 0) {
+          // the first tile's rows are parked.  dM: the msel-th smallest of its 16 exact keys, ROUNDED UP in the key's last bit (still
+          // an upper bound): on keys of 31 bits a count of smaller ones is a subtraction's sign, nothing through VCC.  The lanes
+          // that hold the msel-th smallest 31-bit key (equal keys: all of them) store the same word.  A NaN key sorts last; a
+          // NaN dM drops nothing.  Then every candidate behind the first 16 against its lower bound, one lane each
+          ST_PUT(ST_FIRST, false);
+          unsigned myk = rkey[2 * (lane & 15) + 1] >> 1;
+          asm volatile("" : "+v"(myk));                  // (its range unknown, the sign of a difference stays a shift: no compare, no carry)
+          int below = 0, above = 0, j0 = 0;
+          asm volatile("" : "+v"(j0));                   // (the keys' address is this trip's own, not a scalar held across the loop)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const unsigned kj = rkey[2 * (j0 + j) + 1] >> 1;
+            below -= (int)(kj - myk) >> 31;
+            above -= (int)(myk - kj) >> 31;
+          }
+          if (below < msel && msel <= 16 - above) skey[0] = (myk << 1) | 1u;
+          WSYNC();
+          const unsigned kM = skey[0];
+          int msg = (int)kM >> 31;
+          asm("" : "+v"(msg));                                   // (a mask, not a select)
+          const float dM = __uint_as_float(~(kM ^ ((unsigned)msg >> 1)));         // (ordered_key back to the float: ^ 0x7FFFFFFF for a number >= 0)
+          int nrest = total;                                     // (= ntot on this path; derived here, not held as ntot - 16 across the loop)
+          SEL_OPAQUE_S(nrest);
+          nrest -= 16;
+          const int j = 16 + min(lane, nrest - 1);
+          const int ij = sel[j];
+          const unsigned kj = s16[j];
+          const bool hit = lane < nrest && !(__uint_as_float(skey[j]) > dM);          // dropped iff lower bound > dM, strictly
+          const unsigned long long bal = __ballot(hit);
+          const int pos = 16 + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
+          WSYNC();
+          if (hit) { sel[pos] = ij; s16[pos] = kj; }                    // (position <= source; the loads stand in front of the barrier)
+          WSYNC();
+          SELP(8);                                                       // (the bound and the test: with rank + emit)
+          fellback = 4;                                                  // (debug statistics: decided behind the first tile)
+          if (bal != 0ull) {
+            fellback = 5;                                                // (first tile + a second one for the survivors)
+            ncand = 16 + __popcll(bal);
+            ST_PUT(ST_SECOND, true);
+            ST_PUT(ST_AUD16, true);                                      // (|exact - table key| of every survivor, like the filter's)
+            continue;
+          }
+        }
+      }
       const size_t orow = (size_t)__float_as_int(frg[5 * NPA_MAX_E + 5]);
       const int Me = karg_load<int>(karg_fence(sel_kbase), offsetof(DevParams, M));      // (M, fetched for the emit: not carried to it)
       // lane q speaks for candidate q: rank on the exact (distance, index) key, emit; rows >= msel replicate row 0
