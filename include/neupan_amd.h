@@ -567,7 +567,7 @@ int npa_world_step(int batch, int n_worlds, int c_stride, int s_stride, double *
  *                                                    8 goal_threshold   9 the index of the candidate chosen by the last call
  *   agent_idx [W][a_stride][NPA_AGENT_INTS] int32    0 first primitive (the world's numbering: circles, then segments)
  *                                                    1 count (1 for a circle)   2 wander (0 / 1)   3 draws (uint32: wander
- *                                                    goals drawn so far)
+ *                                                    goals drawn so far, modulo 2^32)
  *   n_agents  [W] int32 (clamped to a_stride).  A row whose primitives do not exist (first < 0, count < 1, a circle with
  *   count != 1, a run beyond n_segments) is no agent: it is neither moved nor anybody's neighbour.  Runs must not overlap.
  * npa_behave_params (HOST): weight (the w of the penalty, > 0), horizon (seconds, > 0), robot_share (in (0, 1]),
@@ -609,7 +609,8 @@ int npa_world_step(int batch, int n_worlds, int c_stride, int s_stride, double *
  * NPA_E_ARG (before anything touches a device): a null required pointer (prev_state may be null; dirs when there is no
  *   grid), batch <= 0, a_stride <= 0, n_worlds not in {1, batch}, dt <= 0, weight <= 0, horizon <= 0, robot_share outside
  *   (0, 1], range_low above range_high, robot_radius < 0, more candidates than the cap, strides that do not fit (no
- *   primitives at all, seg_limit beyond s_stride, more rows than a launch addresses). */
+ *   primitives at all, seg_limit beyond s_stride, more rows than a launch addresses), world_base < 0 (or world_base +
+ *   n_worlds beyond an int: the generator's world is world_base + w as a uint32, zero-extended). */
 #define NPA_AGENT_DOUBLES 10
 #define NPA_AGENT_INTS 4
 typedef struct npa_behave_params {

@@ -382,6 +382,8 @@ extern "C" int npa_world_behave(int batch, int n_worlds, int c_stride, int s_str
       !n_circles || !n_segments || (c_stride > 0 && !circles) || (s_stride > 0 && !segments))
     return fail(NPA_E_ARG, "npa_world_behave: bad argument");
   if (n_worlds != 1 && n_worlds != batch) return fail(NPA_E_ARG, "npa_world_behave: n_worlds must be 1 or batch");
+  if (params->world_base < 0 || params->world_base > 0x7fffffff - n_worlds)
+    return fail(NPA_E_ARG, "npa_world_behave: world_base must be >= 0 (and world_base + n_worlds an int)");
   if ((long long)c_stride + (long long)s_stride <= 0) return fail(NPA_E_ARG, "npa_world_behave: strides: agents without primitives");
   if (!(dt > 0.0)) return fail(NPA_E_ARG, "npa_world_behave: dt must be > 0");
   if (!(params->weight > 0.0)) return fail(NPA_E_ARG, "npa_world_behave: weight must be > 0");

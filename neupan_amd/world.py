@@ -279,6 +279,9 @@ class LidarWorld:
         unknown = set(behaviour) - set(BEHAVIOUR)
         if unknown:
             raise TypeError(f"unknown behaviour parameters {sorted(unknown)}")
+        wb = int(behaviour.get("world_base", self.behaviour["world_base"]))
+        if wb < 0 or wb > 0x7FFFFFFF - self.W:                   # npa_world_behave's rule, before a goal is drawn with it
+            raise ValueError("world_base must be >= 0 (and world_base + the number of worlds an int)")
         self._download()
         self.behaviour.update(behaviour)
         bh = self.behaviour

@@ -1,11 +1,15 @@
-"""The tables of tests/test_behave.py (the restatement, on the CPU) and tests/test_behave_gpu.py (npa_world_behave).
+"""The tables of tests/test_behave.py (the restatement, on the CPU) and tests/test_behave_gpu.py and
+tests/test_behave_edges_gpu.py (npa_world_behave).
 
 DECIDED: cases on dyadic inputs, on which every intermediate is exact (or a single correctly rounded operation), with the
 expected result written out as literals.  A case is a dict:
     worlds   list of dict(circles (C, 6), segments (S, 6), rows (A, 10), idx (A, 4))
     par      dict(weight, horizon, robot_share, range_low, range_high, seed)
     robots (B, 3), prev (B, 3) or None, radius, seg_limit, dt, n_speed, dirs
-    expect   per world, per agent: (chosen index, (vx, vy), (gx, gy), draws)
+    expect   per world, per agent row: (chosen index, (vx, vy), (gx, gy), draws); None for a row that is no agent (it comes back
+             bitwise as it went in and owns nothing)
+EDGES: the same format, on the inputs DECIDED leaves out (rows that are no agent, the clamped current velocity, a segment of
+length zero and one that moves, L == 0, the counter's wrap, seg_limit 0, a null array with stride 0).
 The candidate table of the decided cases: 4 exact directions, 2 speeds -> 0 zero, 1 v_pref, 2 v_A, 3 - 6 half speed E N W S,
 7 - 10 full speed E N W S.
 """
@@ -33,8 +37,11 @@ def world(circles=(), segments=(), rows=(), idx=()):
 
 
 def case(name, worlds, expect, robots=(FAR,), prev=None, radius=0.5, seg_limit=-1, weight=1.0, horizon=8.0, share=1.0, seed=11,
-         lo=(-8.0, -8.0), hi=(8.0, 8.0), dt=0.5, n_speed=2, dirs=DIRS4):
-    return dict(name=name, worlds=worlds, expect=expect, robots=np.array(robots, dtype=np.float64).reshape(-1, 3),
+         lo=(-8.0, -8.0), hi=(8.0, 8.0), dt=0.5, n_speed=2, dirs=DIRS4, null=(), expect2=None):
+    """null: the arrays ("circles", "segments") no world of the case has a row of: the device run passes them as a null
+    pointer with stride 0 as well; expect2: what a second call from the first one's tables gives"""
+    return dict(name=name, worlds=worlds, expect=expect, null=tuple(null), expect2=expect2,
+                robots=np.array(robots, dtype=np.float64).reshape(-1, 3),
                 prev=None if prev is None else np.array(prev, dtype=np.float64).reshape(-1, 3), radius=radius, seg_limit=seg_limit,
                 par=dict(weight=weight, horizon=horizon, robot_share=share, range_low=lo, range_high=hi, seed=seed), dt=dt,
                 n_speed=n_speed, dirs=np.asarray(dirs, dtype=np.float64).reshape(-1, 2))
@@ -119,6 +126,67 @@ DECIDED = [
 ]
 
 
+def _no_agent(name, idx1, expect1=None):
+    """plain_circle's world with a far segment (primitive 2) and a second row whose primitives are `idx1`: as long as that row
+    is no agent, circle 1 stays a plain circle (alpha 1, tc 2 beyond the horizon 1: row 0 takes index 1; an agent's circle would
+    give index 3, see agent_circle) and the row itself, with its stale velocity and index, is not touched"""
+    wd = world([circle(0.0, 0.0, 0.5), circle(3.0, 0.0, 0.5)], [seg(3.0, -64.0, 4.0, -64.0)],
+               [agent_row(4.0, 0.0), agent_row(3.0, 0.0, vx=0.125, vy=0.25)], [[0, 1, 0, 7], idx1])
+    return case(name, [wd], [[(1, (1.0, 0.0), (4.0, 0.0), 7), expect1]], horizon=1.0)
+
+
+_POLYGON = [seg(80.0, 80.0, 81.0, 80.0), seg(-0.5, -0.5, 0.5, -0.5), seg(0.5, -0.5, 0.5, 0.5), seg(0.5, 0.5, -0.5, 0.5),
+            seg(-0.5, 0.5, -0.5, -0.5), seg(90.0, 90.0, 91.0, 90.0)]
+
+EDGES = [
+    # ---- rows that are no agent, one per way agent_ok fails: first < 0, count < 1, a circle with count != 1, first = nC + nS,
+    #      a run past n_segments.  The control: the one segment is a valid polygon agent, 64 below its goal: v_pref = (0, 1)
+    _no_agent("no_agent_first_negative", [-1, 1, 0, 3]),
+    _no_agent("no_agent_count_zero", [1, 0, 0, 3]),
+    _no_agent("no_agent_circle_count_two", [1, 2, 0, 3]),
+    _no_agent("no_agent_first_at_end", [3, 1, 0, 3]),
+    _no_agent("no_agent_run_past_end", [2, 2, 0, 3]),
+    _no_agent("no_agent_control", [2, 1, 0, 3], (1, (0.0, 1.0), (3.0, 0.0), 3)),
+    # no grid; the agent drifts at (0, 2) with v_max 1, a free circle at (2, 0) comes at (-1, 0) along the goal line (c2 = 3).
+    # Standing: u = (1, 0), b = 2, disc = 4 - 3, tc = 3 / 3, cost 1 + 1; v_pref = (1, 0): u = (2, 0), b = 4, disc = 16 - 12, tc = 3 / 6,
+    # cost 2 + 0; candidate 2 = (0, 2) (1 / 2) = (0, 1): u = (1, 1), disc = 4 - 2 * 3 < 0: free, cost |(1, -1)| = sqrt 2 -> 2
+    case("vcur_clamped", [world([circle(0.0, 0.0, 0.5, 0.0, 2.0), circle(2.0, 0.0, 0.5, -1.0, 0.0)], (), [agent_row(4.0, 0.0)],
+                                [[0, 1, 0, 7]])],
+         [[(2, (0.0, 1.0), (4.0, 0.0), 7)]], n_speed=0, dirs=np.zeros((0, 2))),
+    # a segment of length zero is one disc (e2 == 0: no normal, both shifted segments invalid): c = (3, 0), c2 = 9 - 1/4, u = (1, 0):
+    # disc = 1/4, tc = 8.75 / 3.5 = 2.5 -- wall_end_disc's numbers
+    case("point_segment_at", [_one(segments=[seg(3.0, 0.0, 3.0, 0.0)])], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], weight=5.0, horizon=2.5),
+    case("point_segment_below", [_one(segments=[seg(3.0, 0.0, 3.0, 0.0)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], weight=5.0,
+         horizon=BELOW(2.5)),
+    # the wall x = 2 comes at (-1, 0) (its velocity is the capsule's apex): u = v' + (1, 0), tc = 1.5 / 2 at speed 1 (cost 3 / 0.75),
+    # 1.5 / 1.5 at speed 1/2 and 1.5 standing (both beyond the horizon: costs 1/2 and 1)
+    case("moving_wall_at", [_one(segments=[seg(2.0, -4.0, 2.0, 4.0, vx=-1.0)])], [[(3, (0.5, 0.0), (4.0, 0.0), 7)]], weight=3.0,
+         horizon=0.75),
+    case("moving_wall_below", [_one(segments=[seg(2.0, -4.0, 2.0, 4.0, vx=-1.0)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], weight=3.0,
+         horizon=BELOW(0.75)),
+    # the goal at the centre (L == 0) with wander: a negative threshold is not arrived, so nothing is drawn and L == 0 rests;
+    # threshold 0 is arrived: draw 7 of (seed 11, world 0, agent 0), counter + 1, then towards the new goal
+    case("L0_threshold_negative", [_one(goal=(0.0, 0.0), wander=1, thr=-1.0)], [[(0, (0.0, 0.0), (0.0, 0.0), 7)]]),
+    case("L0_threshold_zero", [_one(goal=(0.0, 0.0), wander=1, thr=0.0)],
+         [[(1, (0.8341659763429594, -0.5515134847959724), (6.325486335491668, -4.1821305481800355), 8)]]),
+    # the counter is a uint32 in an int32 column: -1 is draw number 4294967295, the counter wraps to 0, and the next call (the
+    # threshold 32 is beyond the box: the agent is arrived wherever its goal is) draws number 0
+    case("draws_wrap", [_one(goal=(0.0, 0.0), wander=1, draws=-1, thr=32.0)],
+         [[(1, (-0.5201745549893948, -0.8540599699913264), (-3.634968440866226, -5.968152436039324), 0)]],
+         expect2=[[(1, (0.6428758136797308, 0.76597042252663), (1.916894750002898, 2.283932060213221), 1)]]),
+    # seg_limit 0 hides every segment (seg_limit_open's world: with the wall in sight the choice is 3)
+    case("seg_limit_zero", [_one(segments=[seg(64.0, 64.0, 65.0, 64.0), seg(2.0, -4.0, 2.0, 4.0)])], [[(1, (1.0, 0.0), (4.0, 0.0), 7)]],
+         weight=3.0, horizon=1.5, seg_limit=0),
+    # worlds without a circle or without a segment: polygon_agent's and agent_circle's; run padded, and with the absent array a null
+    # pointer with stride 0
+    case("segments_only", [world((), _POLYGON, [agent_row(4.0, 0.0, R=0.7071067811865476, ox=0.5, oy=0.5)], [[1, 4, 0, 7]])],
+         [[(1, (1.0, 0.0), (4.0, 0.0), 7)]], null=("circles",)),
+    case("circles_only", [world([circle(0.0, 0.0, 0.5), circle(3.0, 0.0, 0.5)], (), [agent_row(4.0, 0.0), agent_row(3.0, 0.0)],
+                                [[0, 1, 0, 7], [1, 1, 0, 9]])],
+         [[(3, (0.5, 0.0), (4.0, 0.0), 7), (0, (0.0, 0.0), (3.0, 0.0), 9)]], horizon=1.0, null=("segments",)),
+]
+
+
 # ---------------------------------------------------------------------------------------------------------------- random worlds
 def directions(n_dir):
     from math import cos, pi, sin
@@ -185,17 +253,66 @@ RANDOM = [
 ]
 
 
+# The same tuple with a dict behind it: box (half the side of the square everything is drawn in), horizon, seg_limit, prev=False
+# (no prev_state), shapes (per world: agents, free circles, free segments, polygon agents -- instead of the common four).
+# In a world the circles come first in the disc index space, then the agent rows, then the robots; segment s is primitive nC + s.
+RANDOM_EDGES = [
+    # 3 + 509 = 512 candidates = npa_behave_max_candidates(): trips 0 .. 7 of 64 lanes (the suite above stops in trip 2)
+    ("c512", 1, 3, 12, 4, 0, 1, 509, 1, 8, dict()),
+    # 3 + 63 x 3 = 192: exactly three full trips, no ragged tail
+    ("c192", 1, 5, 7, 9, 2, 3, 63, 3, 10, dict()),
+    # nC = 190 + 4 = 194 circles, 4 agent rows, 1 robot = 199 discs: chunks 0 - 63, 64 - 127, 128 - 191 (free circles, each chunk
+    # asks every agent row for ownership) and 192 - 198 (2 circles, the agents, the robot)
+    ("d200", 1, 4, 190, 0, 0, 1, 20, 3, 5, dict(box=24.0)),
+    # nC = 5 + 3 = 8 circles, 3 agent rows, 70 robots = 81 discs: chunk 0 ends at robot 52, chunk 1 holds robots 53 - 69
+    ("r70", 1, 3, 5, 0, 0, 70, 20, 3, 1, dict(box=12.0)),
+    ("r70_noprev", 1, 3, 5, 0, 0, 70, 20, 3, 1, dict(box=12.0, prev=False)),
+    # 140 free segments, then two squares (segments 140 - 147, owned): seg_limit 100 cuts chunk 1 (64 - 127) at lane 36 and leaves
+    # no chunk 2; the polygon agents' edges lie beyond the cut.  seg_limit 0: no chunk at all.  Open: chunks 0, 1 and 2 (128 - 147)
+    ("s148_lim100", 1, 4, 3, 140, 2, 1, 20, 3, 4, dict(box=12.0, seg_limit=100)),
+    ("s148_lim0", 1, 4, 3, 140, 2, 1, 20, 3, 4, dict(box=12.0, seg_limit=0)),
+    ("s148_open", 1, 4, 3, 140, 2, 1, 20, 3, 4, dict(box=12.0)),
+    # per world 253 circles and 28 segments; the packed strides are 255 + 30 = 285 primitives = two commit workgroups of 256 per
+    # world: workgroup 1 has t = 256 - 511, all of them segments (p = t - 255 = 1 - 256, 29 of them in the array), the owned
+    # segments 20 - 27 among them; the circle agents' circles lie in workgroup 0.  World 1 is workgroups 2 and 3
+    ("commit2blk", 2, 5, 250, 20, 2, 0, 20, 3, 1, dict(box=24.0)),
+    # w1_a5_mixed with an infinite horizon: nothing is culled, every finite tc counts
+    ("hz_inf", 1, 5, 7, 9, 2, 3, 32, 4, 5, dict(horizon=float("inf"))),
+    # three worlds under common strides: no agent row at all; no circle (two squares among 3 free segments); no segment
+    ("ragged", 3, 0, 0, 0, 0, 0, 20, 3, 4, dict(shapes=[(0, 4, 3, 0), (2, 0, 3, 2), (3, 4, 0, 0)])),
+]
+
+
 def random_case(spec):
-    name, W, nA, nc, ns, npoly, nrob, n_dir, n_speed, seed = spec
+    name, W, nA, nc, ns, npoly, nrob, n_dir, n_speed, seed = spec[:10]
+    opt = spec[10] if len(spec) > 10 else {}
+    box = opt.get("box", 6.0)
+    shapes = opt.get("shapes", [(nA, nc, ns, npoly)] * W)
     rng = np.random.default_rng(seed)
-    worlds = [random_world(rng, nA, nc, ns, npoly) for _ in range(W)]
+    worlds = [random_world(rng, *shape, **({"box": box} if "box" in opt else {})) for shape in shapes]
     B = W if W > 1 else max(nrob, 1)
     robots = np.zeros((B, 3))
-    robots[:, 0:2] = rng.uniform(-6, 6, (B, 2)) if (W > 1 or nrob > 0) else 4096.0
+    robots[:, 0:2] = rng.uniform(-box, box, (B, 2)) if (W > 1 or nrob > 0) else 4096.0
     prev = robots.copy()
     prev[:, 0:2] -= rng.uniform(-0.05, 0.05, (B, 2))
-    return dict(name=name, worlds=worlds, robots=robots, prev=prev, radius=0.6, seg_limit=-1, par=dict(PAR), dt=0.1, n_speed=n_speed,
-                dirs=directions(n_dir) if n_dir else np.zeros((0, 2)))
+    par = dict(PAR, horizon=opt.get("horizon", PAR["horizon"]))
+    return dict(name=name, worlds=worlds, robots=robots, prev=prev if opt.get("prev", True) else None, radius=0.6,
+                seg_limit=opt.get("seg_limit", -1), par=par, dt=0.1, n_speed=n_speed,
+                dirs=directions(n_dir) if n_dir else np.zeros((0, 2)), null=(), expect2=None)
+
+
+def shifted(case, circles=(), segments=(), robots=(), by=4096.0):
+    """the case with the named primitives of world 0 and the named robots (with their prev) moved by (by, by): out of everybody's
+    sight, the indices of all others unchanged"""
+    wd = {k: np.array(v) for k, v in case["worlds"][0].items()}
+    wd["circles"][list(circles), 0:2] += by
+    wd["segments"][list(segments), 0:4] += by
+    rb = case["robots"].copy()
+    rb[list(robots), 0:2] += by
+    pv = None if case["prev"] is None else case["prev"].copy()
+    if pv is not None:
+        pv[list(robots), 0:2] += by
+    return dict(case, worlds=[wd] + list(case["worlds"][1:]), robots=rb, prev=pv)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the loops

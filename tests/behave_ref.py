@@ -9,6 +9,7 @@ One world at a time, every candidate against every neighbour: no culling, no chu
 import numpy as np
 
 M64 = (1 << 64) - 1
+M32 = (1 << 32) - 1
 INF = np.inf
 
 
@@ -77,16 +78,22 @@ def seg_tc(wx, wy, ex, ey, ux, uy):
     return np.where(valid, t, INF)
 
 
-def behave_world(circles, segments, rows, idx, par, robots, prev_robots, robot_radius, seg_limit, dirs, n_speed, dt, world=0):
+def behave_world(circles, segments, rows, idx, par, robots, prev_robots, robot_radius, seg_limit, dirs, n_speed, dt, world=0,
+                 counts=None):
     """One call of npa_world_behave for one world.  par: dict(weight, horizon, robot_share, range_low, range_high, seed);
-    robots (R, 3): the robots this world's agents see; prev_robots (R, 3) or None; world: world_base + w.
+    robots (R, 3): the robots this world's agents see; prev_robots (R, 3) or None; world: world_base + w; counts: None (the
+    arrays' lengths), or (n_circles, n_segments, n_agents) as the count arrays hold them: each is clamped to [0, the array's
+    length], and the rows at and beyond it are neither read nor written (they come back as they went in).
     Returns dict(circles, segments, rows, idx: the arrays after the call; chosen (A,) int; costs: list of (n_cand,) arrays;
-    tc: list of (n_cand,) arrays; None for rows that are no agents)."""
-    C = np.array(circles, dtype=np.float64).reshape(-1, 6)
-    S = np.array(segments, dtype=np.float64).reshape(-1, 6)
-    rows = np.array(rows, dtype=np.float64).reshape(-1, 10)
-    idx = np.array(idx, dtype=np.int64).reshape(-1, 4)
-    nC, nS, nA = len(C), len(S), len(rows)
+    tc: list of (n_cand,) arrays; None for rows that are no agents), A the clamped number of agents."""
+    C_all = np.array(circles, dtype=np.float64).reshape(-1, 6)
+    S_all = np.array(segments, dtype=np.float64).reshape(-1, 6)
+    rows_all = np.array(rows, dtype=np.float64).reshape(-1, 10)
+    idx_all = np.array(idx, dtype=np.int64).reshape(-1, 4)
+    nC, nS, nA = len(C_all), len(S_all), len(rows_all)
+    if counts is not None:
+        nC, nS, nA = (min(max(int(n), 0), full) for n, full in zip(counts, (nC, nS, nA)))
+    C, S, rows, idx = C_all[:nC], S_all[:nS], rows_all[:nA], idx_all[:nA]           # (views: launch 2 writes through them)
     robots = np.zeros((0, 3)) if robots is None else np.asarray(robots, dtype=np.float64).reshape(-1, 3)
     ok = [agent_ok(int(idx[k, 0]), int(idx[k, 1]), nC, nS) for k in range(nA)]
     owned = np.zeros(nC + nS, dtype=bool)
@@ -105,7 +112,7 @@ def behave_world(circles, segments, rows, idx, par, robots, prev_robots, robot_r
     for a in range(nA):
         if not ok[a]:
             continue
-        first, wander, draws = int(idx[a, 0]), int(idx[a, 2]), int(idx[a, 3])
+        first, wander, draws = int(idx[a, 0]), int(idx[a, 2]), int(idx[a, 3]) & M32     # (the int32 column holds a uint32)
         anc, vA = anchor(first)
         px, py = anc[0] + rows[a, 4], anc[1] + rows[a, 5]
         RA, vmax, thr = rows[a, 6], rows[a, 7], rows[a, 8]
@@ -118,7 +125,7 @@ def behave_world(circles, segments, rows, idx, par, robots, prev_robots, robot_r
         redraw = arrived and wander != 0
         if redraw:
             gx, gy = draw_goal(par["seed"], world, first, draws, par["range_low"], par["range_high"])
-            draws += 1
+            draws = (draws + 1) & M32
             dx, dy = gx - px, gy - py
             L = np.sqrt(dx * dx + dy * dy)
         if (arrived and not redraw) or not (L > 0.0):
@@ -178,7 +185,7 @@ def behave_world(circles, segments, rows, idx, par, robots, prev_robots, robot_r
         chosen[a], costs[a], tcs[a] = best, cost, tc
         new_rows[a, 0:4] = [gx, gy, V[best, 0], V[best, 1]]
         new_rows[a, 9] = float(best)
-        new_idx[a, 3] = draws
+        new_idx[a, 3] = draws - (1 << 32) if draws >> 31 else draws               # (back into the int32 column)
     # ---- launch 2
     for a in range(nA):
         if ok[a]:
@@ -187,7 +194,8 @@ def behave_world(circles, segments, rows, idx, par, robots, prev_robots, robot_r
                     C[p, 3:5] = new_rows[a, 2:4]
                 else:
                     S[p - nC, 4:6] = new_rows[a, 2:4]
-    return dict(circles=C, segments=S, rows=new_rows, idx=new_idx, chosen=chosen, costs=costs, tc=tcs)
+    rows_all[:nA], idx_all[:nA] = new_rows, new_idx
+    return dict(circles=C_all, segments=S_all, rows=rows_all, idx=idx_all, chosen=chosen, costs=costs, tc=tcs)
 
 
 def decided(costs, rel=1e-12):

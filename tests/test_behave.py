@@ -32,8 +32,8 @@ def test_argument_validation_without_gpu(lib):
     cap = lib.npa_behave_max_candidates()
     assert cap >= 131 and lib.npa_behave_list_capacity() >= 1
 
-    def params(weight=1.0, horizon=5.0, share=0.5, lo=(0.0, 0.0), hi=(10.0, 10.0)):
-        return NpaBehaveParams(weight, horizon, share, (C.c_double * 2)(*lo), (C.c_double * 2)(*hi), 7, 0, 0)
+    def params(weight=1.0, horizon=5.0, share=0.5, lo=(0.0, 0.0), hi=(10.0, 10.0), world_base=0):
+        return NpaBehaveParams(weight, horizon, share, (C.c_double * 2)(*lo), (C.c_double * 2)(*hi), 7, world_base, 0)
 
     def call(batch=4, n_worlds=4, c_stride=8, s_stride=8, a_stride=4, par=None, radius=0.5, seg_limit=-1, n_dir=20, n_speed=3, dt=0.1,
              null=(), no_par=False, dirs=P):
@@ -72,6 +72,12 @@ def test_argument_validation_without_gpu(lib):
     refused(call(c_stride=0, s_stride=0, null=("circles", "segments")), b"strides")
     refused(call(seg_limit=9), b"strides")                       # beyond s_stride
     refused(call(n_worlds=4, a_stride=1 << 30), b"strides")      # more rows than a launch addresses
+    # item 8: the generator's world is world_base + w as a uint32; a negative base, or a sum beyond an int, has no meaning
+    refused(call(par=params(world_base=-1)), b"world_base"); refused(call(par=params(world_base=-(1 << 31))), b"world_base")
+    refused(call(par=params(world_base=(1 << 31) - 4)), b"world_base")            # + 4 worlds: one past an int
+    refused(call(batch=4, n_worlds=1, par=params(world_base=(1 << 31) - 1)), b"world_base")
+    ok_base = params(world_base=(1 << 31) - 5)                   # the largest base four worlds may have: refused for another reason
+    refused(call(par=ok_base, dt=0.0), b"dt")
 
 
 def test_from_yaml_makes_agents_of_rvo_groups():
@@ -158,6 +164,19 @@ obstacle:
     assert w.agents["idx"][0, 2].tolist() == [7, 3, 0, 0] and w.agents["rows"][0, 2, 0:2].tolist() == [3.0, 3.0]
 
 
+def test_add_agents_refuses_a_world_base_the_library_refuses():
+    """item 8 on the Python side: the rule of npa_world_behave, before a goal is drawn with a world index that has no meaning;
+    a refused call leaves the world as it was"""
+    from neupan_amd.world import LidarWorld
+    w = LidarWorld(np.array([bc.circle(0.0, 0.0, 0.5), bc.circle(3.0, 0.0, 0.5)]), np.zeros((0, 6)), device="cpu")
+    for bad in (-1, (1 << 31) - 1, 1 << 31):
+        with pytest.raises(ValueError, match="world_base"):
+            w.add_agents([0], wander=True, world_base=bad)
+        assert not w.has_agents and w.behaviour["world_base"] == 0
+    assert w.add_agents([0], wander=True, world_base=(1 << 31) - 2) == 0 and w.behaviour["world_base"] == (1 << 31) - 2
+    assert w.agents["rows"][0, 0, 0] == ref.draw_goal(0, (1 << 31) - 2, 0, 0, (0.0, 0.0), (10.0, 10.0))[0]
+
+
 def test_generator():
     from neupan_amd.world import wander_goal
     lo, hi = (-3.0, 5.0), (9.0, 5.5)
@@ -174,34 +193,156 @@ def test_generator():
     assert (want[:, 0] >= lo[0]).all() and (want[:, 0] <= hi[0]).all() and (want[:, 1] >= lo[1]).all() and (want[:, 1] <= hi[1]).all()
 
 
-@pytest.mark.parametrize("case", bc.DECIDED, ids=lambda c: c["name"])
+def after(case, res):
+    """the case whose worlds are the tables a call left (for a second call without a move in between)"""
+    return dict(case, worlds=[dict(circles=o["circles"], segments=o["segments"], rows=o["rows"], idx=o["idx"].astype(np.int32))
+                              for o in res])
+
+
+@pytest.mark.parametrize("case", bc.DECIDED + bc.EDGES, ids=lambda c: c["name"])
 def test_restatement_on_decided_cases(case):
-    """the literals of behave_cases.DECIDED are what the restatement computes, bit for bit"""
-    for o, wd, exp in zip(ref.run_case(case), case["worlds"], case["expect"]):
-        for a, (chosen, vel, goal, draws) in enumerate(exp):
-            assert int(o["chosen"][a]) == chosen, (a, o["costs"][a])
-            assert tuple(o["rows"][a, 2:4]) == tuple(vel) and tuple(o["rows"][a, 0:2]) == tuple(goal)
-            assert int(o["idx"][a, 3]) == draws and o["rows"][a, 9] == chosen
-            f, n = int(wd["idx"][a, 0]), int(wd["idx"][a, 1])
-            nC = len(wd["circles"])
-            for p in range(f, f + n):
-                got = o["circles"][p, 3:5] if p < nC else o["segments"][p - nC, 4:6]
-                assert tuple(got) == tuple(vel)
+    """the literals of behave_cases.DECIDED and EDGES are what the restatement computes, bit for bit.  EDGES reach: rows that are
+    no agent, one per failure of agent_ok (item 1: such a row is bitwise its input, owns nothing and is nobody's neighbour); a
+    null array with stride 0 (item 3, on the device); seg_limit == 0 (item 6); the counter's wrap 0xFFFFFFFF -> 0 and the draw
+    after it (item 7); the clamped candidate 2 as the winner, a segment of length zero, a segment with a velocity, L == 0 below
+    and at the threshold (item 9)"""
+    calls = [(case, case["expect"])]
+    if case["expect2"] is not None:
+        calls.append((after(case, ref.run_case(case)), case["expect2"]))
+    for cs, expect in calls:
+        for o, wd, exp in zip(ref.run_case(cs), cs["worlds"], expect):
+            nC, nS = len(wd["circles"]), len(wd["segments"])
+            want_c, want_s = np.array(wd["circles"]), np.array(wd["segments"])
+            assert len(exp) == len(wd["rows"])
+            for a, e in enumerate(exp):
+                f, n = int(wd["idx"][a, 0]), int(wd["idx"][a, 1])
+                assert ref.agent_ok(f, n, nC, nS) == (e is not None), (a, f, n)
+                if e is None:                                        # no agent: the row is bitwise its input and owns nothing
+                    assert o["rows"][a].tobytes() == wd["rows"][a].tobytes() and o["chosen"][a] == -1 and o["costs"][a] is None
+                    assert o["idx"][a].astype(np.int32).tobytes() == wd["idx"][a].tobytes()
+                    continue
+                chosen, vel, goal, draws = e
+                assert int(o["chosen"][a]) == chosen, (a, o["costs"][a])
+                assert tuple(o["rows"][a, 2:4]) == tuple(vel) and tuple(o["rows"][a, 0:2]) == tuple(goal), o["rows"][a].tolist()
+                assert int(o["idx"][a, 3]) == draws and o["rows"][a, 9] == chosen
+                for p in range(f, f + n):
+                    if p < nC:
+                        want_c[p, 3:5] = vel
+                    else:
+                        want_s[p - nC, 4:6] = vel
+            # the primitives: the owned ones took their agent's velocity, every other number is bitwise the input
+            assert o["circles"].tobytes() == want_c.tobytes() and o["segments"].tobytes() == want_s.tobytes()
 
 
 def test_random_cases_are_decided():
     """the cases left out of the device comparison (the restatement's two lowest costs within 1e-12 relative) are capped at 1 %:
     these seeds keep the restatement alone under the cap"""
-    for spec in bc.RANDOM:
+    total = 0
+    for spec in bc.RANDOM + bc.RANDOM_EDGES:
         case = bc.random_case(spec)
         res = ref.run_case(case)
         agents = sum(len(o["chosen"]) for o in res)
         open_ = sum(1 for o in res for c in o["costs"] if not ref.decided(c))
-        assert agents == spec[1] * spec[2] and open_ <= 0.01 * agents, (spec[0], agents, open_)
+        shapes = spec[10].get("shapes") if len(spec) > 10 else None
+        assert agents == (sum(s[0] for s in shapes) if shapes else spec[1] * spec[2]), (spec[0], agents)
+        assert open_ <= 0.01 * agents, (spec[0], agents, open_)
         n_cand = 3 + len(case["dirs"]) * case["n_speed"] if len(case["dirs"]) else 3
         assert all(len(c) == n_cand for o in res for c in o["costs"])
-    counts = sorted({3 + s[7] * s[8] for s in bc.RANDOM})
-    assert counts == [3, 63, 64, 65, 131]
+        total += agents
+    assert total == 292 + 50                                     # (what DESIGN.md states)
+    counts = sorted({3 + s[7] * s[8] for s in bc.RANDOM + bc.RANDOM_EDGES})
+    assert counts == [3, 63, 64, 65, 131, 192, 512]
+    assert 512 == 8 * 64 and 192 == 3 * 64                       # item 5: eight trips of 64 lanes (the cap); three full ones
+
+
+def _owned(wd):
+    nC, nS = len(wd["circles"]), len(wd["segments"])
+    return {p for f, n in wd["idx"][:, 0:2].tolist() if ref.agent_ok(f, n, nC, nS) for p in range(f, f + n)}
+
+
+def _chosen(case):
+    res = ref.run_case(case)
+    assert all(ref.decided(c) for o in res for c in o["costs"]), case["name"]
+    return res[0]["chosen"], res
+
+
+def test_random_edges_depend_on_what_they_are_there_for():
+    """a kernel that dropped the last chunk, the last trips or the infinite horizon would still pass a spec whose result does
+    not hang on them.  So, on the restatement: with the neighbours of the last chunk moved by +4096 (indices unchanged) at
+    least one agent chooses another index (item 6: d200's free circles from 128 on, r70's robots 64 - 69 with their prev,
+    s148_lim100's segments 64 - 99 and s148_open's 128 - 139), every choice still decided; the segments seg_limit hides change
+    nothing; c512's agents choose in trips 6 and 7 and c192's in trip 2 (item 5); hz_inf's choices are not those of horizon 6"""
+    spec = {s[0]: s for s in bc.RANDOM_EDGES}
+    case = bc.random_case(spec["d200"])
+    wd = case["worlds"][0]
+    nC = len(wd["circles"])
+    assert nC == 194 and nC + len(wd["rows"]) + len(case["robots"]) == 199                  # four chunks of 64
+    last = [p for p in range(128, nC) if p not in _owned(wd)]
+    assert len(last) >= 60
+    assert (_chosen(case)[0] != _chosen(bc.shifted(case, circles=last))[0]).any()
+
+    for name in ("r70", "r70_noprev"):
+        case = bc.random_case(spec[name])
+        wd = case["worlds"][0]
+        assert len(case["robots"]) == 70 and len(wd["circles"]) + len(wd["rows"]) == 11    # robot b is disc 11 + b: 53 opens chunk 1
+        assert (case["prev"] is None) == (name == "r70_noprev")
+        assert (_chosen(case)[0] != _chosen(bc.shifted(case, robots=range(64, 70)))[0]).any(), name
+
+    case = bc.random_case(spec["s148_lim100"])
+    wd = case["worlds"][0]
+    assert len(wd["segments"]) == 148 and case["seg_limit"] == 100
+    assert _owned(wd) & set(range(len(wd["circles"]), len(wd["circles"]) + 148)) == set(range(len(wd["circles"]) + 140, len(wd["circles"]) + 148))
+    base, res = _chosen(case)
+    assert (base != _chosen(bc.shifted(case, segments=range(64, 100)))[0]).any()
+    hidden = ref.run_case(bc.shifted(case, segments=range(100, 140)))[0]
+    assert hidden["rows"].tobytes() == res[0]["rows"].tobytes() and hidden["idx"].tobytes() == res[0]["idx"].tobytes()
+    for other in ("s148_lim0", "s148_open"):                     # the same world under the three limits, three results
+        assert bc.random_case(spec[other])["worlds"][0]["segments"].tobytes() == wd["segments"].tobytes()
+        assert (_chosen(bc.random_case(spec[other]))[0] != base).any(), other
+    case = bc.random_case(spec["s148_open"])
+    assert (_chosen(case)[0] != _chosen(bc.shifted(case, segments=range(128, 140)))[0]).any()
+
+    c512 = _chosen(bc.random_case(spec["c512"]))[0]
+    assert ((c512 >= 6 * 64) & (c512 < 7 * 64)).any() and (c512 >= 7 * 64).any(), c512
+    assert (_chosen(bc.random_case(spec["c192"]))[0] >= 2 * 64).any()
+
+    case = bc.random_case(spec["hz_inf"])
+    assert case["par"]["horizon"] == np.inf
+    assert (_chosen(case)[0] != _chosen(dict(case, par=dict(case["par"], horizon=6.0)))[0]).sum() >= 2
+
+    case = bc.random_case(spec["commit2blk"])                    # item 4: what the strides of the packed tables will be
+    assert [(len(w["circles"]), len(w["segments"])) for w in case["worlds"]] == [(253, 28)] * 2 and 256 < 253 + 2 + 28 + 2 <= 512
+    case = bc.random_case(spec["ragged"])
+    assert [(len(w["rows"]), len(w["circles"]), len(w["segments"])) for w in case["worlds"]] == [(0, 4, 3), (2, 0, 11), (3, 7, 0)]
+
+
+def test_restatement_counts_and_counter():
+    """the restatement under counts outside the arrays (item 2): clamped to [0, length], rows beyond them neither read nor
+    written; and the draw counter as the uint32 the header says it is (item 7): 2^31 and beyond are draw numbers, not negative"""
+    case = bc.random_case(bc.RANDOM[4])
+    wd = case["worlds"][0]
+    args = (wd["circles"], wd["segments"], wd["rows"], wd["idx"], case["par"], case["robots"], case["prev"], case["radius"], -1, case["dirs"],
+            case["n_speed"], case["dt"])
+    full = ref.behave_world(*args)
+    over = ref.behave_world(*args, counts=(len(wd["circles"]) + 5, len(wd["segments"]) + 1, len(wd["rows"]) + 7))
+    for k in ("circles", "segments", "rows", "idx"):
+        assert over[k].tobytes() == full[k].tobytes()
+    none = ref.behave_world(*args, counts=(len(wd["circles"]), len(wd["segments"]), -3))
+    assert none["rows"].tobytes() == wd["rows"].tobytes() and none["circles"].tobytes() == wd["circles"].tobytes() and len(none["chosen"]) == 0
+    noseg = ref.behave_world(*args, counts=(len(wd["circles"]), -2, len(wd["rows"])))
+    assert noseg["segments"].tobytes() == wd["segments"].tobytes()
+    nC = len(wd["circles"])
+    for a in range(len(wd["rows"])):
+        if wd["idx"][a, 0] >= nC:
+            assert noseg["chosen"][a] == -1 and noseg["rows"][a].tobytes() == wd["rows"][a].tobytes()
+        else:
+            assert noseg["chosen"][a] >= 0
+    # the counter
+    for draws in (1 << 31, 4000000000, 0xFFFFFFFF):
+        w1 = bc._one(goal=(0.0, 0.0), wander=1, draws=int(np.uint32(draws).astype(np.int32)))
+        o = ref.run_case(bc.case("counter", [w1], None))[0]
+        assert tuple(o["rows"][0, 0:2]) == tuple(ref.draw_goal(11, 0, 0, draws, (-8.0, -8.0), (8.0, 8.0)))
+        assert int(o["idx"][0, 3]) & 0xFFFFFFFF == (draws + 1) & 0xFFFFFFFF and -(1 << 31) <= int(o["idx"][0, 3]) < (1 << 31)
 
 
 def test_restatement_two_discs_head_on_pass_and_arrive():

@@ -28,10 +28,13 @@ _PAIRS = {}
 
 
 # ---------------------------------------------------------------------------------------------------- the call on packed tables
-def device_behave(case, world_base=0, calls=1, pad=2):
-    """npa_world_behave on the worlds of a case, packed with `pad` poisoned rows beyond every count and one poisoned world, robot
-    and direction row behind every array.  Returns the list of per-world dict(circles, segments, rows, idx) after the call(s);
-    asserts that nothing beyond a count and no guard was written."""
+def device_behave(case, world_base=0, calls=1, pad=2, counts=None):
+    """npa_world_behave on the worlds of a case, packed with `pad` poisoned rows beyond every world's longest table and one
+    poisoned world, robot and direction row behind every array.  pad: a number, or a dict by array ("circles", "segments", "rows";
+    2 where it names none); 0 is allowed, and an array whose stride comes out 0 is passed as a null pointer.  counts: None, or a
+    dict by array of per-world numbers that go into the count arrays in place of the tables' lengths (the kernels clamp a count to
+    [0, stride]).  Returns the list of per-world dict(circles, segments, rows, idx) after the call(s), each as long as the world's
+    table; asserts that nothing at or beyond a clamped count, no guard and no input array was written."""
     import torch
     from neupan_amd import _lib
     from neupan_amd._lib import NpaBehaveParams
@@ -40,14 +43,15 @@ def device_behave(case, world_base=0, calls=1, pad=2):
     worlds, W = case["worlds"], len(case["worlds"])
     B = len(case["robots"])
     assert W in (1, B)
-    strides = {k: max(len(w[k]) for w in worlds) + pad for k in ("circles", "segments", "rows")}
+    pads = {k: (pad.get(k, 2) if isinstance(pad, dict) else pad) for k in ("circles", "segments", "rows")}
+    strides = {k: max(len(w[k]) for w in worlds) + pads[k] for k in ("circles", "segments", "rows")}
     host = dict(circles=np.full((W + 1, strides["circles"], 6), POISON), segments=np.full((W + 1, strides["segments"], 6), POISON),
                 rows=np.full((W + 1, strides["rows"], 10), POISON), idx=np.full((W + 1, strides["rows"], 4), IPOISON, dtype=np.int32))
-    counts = {k: np.full(W + 1, IPOISON, dtype=np.int32) for k in ("circles", "segments", "rows")}
+    count_h = {k: np.full(W + 1, IPOISON, dtype=np.int32) for k in ("circles", "segments", "rows")}
     for w, wd in enumerate(worlds):
         for k in ("circles", "segments", "rows"):
             host[k][w, :len(wd[k])] = wd[k]
-            counts[k][w] = len(wd[k])
+            count_h[k][w] = len(wd[k]) if counts is None or k not in counts else counts[k][w]
         host["idx"][w, :len(wd["idx"])] = wd["idx"]
     guard = lambda a, fill: np.concatenate([np.asarray(a, dtype=np.float64), np.full((1,) + np.shape(a)[1:], fill)], axis=0)
     st_h = guard(case["robots"], POISON)
@@ -56,14 +60,15 @@ def device_behave(case, world_base=0, calls=1, pad=2):
     dr_h = guard(case["dirs"].reshape(-1, 2), POISON)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
     dev = {k: up(v) for k, v in host.items()}
-    cnt = {k: up(v) for k, v in counts.items()}
+    cnt = {k: up(v) for k, v in count_h.items()}
     st, pv, dr = up(st_h), None if pv_h is None else up(pv_h), up(dr_h)
+    base = lambda k: _ptr(dev[k]) if strides[k] > 0 else None    # (a zero stride goes with a null pointer)
     p = case["par"]
     par = NpaBehaveParams(p["weight"], p["horizon"], p["robot_share"], (C.c_double * 2)(*p["range_low"]), (C.c_double * 2)(*p["range_high"]),
                           p["seed"], world_base, 0)
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     for _ in range(calls):
-        rc = lib.npa_world_behave(B, W, strides["circles"], strides["segments"], _ptr(dev["circles"]), _ptr(dev["segments"]),
+        rc = lib.npa_world_behave(B, W, strides["circles"], strides["segments"], base("circles"), base("segments"),
                                   _ptr(cnt["circles"]), _ptr(cnt["segments"]), strides["rows"], _ptr(dev["rows"]), _ptr(dev["idx"]),
                                   _ptr(cnt["rows"]), C.byref(par), _ptr(st), _ptr(pv), case["radius"], case["seg_limit"], n_dir,
                                   _ptr(dr) if n_dir else None, case["n_speed"] if n_dir else 0, case["dt"], stream)
@@ -71,7 +76,7 @@ def device_behave(case, world_base=0, calls=1, pad=2):
     torch.cuda.synchronize()
     got = {k: v.cpu().numpy() for k, v in dev.items()}
     for k in ("circles", "segments", "rows"):
-        np.testing.assert_array_equal(cnt[k].cpu().numpy(), counts[k])
+        np.testing.assert_array_equal(cnt[k].cpu().numpy(), count_h[k])
     np.testing.assert_array_equal(st.cpu().numpy(), st_h)
     np.testing.assert_array_equal(dr.cpu().numpy(), dr_h)
     if pv is not None:
@@ -79,8 +84,8 @@ def device_behave(case, world_base=0, calls=1, pad=2):
     out = []
     for w, wd in enumerate(worlds):
         for k, key in (("circles", "circles"), ("segments", "segments"), ("rows", "rows"), ("idx", "rows")):
-            n = len(wd[key])
-            assert (got[k][w, n:] == (IPOISON if k == "idx" else POISON)).all(), f"world {w}: {k} rows beyond the count were written"
+            n = min(max(int(count_h[key][w]), 0), strides[key])  # the count as the kernels clamp it
+            assert got[k][w, n:].tobytes() == host[k][w, n:].tobytes(), f"world {w}: {k} rows beyond the count were written"
         out.append({k: got[k][w, :len(wd["rows" if k == "idx" else k])] for k in ("circles", "segments", "rows", "idx")})
     for k in got:
         assert (got[k][W] == (IPOISON if k == "idx" else POISON)).all(), f"{k}: the guard world was written"
@@ -88,16 +93,22 @@ def device_behave(case, world_base=0, calls=1, pad=2):
 
 
 def check_untouched_columns(got, wd, want_rows):
-    """launch 2 writes the velocity columns of owned primitives only; launch 1 columns 0 - 3 and 9 of a row and `draws`"""
-    nC = len(wd["circles"])
+    """launch 2 writes the velocity columns of owned primitives only; launch 1 columns 0 - 3 and 9 of a row and `draws`.  Only a row
+    that is an agent (ref.agent_ok) owns primitives; every other row is bitwise its input"""
+    nC, nS = len(wd["circles"]), len(wd["segments"])
     owned = {}
     for a in range(len(wd["idx"])):
-        for p in range(int(wd["idx"][a, 0]), int(wd["idx"][a, 0] + wd["idx"][a, 1])):
-            owned[p] = a
+        f, n = int(wd["idx"][a, 0]), int(wd["idx"][a, 1])
+        if not ref.agent_ok(f, n, nC, nS):
+            assert got["rows"][a].tobytes() == np.asarray(wd["rows"])[a].tobytes(), f"row {a} is no agent and was written"
+            assert got["idx"][a].tobytes() == np.asarray(wd["idx"], dtype=np.int32)[a].tobytes(), f"row {a} is no agent and was written"
+            continue
+        for p in range(f, f + n):
+            owned.setdefault(p, a)                               # (the lowest agent row that claims it)
     for p in range(nC):
         np.testing.assert_array_equal(got["circles"][p, [0, 1, 2, 5]], wd["circles"][p, [0, 1, 2, 5]])
         np.testing.assert_array_equal(got["circles"][p, 3:5], want_rows[owned[p], 2:4] if p in owned else wd["circles"][p, 3:5])
-    for s in range(len(wd["segments"])):
+    for s in range(nS):
         np.testing.assert_array_equal(got["segments"][s, 0:4], wd["segments"][s, 0:4])
         np.testing.assert_array_equal(got["segments"][s, 4:6], want_rows[owned[nC + s], 2:4] if nC + s in owned else wd["segments"][s, 4:6])
     np.testing.assert_array_equal(got["rows"][:, 4:9], wd["rows"][:, 4:9])
@@ -105,18 +116,28 @@ def check_untouched_columns(got, wd, want_rows):
 
 
 # ---------------------------------------------------------------------------------------------------- decided cases
+def check_decided(case, got, expect):
+    """the device's tables against a decided case's literals, bit for bit; a row the case marks None is no agent"""
+    for w, (g, wd, exp) in enumerate(zip(got, case["worlds"], expect)):
+        want = np.array(wd["rows"])
+        assert len(exp) == len(wd["rows"])
+        for a, e in enumerate(exp):
+            what = (case["name"], w, a)
+            f, n = int(wd["idx"][a, 0]), int(wd["idx"][a, 1])
+            assert ref.agent_ok(f, n, len(wd["circles"]), len(wd["segments"])) == (e is not None), what
+            if e is None:
+                continue                                             # (check_untouched_columns: bitwise its input)
+            chosen, vel, goal, draws = e
+            assert g["rows"][a, 9] == chosen, (what, g["rows"][a])
+            assert tuple(g["rows"][a, 2:4]) == tuple(vel) and tuple(g["rows"][a, 0:2]) == tuple(goal), (what, g["rows"][a])
+            assert int(g["idx"][a, 3]) == draws, what
+            want[a, 2:4] = vel
+        check_untouched_columns(g, wd, want)
+
+
 def test_decided_cases():
     for case in bc.DECIDED:
-        got = device_behave(case)
-        for w, (g, wd, exp) in enumerate(zip(got, case["worlds"], case["expect"])):
-            want = np.array(wd["rows"])
-            for a, (chosen, vel, goal, draws) in enumerate(exp):
-                what = (case["name"], w, a)
-                assert g["rows"][a, 9] == chosen, (what, g["rows"][a])
-                assert tuple(g["rows"][a, 2:4]) == tuple(vel) and tuple(g["rows"][a, 0:2]) == tuple(goal), (what, g["rows"][a])
-                assert int(g["idx"][a, 3]) == draws, what
-                want[a, 2:4] = vel
-            check_untouched_columns(g, wd, want)
+        check_decided(case, device_behave(case), case["expect"])
 
 
 # ---------------------------------------------------------------------------------------------------- random worlds
@@ -126,6 +147,8 @@ def compare(case, got, res):
     for g, o, wd in zip(got, res, case["worlds"]):
         want = o["rows"].copy()
         for a in range(len(wd["rows"])):
+            if o["costs"][a] is None:
+                continue                                             # no agent: check_untouched_columns wants it bitwise its input
             agents += 1
             np.testing.assert_array_equal(g["rows"][a, 0:2], o["rows"][a, 0:2])          # the goal, redrawn or not
             assert int(g["idx"][a, 3]) == int(o["idx"][a, 3])
